@@ -14,7 +14,13 @@ the timed region; the loop is a replayed per-step hipGraph with device-side Phil
 (dpir_allgather_results), engine-owned buffers, engine stream -- inside the timed region (diffpir_amd.dist, the function the
 YAML driver uses).  Weights are synthetic.
 
-Rank 0 adds to the ONE JSON line (single-GPU runs; each part can be switched off):
+A plain run sets up, warms up, times the --steps steps and prints the ONE JSON line (metric, value, unit, ms_per_step, dtype, config).
+--dump-outputs DIR writes what the timed path computed in its last step as float32 .npy files (rank 0): `restored_f32.npy`, rank 0's
+x_0 [B,3,H,W] in [0,1], and `restored_u8.npy`, the all-gathered uint8 NHWC images [B*N,H,W,3] as float32; a larger output is cut to
+a fixed, seeded sample of images so that the files stay under 64 MB.  Inputs, weights and device noise are seeded: two builds run
+with the same arguments can be compared file for file.
+
+With --full, rank 0 adds to the JSON line (single-GPU runs; each part can be switched off):
   roofline       the dominant kernel class (3x3 convolutions): algorithmic FLOPs over the HIP-event duration of every
                  launch of the class in an instrumented pass (events on the engine stream), against the dense MFMA peak of
                  the arithmetic used; plus the WHOLE UNet step against the same peak (`unet_step_frac`, the north-star figure);
@@ -46,6 +52,7 @@ PROX_BYTES_PER_IMAGE = {1: 2_497_536, 4: 2_761_728}
 # HBM-side bytes per launch of the roofline kernel classes from the committed PMC passes (bench.py cannot run rocprofv3 on
 # itself): profiles/pmc_traffic.json is written by tools/pmc_traffic.py from profiles/r03/*_pmc_{FETCH,WRITE}_SIZE.txt (commands:
 # tools/gpu_prof_round.sh; FETCH_SIZE doubled per the gfx950 note).
+DUMP_BYTES = 60_000_000         # --dump-outputs: all files together stay under 64 MB
 PMC_TRAFFIC = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json"))) if os.path.exists(os.path.join(ROOT, "profiles", "pmc_traffic.json")) else {}
 
 
@@ -71,6 +78,9 @@ def parse():
                     help="arithmetic of the conv GEMMs for the headline value: f16x3 = fp32 operands split into f16 hi+lo, three f16 MFMAs "
                          "per product, fp32 accumulate (fp32-equivalent results, see DESIGN.md); f32 = v_mfma_f32_32x32x2_f32")
     ap.add_argument("--no-alt", action="store_true", help="skip the secondary measurement in the other precision mode")
+    ap.add_argument("--full", action="store_true", help="also run the secondary measurements (roofline, prox, degrade / metrics, DPS_y0, "
+                    "other precisions, configs[2], CPU baseline); a plain run times the headline workload only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (float32)")
     ap.add_argument("--cpu-threads", type=int, default=32, help="torch CPU threads for the oracle (all 256 host threads "
                     "oversubscribe MKL-DNN at B=1: 79 s/NFE measured vs ~1 s/NFE at 32)")
     a = ap.parse_args()
@@ -83,6 +93,19 @@ def parse():
         if getattr(a, kk) is None:
             setattr(a, kk, v)
     return a
+
+
+def dump_outputs(d, arrays):
+    """One float32 DIR/<name>.npy per output.  Where the outputs together exceed DUMP_BYTES, each keeps a fixed, seeded sample of its
+    images (axis 0), sized by its share of the total."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {kk: np.asarray(v, np.float32) for kk, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES:
+            n = max(1, min(a.shape[0], int(DUMP_BYTES * a.nbytes / total) // a[0].nbytes))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=n, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def make_problem(restore, synth, task, B, H, nfe, seed, blur="gaussian"):
@@ -267,6 +290,7 @@ def main():
     out_f32 = eng.empty((B, 3, H, H))
     out_u8 = eng.empty((B, H, H, 3), np.uint8)       # engine-owned send buffer of the one collective
     keep = {}
+    gathered = {}
 
     def one_step():
         # weak scaling: every rank restores its own B images (global indices [rank*B, (rank+1)*B)), then the ONE collective of
@@ -274,7 +298,7 @@ def main():
         restore.restore_batch(eng, cfg, y, k=k, mask=mask, labels=labels, noise_source="device", seed=1234, image_offset=rank * B,
                               use_graph=not args.no_graph, out_f32=out_f32, out_u8=out_u8, _cache=keep)
         eng.sync()
-        ddist.all_gather_results(out_u8, B * world, rank, world, engine=eng)
+        gathered["u8"] = ddist.all_gather_results(out_u8, B * world, rank, world, engine=eng)
 
     def fence():
         eng.sync()
@@ -294,6 +318,35 @@ def main():
     ranks_info = ddist.gather_rank_info(eng, local_rank)     # every rank's device / RCCL version, moved by the same collective as the results
     value = B * world * args.steps / elapsed
     headline_out = out_f32.numpy()           # before the instrumented passes below reuse the buffer
+    if args.dump_outputs and rank == 0:
+        u8 = gathered["u8"]
+        dump_outputs(args.dump_outputs, {"restored_f32": headline_out, "restored_u8": u8.numpy() if hasattr(u8, "numpy") else np.asarray(u8)})
+
+    def headline_line():
+        names = {"c2": "configs[1]" if world == 1 else f"configs[1] per GPU (weak scaling: batch {B} on each of {world} GPUs)", "c4": f"configs[3] (batch {B} per GPU; BASELINE quotes 256 images over 8 GPUs)",
+                 "c5": f"configs[4] (batch {B} per GPU; BASELINE quotes 64 images over 8 GPUs)"}
+        cfg_tag = (names[args.preset] if args.exact_preset else
+                   "configs[2] topology/task (reduced batch or NFE)" if (args.model, args.task) == ("imagenet256", "sr") else
+                   f"BASELINE {names[args.preset].split(' ')[0]} family, non-default flags")
+        psf = {"deblur": "61x61 motion PSF (seeded random walk)" if args.blur == "motion" else "61x61 Gaussian PSF",
+               "sr": "x4, bicubic PSF, FFT prox", "inpaint": "box mask"}[args.task]
+        return {"metric": f"restored images/sec @{args.nfe} NFE, {H}x{H}", "value": round(value, 4), "unit": "images/s",
+                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": round(elapsed / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak",
+                "vs_baseline": None,
+                "dtype": "f32" if args.precision == "f32" else "f32 (GEMMs as 3 x f16 MFMA on hi/lo-split fp32 operands, fp32 accumulate; exact-fp32-MFMA mode in alt_precision)",
+                "data": "synthetic",
+                "config": {"workload": f"{cfg_tag}: {args.model} topology {H}x{H} {args.task} ({psf}), {args.nfe} NFE, "
+                                       f"batch {B}/GPU, device Philox noise, hipGraph={'off' if args.no_graph else 'on'}",
+                           "global_batch": B * world, "nfe": args.nfe, "sharding": f"images x{world}, all_gather(u8) of results",
+                           "collective": coll_name, "ranks": ranks_info}}
+
+    if not args.full:           # a plain run: the headline figure only
+        if rank == 0:
+            print(json.dumps(headline_line()))
+        ddist.shutdown()
+        eng.close()
+        return
 
     extras = rank == 0 and world == 1
     roofline = conv_roofline(eng, B, H, args.precision, args.model) if rank == 0 else None
@@ -470,24 +523,7 @@ def main():
     cpu = cpu_baseline_c1(weights, args.cpu_threads) if extras and not args.no_cpu_baseline else None
 
     if rank == 0:
-        names = {"c2": "configs[1]" if world == 1 else f"configs[1] per GPU (weak scaling: batch {B} on each of {world} GPUs)", "c4": f"configs[3] (batch {B} per GPU; BASELINE quotes 256 images over 8 GPUs)",
-                 "c5": f"configs[4] (batch {B} per GPU; BASELINE quotes 64 images over 8 GPUs)"}
-        cfg_tag = (names[args.preset] if args.exact_preset else
-                   "configs[2] topology/task (reduced batch or NFE)" if (args.model, args.task) == ("imagenet256", "sr") else
-                   f"BASELINE {names[args.preset].split(' ')[0]} family, non-default flags")
-        psf = {"deblur": "61x61 motion PSF (seeded random walk)" if args.blur == "motion" else "61x61 Gaussian PSF",
-               "sr": "x4, bicubic PSF, FFT prox", "inpaint": "box mask"}[args.task]
-        line = {"metric": f"restored images/sec @{args.nfe} NFE, {H}x{H}", "value": round(value, 4), "unit": "images/s",
-                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                "ms_per_step": round(elapsed / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak",
-                "vs_baseline": None,
-                "dtype": "f32" if args.precision == "f32" else "f32 (GEMMs as 3 x f16 MFMA on hi/lo-split fp32 operands, fp32 accumulate; exact-fp32-MFMA mode in alt_precision)",
-                "data": "synthetic",
-                "config": {"workload": f"{cfg_tag}: {args.model} topology {H}x{H} {args.task} ({psf}), {args.nfe} NFE, "
-                                       f"batch {B}/GPU, device Philox noise, hipGraph={'off' if args.no_graph else 'on'}",
-                           "global_batch": B * world, "nfe": args.nfe, "sharding": f"images x{world}, all_gather(u8) of results",
-                           "collective": coll_name, "ranks": ranks_info},
-                "roofline": roofline, "roofline_prox": prox, "degrade_metrics": f1, "dps_y0": dps, "cpu_baseline": cpu, "config_c3": c3, "alt_precision": alt, "reduced_precision": reduced}
+        line = {**headline_line(), "roofline": roofline, "roofline_prox": prox, "degrade_metrics": f1, "dps_y0": dps, "cpu_baseline": cpu, "config_c3": c3, "alt_precision": alt, "reduced_precision": reduced}
         print(json.dumps(line))
     ddist.shutdown()
     if not eng_closed:

@@ -17,7 +17,7 @@ reference's source file with ``ast`` and runs them unmodified -- no restated
 loop glue -- and runs the reference's whole ``main()`` on the images and kernel
 files it ships.  The outputs are committed under ``tests/golden/`` (generators:
 ``oracle/gen_golden*.py``) and re-checked on every ``pytest`` run
-(``tests/test_oracle_golden.py``); where ``/root/reference`` is present the
-restatement is additionally compared with the reference executed live
-(``tests/test_oracle_vs_live_reference.py``).
+(``tests/test_oracle_golden.py``, and ``tests/test_oracle_vs_live_reference.py``
+over the executed ``test_rho`` outputs and step traces of
+``oracle/gen_golden_executed.py``).
 """

@@ -142,7 +142,7 @@ def test_bench_launch_line_two_ranks_on_one_gpu_gloo():
     env = dict(os.environ, DIFFPIR_BENCH_BACKEND="gloo", DIFFPIR_BENCH_DEVICE="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-           "--nfe", "6", "--batch", "2"]
+           "--nfe", "6", "--batch", "2", "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

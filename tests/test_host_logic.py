@@ -145,10 +145,12 @@ def test_product_weight_schema_equals_oracle_and_reference():
 def test_yaml_driver_accepts_reference_style_configs(tmp_path):
     """The driver's config surface: same flat keys as the reference's configs/*.yaml, same derived fields and sweeps."""
     from diffpir_amd import main_ddpir as drv
-    ref_dir = "/root/reference/configs"
+    import yaml
+    from oracle.gen_golden_executed import stored_configs
     paths = [os.path.join(ROOT, "configs", "engine_example.yaml")]
-    if os.path.isdir(ref_dir):
-        paths += [os.path.join(ref_dir, f) for f in ("deblur.yaml", "inpaint.yaml", "sisr.yaml")]
+    for f, d in sorted(stored_configs().items()):      # the reference's configs/{deblur,inpaint,sisr}.yaml, key / value pairs as stored
+        (tmp_path / f).write_text(yaml.safe_dump(d))
+        paths.append(str(tmp_path / f))
     for p in paths:
         c = drv.parse_config(p)
         lam, zeta = drv.sweeps(c)[0]

@@ -1,38 +1,26 @@
-"""CPU, build container only (skipped where /root/reference does not exist, i.e. on the GPU box): the reference's OWN loop -- `test_rho`,
-taken out of /root/reference/main_ddpir.py with `ast` and executed unmodified (oracle/ref_exec.py) -- against the oracle restatement, live,
-on every run of the CPU suite.  The committed fixtures (tests/golden/*.npz) were generated by the same machinery; this file re-executes the
-reference instead of trusting the files."""
+"""CPU: the reference's OWN loop -- `test_rho`, taken out of the reference's main_ddpir.py with `ast` and executed unmodified
+(oracle/ref_exec.py) -- against the oracle restatement.  What the executed reference produced is stored as data in
+tests/golden/executed_reference.npz (oracle/gen_golden_executed.py re-executes it where the reference tree is at hand), so these tests
+run on every checkout of the repository."""
 import numpy as np
 import pytest
 import torch
 
-from oracle import ref_import, unet_oracle as uo, diffpir_oracle as do
-
-pytestmark = pytest.mark.skipif(not ref_import.available(), reason="/root/reference is not present (GPU box): the reference cannot be executed here")
-
-
-def seeded(seed):
-    g = torch.Generator().manual_seed(seed)
-    return lambda like: torch.randn(like.shape, generator=g, dtype=torch.float32)
+from oracle import unet_oracle as uo, diffpir_oracle as do
+from oracle.gen_golden_executed import case, seeded
 
 
 @pytest.fixture(scope="module")
 def tiny():
-    from oracle import ref_exec
     hp = uo.tiny_hp()
-    sd = uo.synth_state_dict(hp, 0)
-    model, diffusion = ref_exec.build_unet(hp, sd)
-    return ref_exec, hp, sd, model, diffusion
+    return hp, uo.synth_state_dict(hp, 0)
 
 
-def test_the_pieces_executed_are_the_reference_lines_and_the_one_edit_is_one_statement(tiny):
-    ref_exec = tiny[0]
-    import ast
-    p = ref_exec.main_pieces()
-    assert p["lines"]["schedule"] == (184, 200) and p["lines"]["freeze"] == (236, 239) and p["lines"]["test_rho"] == (249, 536) and p["lines"]["sweep"] == (548, 580)
-    a, b = ast.unparse(p["test_rho"][0]).splitlines(), ast.unparse(p["test_rho_deblur"][0]).splitlines()
-    gone = [l for l in a if l not in b]
-    assert len(a) - len(b) == 1 and len(gone) == 1 and "k_4d = torch.einsum('ab,cd->abcd'" in gone[0]       # SURVEY quirk Q1, nothing else
+def test_the_pieces_executed_are_the_reference_lines_and_the_one_edit_is_one_statement(golden):
+    ex = golden("executed_reference")
+    lines = {piece: tuple(int(v) for v in ex[f"lines_{piece}"]) for piece in ("schedule", "freeze", "test_rho", "sweep")}
+    assert lines["schedule"] == (184, 200) and lines["freeze"] == (236, 239) and lines["test_rho"] == (249, 536) and lines["sweep"] == (548, 580)
+    assert int(ex["n_stmt_test_rho"]) - int(ex["n_stmt_test_rho_deblur"]) == 1 and int(ex["n_dropped"]) == 1 and bool(ex["dropped_is_q1"])     # SURVEY quirk Q1, nothing else
     # as shipped, a deblur batch cannot pass that statement
     with pytest.raises(RuntimeError):
         torch.einsum('ab,cd->abcd', torch.eye(3), torch.zeros(2, 5, 5))
@@ -40,25 +28,13 @@ def test_the_pieces_executed_are_the_reference_lines_and_the_one_edit_is_one_sta
 
 @pytest.mark.parametrize("name", ["deblur", "inpaint", "sr_cubic", "repaint", "dps_yt"])
 def test_oracle_equals_the_executed_reference_loop(tiny, golden, name):
-    ref_exec, hp, sd, model, diffusion = tiny
-    g = golden("loops")
-    k = mask = None
-    if name == "deblur":
-        cfg, y, k, seed = do.LoopConfig("deblur", 5, 12.75 / 255, 7.0, 0.3, eta=0.7), g["deblur_y"], g["deblur_k"], 43
-    elif name == "inpaint":
-        cfg, y, mask, seed = do.LoopConfig("inpaint", 6, 0.0, 1.0, 1.0), g["inpaint_y"], g["inpaint_mask"], 44
-    elif name == "repaint":
-        cfg, y, mask, seed = do.LoopConfig(task="inpaint", iter_num=6, noise_level_img=0.0, lambda_=1.0, zeta=1.0, generate_mode="repaint"), g["inpaint_y"], g["inpaint_mask"], 45
-    elif name == "sr_cubic":
-        cfg, y, seed = do.LoopConfig("sr", 5, 12.75 / 255, 6.0, 0.25, sf=4, sr_mode="cubic", inIter=2, gamma=0.5), g["sr_y"], 46
-        k = np.stack([golden("operators")["k_bic4"]] * 2)[:, None]
-    else:       # the mode whose rhos come from sqrt(beta / alpha), main_ddpir.py:279-283 -- at the reference's own lambda
-        cfg, y, seed = do.LoopConfig("sr", 10, 12.75 / 255, 6.0, 0.25, sf=4, sr_mode="cubic", generate_mode="DPS_yt"), g["sr_y"], 82
-        k = np.stack([golden("operators")["k_bic4"]] * 2)[:, None]
+    hp, sd = tiny
+    ex = golden("executed_reference")
+    cfg, y, k, mask, seed = case(golden, name)
     ty = torch.from_numpy(y)
     tk = None if k is None else torch.from_numpy(k)
     tm = None if mask is None else torch.from_numpy(mask).float()
-    ref = ref_exec.restore_ref(model, diffusion, cfg, ty, k=tk, mask=tm, noise_fn=seeded(seed)).numpy()
+    ref = ex[f"out_{name}"]
     if name == "dps_yt":
         ora = do.restore_dps_y0(sd, hp, cfg, ty, noise_fn=seeded(seed)).numpy()
     else:
@@ -68,21 +44,21 @@ def test_oracle_equals_the_executed_reference_loop(tiny, golden, name):
     print(f"{name}: oracle vs executed test_rho max |diff| {d:.3e} (output range [{ref.min():.2f}, {ref.max():.2f}])")
     assert np.isfinite(ref).all() and d <= 5e-6
     if name == "dps_yt":
-        tabs = ref_exec.reference_tables(ref_exec.yaml_for("sr", iter_num=10, lambda_=6.0, zeta=0.25, generate_mode="DPS_yt", sr_mode="cubic"))
         _, steps = do.step_tables(cfg)
-        assert all(float(st["tau"]) == float(tabs["rhos"][st["t_i"]]) for st in steps)       # the table DPS_yt divides by, bit for bit
+        assert all(float(st["tau"]) == float(ex["dps_yt_rhos"][st["t_i"]]) for st in steps)       # the table DPS_yt divides by, bit for bit
 
 
 @pytest.mark.parametrize("task", ["deblur", "sr"])
-def test_engine_schedule_and_sweep_equal_the_executed_reference(task):
+def test_engine_schedule_and_sweep_equal_the_executed_reference(golden, task):
     """The PRODUCT's host logic against the reference executed live: `diffpir_amd.main_ddpir.sweeps` (the lambda / zeta the YAML driver hands to
     the loop) and `diffpir_amd.schedule.build_steps` (the per-step t_i and tau the engine uploads) versus what the reference's own sweep +
     test_rho visit -- every `t_i` it calls the denoiser at and every `tau` it passes to `data_solution`, recorded by executing
-    main_ddpir.py:548-580 over a stand-in network (oracle/ref_exec.reference_step_trace)."""
-    from oracle import ref_exec
+    main_ddpir.py:548-580 over a stand-in network (oracle/ref_exec.reference_step_trace, stored in tests/golden/executed_reference.npz)."""
+    from oracle.gen_golden_executed import stored_yaml_for
     from diffpir_amd import main_ddpir as drv, schedule
-    yd = ref_exec.yaml_for(task, iter_num=20)
-    ts, taus = ref_exec.reference_step_trace(yd, (1, 3, 8, 8), sweep=True)
+    yd = stored_yaml_for(task, iter_num=20)
+    ex = golden("executed_reference")
+    ts, taus = ex[f"ts_{task}"], ex[f"taus_{task}"]
     cfg = drv.Config(dict(yd))
     cfg.noise_level_img = cfg.noise_level_img / 255.0
     cfg.sigma = max(0.001, cfg.noise_level_img)

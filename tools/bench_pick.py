@@ -1,4 +1,4 @@
-"""Print the few numbers of a bench.py JSON line that A/B runs compare.  usage: python bench.py ... | python tools/bench_pick.py"""
+"""Print the few numbers of a bench.py JSON line that A/B runs compare.  usage: python bench.py --full ... | python tools/bench_pick.py"""
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = d.get("roofline") or {}

@@ -7,4 +7,4 @@ tag=${1:-evidence}
 bash tools/gpu_prof_round.sh $tag
 bash tools/gpu_prof_bench.sh $tag
 out=$PWD/gpurun_out/$tag
-timeout 900 python bench.py > $out/bench_1gpu.json 2> $out/bench_1gpu.err; tail -c 600 $out/bench_1gpu.json; tail -2 $out/bench_1gpu.err
+timeout 900 python bench.py --full > $out/bench_1gpu.json 2> $out/bench_1gpu.err; tail -c 600 $out/bench_1gpu.json; tail -2 $out/bench_1gpu.err

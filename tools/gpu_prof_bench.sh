@@ -5,9 +5,10 @@
 # `roofline.class_ms_per_forward_instrumented`).  usage: tools/gpu_prof_bench.sh <tag>
 #   -> gpurun_out/<tag>/bench_kernel_trace.txt, bench_under_rocprof.json   (copy to profiles/rNN/bench_py_*)
 tag=$1; out=$PWD/gpurun_out/$tag; mkdir -p $out
+root=$PWD
 export TMPDIR=/tmp
 d=/tmp/prof_bench; rm -rf $d
-(cd /tmp && timeout 330 rocprofv3 --kernel-trace -d $d -o bench -- python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --no-c3 --no-alt --no-cpu-baseline) > $out/bench_under_rocprof.log 2>&1
+(cd /tmp && timeout 330 rocprofv3 --kernel-trace -d $d -o bench -- python $root/bench.py --full --steps 1 --warmup 1 --no-c3 --no-alt --no-cpu-baseline) > $out/bench_under_rocprof.log 2>&1
 echo "rc=$?" >> $out/bench_under_rocprof.log
 db=$(find $d -name "*.db" | head -1)
 if [ -n "$db" ]; then python tools/rocpd_summary.py $db --top 45 > $out/bench_kernel_trace.txt 2>&1; else echo "no db" > $out/bench_kernel_trace.txt; fi
