@@ -20,8 +20,12 @@ struct GnBwdArgs {
 };
 int gn_bwd_parts(int C, int Hs, int Ws);
 Status launch_gn_bwd(hipStream_t s, const GnBwdArgs& a, int B);
-// scal[0] = s (power of two, max|x| * s in [512, 1024)), scal[1] = 1 / s, prm[0 .. n_prm) = {0, s, 0, 0}; part: scratch of 512 floats
-Status launch_grad_scale(hipStream_t s, const float* x, size_t total, float* part, float* scal, float4* prm, int n_prm);
+// x: B images of per_img floats.  Per image a power of two s_n with max|x_n| * s_n in [512, 1024); scal[0] = s_min (the largest image's),
+// scal[1] = 1 / s_min; sn[0 .. B) = s_n, sn[B .. 2B) = s_min / s_n; prm[n * C + c] = {0, s_n, 0, 0}.  part: scratch of B * grad_scale_parts(B) floats
+int grad_scale_parts(int B);
+Status launch_grad_scale(hipStream_t s, const float* x, int B, size_t per_img, float* part, float* scal, float* sn, float4* prm, int C);
+// x[n] *= f[n] (f = sn + B above: the images the epilogue's 1 / s_min did not fully un-scale)
+Status launch_grad_unscale(hipStream_t s, float* x, int B, size_t per_img, const float* f);
 Status launch_accum_adj(hipStream_t s, const float* src, int Cs, int c0, float* dst, int Cd, int mode, int B, int Hs, int Ws, bool acc);
 Status launch_attention_bwd(hipStream_t s, const float* qkv, const float* dAtt, float* dqkv, float* P, float* dP, int B, int C, int T);
 

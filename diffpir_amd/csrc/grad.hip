@@ -238,11 +238,15 @@ Status launch_accum_adj(hipStream_t s, const float* src, int Cs, int c0, float* 
 }
 
 // f16 dgrad (unet_bwd.hip): gradients span many orders of magnitude, the f16 operand split does not -- dY is brought to
-// max|dY| * s in [512, 1024) with a power of two s before the split (exactly what the loader does to the weights) and the convolution
-// epilogue multiplies by 1 / s.  Stage 1: per-workgroup max; stage 2: s, 1 / s and the uniform {0, s, 0, 0} table act_split / conv5 read.
-__global__ __launch_bounds__(256) void absmax_kernel(const float* x, size_t total, float* part) {
+// max|dY_n| * s_n in [512, 1024) with a power of two s_n PER IMAGE before the split (exactly what the loader does to the weights).  One scale
+// for the whole batch pushed an image whose gradient is 1e-6 of another's toward the f16 subnormals (4.3e-4 per-image error against float64
+// autograd, tests/test_gpu_grad_batches.py case c).  The convolution epilogue multiplies by 1 / s_min, s_min the scale of the batch's largest
+// image; launch_grad_unscale then multiplies the other images' planes by s_min / s_n (a power of two: exact).
+// Stage 1: per-(image, part) max; stage 2: s_n, s_min, 1 / s_min, the per-image factors and the {0, s_n, 0, 0} table act_split / conv5 read.
+__global__ __launch_bounds__(256) void absmax_kernel(const float* x, size_t per_img, float* part) {
+    x += (size_t)blockIdx.y * per_img;                  // image blockIdx.y
     float m = 0.f;
-    const size_t n4 = total >> 2;                       // tensors here are [B, C, H, W] with H * W % 4 == 0 or tiny
+    const size_t n4 = (per_img & 3) ? 0 : per_img >> 2;   // float4 runs only where every image starts 16-byte aligned
     const float4* x4 = reinterpret_cast<const float4*>(x);
     const size_t stride = (size_t)gridDim.x * 256;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += 4 * stride) {     // four requests in flight per thread (max is order-free)
@@ -252,43 +256,70 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* x, size_t tota
 #pragma unroll
         for (int q = 0; q < 4; ++q) m = fmaxf(fmaxf(m, fmaxf(fabsf(v[q].x), fabsf(v[q].y))), fmaxf(fabsf(v[q].z), fabsf(v[q].w)));
     }
-    for (size_t i = (n4 << 2) + (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) m = fmaxf(m, fabsf(x[i]));
+    for (size_t i = (n4 << 2) + (size_t)blockIdx.x * 256 + threadIdx.x; i < per_img; i += stride) m = fmaxf(m, fabsf(x[i]));
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
     __shared__ float red[4];
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    if (threadIdx.x == 0) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
-__global__ __launch_bounds__(256) void grad_scale_kernel(const float* part, int nparts, float* scal, float4* prm, int n_prm) {
-    __shared__ float sh;
-    float m = 0.f;
-    for (int i = threadIdx.x; i < nparts; i += 256) m = fmaxf(m, part[i]);
+// one workgroup.  sn[0 .. B): s_n (0 for an all-zero image), sn[B .. 2B): s_min / s_n (1 for an all-zero image)
+__global__ __launch_bounds__(256) void grad_scale_kernel(const float* part, int nparts, int B, float* scal, float* sn, float4* prm, int C) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int n = wave; n < B; n += 4) {
+        float m = 0.f;
+        for (int i = lane; i < nparts; i += 64) m = fmaxf(m, part[(size_t)n * nparts + i]);
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    __shared__ float red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-        float sc = 1.0f;
-        if (mx > 0.f && mx < 3.0e38f) {
-            int ex = (int)floorf(log2f(1024.0f / mx));
-            ex = ex < -100 ? -100 : (ex > 100 ? 100 : ex);
-            sc = exp2f((float)ex);
-            while (mx * sc >= 1024.0f) sc *= 0.5f;
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        if (lane == 0) {
+            float sc = 0.f;
+            if (m > 0.f && m < 3.0e38f) {
+                int ex = (int)floorf(log2f(1024.0f / m));
+                ex = ex < -100 ? -100 : (ex > 100 ? 100 : ex);
+                sc = exp2f((float)ex);
+                while (m * sc >= 1024.0f) sc *= 0.5f;
+            } else if (m != 0.f) {
+                sc = 1.0f;                              // inf / NaN: left as they are (the range counter reports them)
+            }
+            sn[n] = sc;
         }
-        scal[0] = sc; scal[1] = 1.0f / sc;
-        sh = sc;
     }
     __syncthreads();
-    const float sc = sh;
-    for (int i = threadIdx.x; i < n_prm; i += 256) prm[i] = make_float4(0.f, sc, 0.f, 0.f);
+    __shared__ float smin;
+    if (threadIdx.x == 0) {
+        float v = 0.f;
+        for (int n = 0; n < B; ++n) if (sn[n] > 0.f && (v == 0.f || sn[n] < v)) v = sn[n];
+        if (v == 0.f) v = 1.0f;
+        smin = v;
+        scal[0] = v; scal[1] = 1.0f / v;
+    }
+    __syncthreads();
+    const float s0 = smin;
+    for (int n = threadIdx.x; n < B; n += 256) sn[B + n] = sn[n] > 0.f ? s0 / sn[n] : 1.0f;
+    for (int i = threadIdx.x; i < B * C; i += 256) {
+        const float v = sn[i / C];
+        prm[i] = make_float4(0.f, v > 0.f ? v : s0, 0.f, 0.f);
+    }
 }
-Status launch_grad_scale(hipStream_t s, const float* x, size_t total, float* part, float* scal, float4* prm, int n_prm) {
-    const int nparts = 512;
-    hipLaunchKernelGGL(absmax_kernel, dim3(nparts), dim3(256), 0, s, x, total, part);
-    hipLaunchKernelGGL(grad_scale_kernel, dim3(1), dim3(256), 0, s, part, nparts, scal, prm, n_prm);
+int grad_scale_parts(int B) { return B >= 512 ? 1 : 512 / B; }
+Status launch_grad_scale(hipStream_t s, const float* x, int B, size_t per_img, float* part, float* scal, float* sn, float4* prm, int C) {
+    const int nparts = grad_scale_parts(B);
+    hipLaunchKernelGGL(absmax_kernel, dim3(nparts, B), dim3(256), 0, s, x, per_img, part);
+    hipLaunchKernelGGL(grad_scale_kernel, dim3(1), dim3(256), 0, s, part, nparts, B, scal, sn, prm, C);
+    DPIR_HIP(hipGetLastError());
+    return Status{};
+}
+// x[n] *= f[n]; the workgroups of an image with f[n] == 1 (every image, when the batch has no magnitude spread) return at once
+__global__ __launch_bounds__(256) void grad_unscale_kernel(float* x, size_t per_img, const float* f) {
+    const float v = f[blockIdx.y];
+    if (v == 1.0f) return;
+    x += (size_t)blockIdx.y * per_img;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < per_img; i += (size_t)gridDim.x * 256) x[i] *= v;
+}
+Status launch_grad_unscale(hipStream_t s, float* x, int B, size_t per_img, const float* f) {
+    const size_t wg = (per_img + 255) / 256;
+    hipLaunchKernelGGL(grad_unscale_kernel, dim3((unsigned)(wg < 1024 ? wg : 1024), B), dim3(256), 0, s, x, per_img, f);
     DPIR_HIP(hipGetLastError());
     return Status{};
 }

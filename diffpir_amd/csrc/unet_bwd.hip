@@ -6,8 +6,8 @@
 //                                 -> conv1 dgrad -> (resampling adjoint) GN1+SiLU backward -> gradient of the (concat) input
 //   AttentionBlock (:299-305):    dout -> residual + proj_out dgrad -> QKV attention backward -> qkv dgrad -> GroupNorm backward
 // A convolution's dgrad is a FORWARD convolution kernel on the transposed, spatially flipped weight pack built at load time: in the
-// f16 precisions conv6 / conv5 (operand-split MFMA; dY is scaled by a run-time power of two before the split because gradients span
-// many orders of magnitude, the epilogue undoes it), in f32 mode -- and for shapes those kernels do not tile -- conv2 / conv.
+// f16 precisions conv6 / conv5 (operand-split MFMA; dY is scaled by a run-time power of two per image before the split because gradients
+// span many orders of magnitude, the epilogue and launch_grad_unscale undo it), in f32 mode -- and for shapes those kernels do not tile -- conv2 / conv.
 // GroupNorm / SiLU / attention / resampling adjoints are in grad.hip (fp32, fp64 reductions).  A tensor with several consumers
 // (block inputs, skip connections) has one gradient buffer: the first contribution writes, later ones accumulate, in tape order --
 // deterministic.
@@ -39,7 +39,7 @@ struct Bwd {
 
     // dX [B, cin, H, W] = dgrad of cw applied to dY [B, cout, H, W]
     // reuse_scale: dY is the tensor the PREVIOUS dgrad call scaled (a ResBlock's dout feeds the skip projection's and conv2's dgrad back to back):
-    // its absmax / power-of-two scale / table are still in the shared buffers
+    // its absmax / power-of-two scales / table are still in the shared buffers
     Status dgrad(const ConvW& cw, const float* dY, float* dX, int H, int W, bool reuse_scale = false) {
         if (!cw.wT) return Status{DPIR_ERR_STATE, "gradient mode was not enabled before dpir_load_unet (dpir_enable_grad)"};
         static const bool f16_env = !(getenv("DPIR_DGRAD_F32") && atoi(getenv("DPIR_DGRAD_F32")) != 0);      // A/B switch (tools/, tests)
@@ -47,43 +47,24 @@ struct Bwd {
         const bool use6 = f16_env && cw.w16T && cw.ks == 3 && conv6_supported(H, W);
         const bool use5 = f16_env && cw.w16T && cw.ks == 1 && conv5_supported(B, cw.cin, H, W);
         if (use6 || use5) {
-            // f16 operand-split dgrad on the forward's MFMA kernels.  Gradients span many orders of magnitude: dY is scaled by a run-time
-            // power of two (max|dY| s in [512, 1024)) before the split and the epilogue multiplies by 1 / s (grad.hip launch_grad_scale).
+            // f16 operand-split dgrad on the forward's MFMA kernels.  Gradients span many orders of magnitude, also between the images of a
+            // batch: dY_n is scaled by a run-time power of two s_n (max|dY_n| s_n in [512, 1024)) before the split, the epilogue multiplies by
+            // 1 / s_min and launch_grad_unscale by s_min / s_n (grad.hip launch_grad_scale).
             const int C = cw.cout;
-            float *part = nullptr, *scal = nullptr; float4* prm = nullptr;
-            DPIR_TRY(ws.getT("bwd#absmax", (size_t)512, &part));
+            float *part = nullptr, *scal = nullptr, *sn = nullptr; float4* prm = nullptr;
+            DPIR_TRY(ws.getT("bwd#absmax", (size_t)B * grad_scale_parts(B), &part));
             DPIR_TRY(ws.getT("bwd#scal", (size_t)4, &scal));
+            DPIR_TRY(ws.getT("bwd#sn", (size_t)2 * B, &sn));
             DPIR_TRY(ws.getT("bwd#sprm", (size_t)B * 2048, &prm));
             if (C > 2048) return invalid("dgrad: more than 2048 channels");
             if (!(reuse_scale && scaled == dY && scaled_f16)) {
                 ProfScope ps(&e->prof, PC_ELEM);
-                DPIR_TRY(launch_grad_scale(s, dY, (size_t)B * C * H * W, part, scal, prm, B * C));
+                DPIR_TRY(launch_grad_scale(s, dY, B, (size_t)C * H * W, part, scal, sn, prm, C));
             }
             scaled = dY; scaled_f16 = true;
-            if (use5) {
-                Conv5Args a5;
-                a5.src = CatSrc{dY, C, nullptr, 0}; a5.prm = prm; a5.w16 = cw.w16T; a5.w16_scale = cw.w16T_scale;
-                a5.bias = zeros; a5.out = dX; a5.res = nullptr; a5.B = B; a5.Cout = cw.cin; a5.H = H; a5.W = W;
-                a5.range_ctr = e->range_ctr; a5.x1 = x1; a5.out_scale_dev = scal + 1;
-                ProfScope ps(&e->prof, PC_CONV1);
-                return launch_conv5(s, a5);
-            }
-            const int C8 = 2 * ((C + 15) / 16);
-            const size_t plane = (size_t)B * C8 * H * W * 16;
-            if (plane >= ((size_t)1 << 32)) return invalid("dgrad: split plane exceeds the 4 GiB buffer-descriptor range; reduce the batch");
-            char* s16 = nullptr;
-            DPIR_TRY(ws.getT("act#s16", 2 * plane, &s16));
-            {
-                ProfScope ps(&e->prof, PC_ELEM);
-                DPIR_TRY(launch_act_split(s, CatSrc{dY, C, nullptr, 0}, prm, 0, B, H, W, s16, x1 ? nullptr : s16 + plane, e->range_ctr));
-            }
-            Conv6Args a6;
-            a6.x1 = x1; a6.xhi = s16; a6.xlo = s16 + plane; a6.w16 = cw.w16T; a6.w16_scale = cw.w16T_scale;
-            a6.bias = zeros; a6.out = dX; a6.res = nullptr; a6.res_mode = 0;
-            a6.B = B; a6.Cin = C; a6.Cout = cw.cin; a6.H = H; a6.W = W;
-            a6.partial = partial; a6.partial_capacity = partial_cap; a6.out_scale_dev = scal + 1;
-            ProfScope ps(&e->prof, PC_CONV3);
-            return launch_conv6(s, a6);
+            DPIR_TRY(dgrad_f16(cw, dY, dX, H, W, use5, x1, prm, scal));
+            ProfScope ps(&e->prof, PC_ELEM);
+            return launch_grad_unscale(s, dX, B, (size_t)cw.cin * H * W, sn + B);
         }
         scaled = nullptr; scaled_f16 = false;
         ConvArgs a;
@@ -93,6 +74,34 @@ struct Bwd {
         a.partial = partial; a.partial_capacity = partial_cap;
         ProfScope ps(&e->prof, cw.ks == 3 ? PC_CONV3 : PC_CONV1);
         return launch_conv(s, a);
+    }
+    // the convolution of a scaled dY: conv5 (1x1) or act_split + conv6 (3x3)
+    Status dgrad_f16(const ConvW& cw, const float* dY, float* dX, int H, int W, bool use5, bool x1, const float4* prm, const float* scal) {
+        const int C = cw.cout;
+        if (use5) {
+            Conv5Args a5;
+            a5.src = CatSrc{dY, C, nullptr, 0}; a5.prm = prm; a5.w16 = cw.w16T; a5.w16_scale = cw.w16T_scale;
+            a5.bias = zeros; a5.out = dX; a5.res = nullptr; a5.B = B; a5.Cout = cw.cin; a5.H = H; a5.W = W;
+            a5.range_ctr = e->range_ctr; a5.x1 = x1; a5.out_scale_dev = scal + 1;
+            ProfScope ps(&e->prof, PC_CONV1);
+            return launch_conv5(s, a5);
+        }
+        const int C8 = 2 * ((C + 15) / 16);
+        const size_t plane = (size_t)B * C8 * H * W * 16;
+        if (plane >= ((size_t)1 << 32)) return invalid("dgrad: split plane exceeds the 4 GiB buffer-descriptor range; reduce the batch");
+        char* s16 = nullptr;
+        DPIR_TRY(ws.getT("act#s16", 2 * plane, &s16));
+        {
+            ProfScope ps(&e->prof, PC_ELEM);
+            DPIR_TRY(launch_act_split(s, CatSrc{dY, C, nullptr, 0}, prm, 0, B, H, W, s16, x1 ? nullptr : s16 + plane, e->range_ctr));
+        }
+        Conv6Args a6;
+        a6.x1 = x1; a6.xhi = s16; a6.xlo = s16 + plane; a6.w16 = cw.w16T; a6.w16_scale = cw.w16T_scale;
+        a6.bias = zeros; a6.out = dX; a6.res = nullptr; a6.res_mode = 0;
+        a6.B = B; a6.Cin = C; a6.Cout = cw.cin; a6.H = H; a6.W = W;
+        a6.partial = partial; a6.partial_capacity = partial_cap; a6.out_scale_dev = scal + 1;
+        ProfScope ps(&e->prof, PC_CONV3);
+        return launch_conv6(s, a6);
     }
     Status gn_bwd(const CatSrc& x, int Hs, int Ws, const float4* prm, const float2* st, const float* dA, int mode, float* ga, bool acc_a, float* gb,
                   bool acc_b, const float* extra = nullptr) {

@@ -202,25 +202,25 @@ def synth_state_dict(hp: UNetHP, seed: int = 0) -> Dict[str, torch.Tensor]:
 
 
 # ------------------------------------------------------------------ forward
-def timestep_embedding(t: torch.Tensor, dim: int, max_period: float = 10000.0):
+def timestep_embedding(t: torch.Tensor, dim: int, max_period: float = 10000.0, dtype: torch.dtype = torch.float32):
     """nn.py:103-121: [cos(t f) | sin(t f)], f_i = exp(-ln(max_period) i / half)."""
     half = dim // 2
-    freqs = torch.exp(-math.log(max_period) * torch.arange(half, dtype=torch.float32) / half)
-    args = t[:, None].float() * freqs[None]
+    freqs = torch.exp(-math.log(max_period) * torch.arange(half, dtype=dtype) / half)
+    args = t[:, None].to(dtype) * freqs[None]
     e = torch.cat([torch.cos(args), torch.sin(args)], dim=-1)
     if dim % 2:
         e = torch.cat([e, torch.zeros_like(e[:, :1])], dim=-1)
     return e
 
 
-def _gn(sd, p, x):
-    return F.group_norm(x.float(), 32, sd[p + ".weight"], sd[p + ".bias"], eps=1e-5)
+def _gn(sd, p, x, dt):
+    return F.group_norm(x.to(dt), 32, sd[p + ".weight"], sd[p + ".bias"], eps=1e-5)
 
 
-def _resblock(sd, p, rec, x, emb):
+def _resblock(sd, p, rec, x, emb, dt):
     """unet.py:236-256 with use_scale_shift_norm=True, resblock_updown=True, dropout in eval."""
     _, cin, cout, mode = rec
-    h = F.silu(_gn(sd, p + ".in_layers.0", x))
+    h = F.silu(_gn(sd, p + ".in_layers.0", x, dt))
     if mode == "down":                       # unet.py:136 avg_pool2d k=2 s=2 on h and x
         h = F.avg_pool2d(h, 2, 2)
         x = F.avg_pool2d(x, 2, 2)
@@ -230,56 +230,58 @@ def _resblock(sd, p, rec, x, emb):
     h = F.conv2d(h, sd[p + ".in_layers.2.weight"], sd[p + ".in_layers.2.bias"], padding=1)
     e = F.linear(F.silu(emb), sd[p + ".emb_layers.1.weight"], sd[p + ".emb_layers.1.bias"])
     scale, shift = torch.chunk(e[:, :, None, None], 2, dim=1)
-    h = _gn(sd, p + ".out_layers.0", h) * (1 + scale) + shift
+    h = _gn(sd, p + ".out_layers.0", h, dt) * (1 + scale) + shift
     h = F.conv2d(F.silu(h), sd[p + ".out_layers.3.weight"], sd[p + ".out_layers.3.bias"], padding=1)
     if cin != cout:
         x = F.conv2d(x, sd[p + ".skip_connection.weight"], sd[p + ".skip_connection.bias"])
     return x + h
 
 
-def _attention(sd, p, x, head_ch):
+def _attention(sd, p, x, head_ch, dt):
     """unet.py:299-305 + QKVAttentionLegacy 337-354: heads split BEFORE q|k|v."""
     b, c, hh, ww = x.shape
     xf = x.reshape(b, c, -1)
-    qkv = F.conv1d(_gn(sd, p + ".norm", xf), sd[p + ".qkv.weight"], sd[p + ".qkv.bias"])
+    qkv = F.conv1d(_gn(sd, p + ".norm", xf, dt), sd[p + ".qkv.weight"], sd[p + ".qkv.bias"])
     nh = c // head_ch
     T = xf.shape[-1]
     q, k, v = qkv.reshape(b * nh, 3 * head_ch, T).split(head_ch, dim=1)
     s = 1.0 / math.sqrt(math.sqrt(head_ch))
     w = torch.einsum("bct,bcs->bts", q * s, k * s)
-    w = torch.softmax(w.float(), dim=-1)
+    w = torch.softmax(w.to(dt), dim=-1)
     a = torch.einsum("bts,bcs->bct", w, v).reshape(b, c, T)
     h = F.conv1d(a, sd[p + ".proj_out.weight"], sd[p + ".proj_out.bias"])
     return (xf + h).reshape(b, c, hh, ww)
 
 
-def _run_layers(sd, prefix, blk, h, emb, hp, taps):
+def _run_layers(sd, prefix, blk, h, emb, hp, taps, dt):
     for j, rec in enumerate(blk):
         p = f"{prefix}.{j}"
         if rec[0] == "conv":
             h = F.conv2d(h, sd[p + ".weight"], sd[p + ".bias"], padding=1)
         elif rec[0] == "res":
-            h = _resblock(sd, p, rec, h, emb)
+            h = _resblock(sd, p, rec, h, emb, dt)
         else:
-            h = _attention(sd, p, h, hp.num_head_channels)
+            h = _attention(sd, p, h, hp.num_head_channels, dt)
         if taps is not None:
             taps[p] = h
     return h
 
 
 def unet_forward(sd, hp: UNetHP, x: torch.Tensor, t: torch.Tensor, y: Optional[torch.Tensor] = None,
-                 taps: Optional[dict] = None) -> torch.Tensor:
+                 taps: Optional[dict] = None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """unet.py:634-663.  x [B,3,H,W] fp32, t [B] int64 -> [B,out_channels,H,W].
     `taps`, if given, collects every layer's output keyed by its state-dict prefix.
-    Runs without autograd unless x requires grad (the DPS modes differentiate through the network, main_ddpir.py:370-373)."""
+    Runs without autograd unless x requires grad (the DPS modes differentiate through the network, main_ddpir.py:370-373).
+    `dtype` is the arithmetic of every intermediate: fp32, the reference's, by default.  torch.float64 turns the restatement into a
+    high-precision checker; the weights then come as {k: v.double()}."""
     with torch.set_grad_enabled(bool(x.requires_grad)):
-        return _unet_forward(sd, hp, x, t, y, taps)
+        return _unet_forward(sd, hp, x, t, y, taps, dtype)
 
 
-def _unet_forward(sd, hp, x, t, y, taps):
+def _unet_forward(sd, hp, x, t, y, taps, dt):
     assert (y is not None) == hp.class_cond
     inp, mid, out = build_plan(hp)
-    emb = timestep_embedding(t, hp.model_channels)
+    emb = timestep_embedding(t, hp.model_channels, dtype=dt)
     emb = F.linear(emb, sd["time_embed.0.weight"], sd["time_embed.0.bias"])
     emb = F.linear(F.silu(emb), sd["time_embed.2.weight"], sd["time_embed.2.bias"])
     if hp.class_cond:
@@ -287,15 +289,15 @@ def _unet_forward(sd, hp, x, t, y, taps):
     if taps is not None:
         taps["emb"] = emb
     hs = []
-    h = x.float()
+    h = x.to(dt)
     for i, blk in enumerate(inp):
-        h = _run_layers(sd, f"input_blocks.{i}", blk, h, emb, hp, taps)
+        h = _run_layers(sd, f"input_blocks.{i}", blk, h, emb, hp, taps, dt)
         hs.append(h)
-    h = _run_layers(sd, "middle_block", mid, h, emb, hp, taps)
+    h = _run_layers(sd, "middle_block", mid, h, emb, hp, taps, dt)
     for i, blk in enumerate(out):
         h = torch.cat([h, hs.pop()], dim=1)
-        h = _run_layers(sd, f"output_blocks.{i}", blk, h, emb, hp, taps)
-    h = F.silu(_gn(sd, "out.0", h))
+        h = _run_layers(sd, f"output_blocks.{i}", blk, h, emb, hp, taps, dt)
+    h = F.silu(_gn(sd, "out.0", h, dt))
     return F.conv2d(h, sd["out.2.weight"], sd["out.2.bias"], padding=1)
 
 

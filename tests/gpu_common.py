@@ -39,6 +39,16 @@ def rel_err(a, b):
     return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-30))
 
 
+def per_image_err(a, b):
+    """(worst error, its image index) of max|a_n - b_n| / max|b_n| over the images n of [B, ...] arrays.  rel_err divides by the max over
+    the whole batch: an image whose values are much smaller than the others' can be wrong without it showing there."""
+    a = np.asarray(a, np.float64).reshape(len(a), -1)
+    b = np.asarray(b, np.float64).reshape(len(b), -1)
+    e = np.abs(a - b).max(axis=1) / (np.abs(b).max(axis=1) + 1e-30)
+    n = int(np.argmax(e))
+    return float(e[n]), n
+
+
 _ORACLE_CACHE = {}
 
 
