@@ -402,8 +402,28 @@ int dpir_unet_vjp(dpir_engine* e, const float* x, const int64_t* t_host, const i
 }
 
 // ------------------------------------------------------------------------------------------ FFT prox
-static Status prox_precalc(dpir_engine* e, const float* y, const float* k, int kh, int kw, int sf, int B, int H, int W, ProxState* st) {
+// Shape checks of every prox path, before anything is allocated or launched.  The generic kernels (fft.hip) hold a 16-column strip of H + 1 rows in
+// LDS: H <= 1024 (135 KB at 1024; 2048 would need 264 KB of the 160 KB per CU).
+static Status prox_check(int sf, int B, int H, int W) {
+    if (B < 1) return invalid("pre_calculate: B must be >= 1");
     if (sf < 1 || H % sf || W % sf) return invalid("pre_calculate: image size not divisible by sf");
+    if (fft2_supported(H, W, sf)) return Status{};
+    if (sf != 1 && sf != 2 && sf != 4 && sf != 8 && sf != 16) return Status{DPIR_ERR_UNSUPPORTED, "fft prox: sf must be 1, 2, 4, 8 or 16"};
+    auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
+    if (!pow2(H) || !pow2(W) || H < 16 || W < 16 || H > 1024 || W > 2048)
+        return Status{DPIR_ERR_UNSUPPORTED, "fft prox: H must be a power of two in [16, 1024] and W one in [16, 2048]"};
+    return Status{};
+}
+
+static Status prox_check_psf(int kh, int kw, int H, int W) {
+    if (kh < 1 || kw < 1) return invalid("pre_calculate: empty PSF");
+    if (kh > H || kw > W) return invalid("PSF larger than the image");
+    return Status{};
+}
+
+static Status prox_precalc(dpir_engine* e, const float* y, const float* k, int kh, int kw, int sf, int B, int H, int W, ProxState* st) {
+    DPIR_TRY(prox_check(sf, B, H, W));
+    DPIR_TRY(prox_check_psf(kh, kw, H, W));
     hipStream_t s = e->stream;
     ProfScope ps(&e->prof, PC_FFT);
     if (st->half) {
@@ -460,6 +480,7 @@ static Status prox_precalc(dpir_engine* e, const float* y, const float* k, int k
 }
 
 static Status prox_alloc(dpir_engine* e, int sf, int B, int H, int W, ProxState* st) {
+    DPIR_TRY(prox_check(sf, B, H, W));
     st->B = B; st->H = H; st->W = W; st->sf = sf;
     st->half = fft2_supported(H, W, sf);
     st->colmajor = e->prox_mode == 1 && fft4_supported(H, W, sf);
@@ -493,7 +514,9 @@ int dpir_prox_fft_precalc(dpir_engine* e, const float* y, const float* k, int kh
     *out = nullptr;
     dpir_prox* p = new (std::nothrow) dpir_prox();
     if (!p) return fail(e, Status{DPIR_ERR_NOMEM, "out of host memory"});
-    Status s = prox_alloc(e, sf, B, H, W, &p->st);
+    Status s = prox_check(sf, B, H, W);                   // every shape check before anything is allocated
+    if (s.ok()) s = prox_check_psf(kh, kw, H, W);
+    if (s.ok()) s = prox_alloc(e, sf, B, H, W, &p->st);
     if (s.ok()) s = prox_precalc(e, y, k, kh, kw, sf, B, H, W, &p->st);
     if (!s.ok()) { prox_release(&p->st); delete p; return fail(e, s); }
     *out = p;

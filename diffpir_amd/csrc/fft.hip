@@ -13,6 +13,7 @@
 // inverse column transforms.
 #include "common.h"
 #include "elem.h"
+#include "fft_regs.h"
 
 namespace dpir {
 
@@ -140,8 +141,8 @@ __global__ __launch_bounds__(256) void fft_cols_kernel(float2* buf, SolveArgs a,
         const float inv_n = 1.0f / (float)(sf * sf);
         for (int it = threadIdx.x; it < tc * tr; it += 256) {
             int cb = it % tc, rb = it / tc;
-            float2 fbr = make_float2(0.f, 0.f);
-            float invw = 0.f;
+            PairSum<float2, 9> sx;               // the sf^2 <= 256 aliases summed pairwise (fft_regs.h): the mean is cancelled against FR / alpha
+            PairSum<float, 9> sw;
             for (int i = 0; i < sf; ++i)
                 for (int j = 0; j < sf; ++j) {
                     int r = rb * sf + i, c = cb * sf + j;
@@ -150,10 +151,11 @@ __global__ __launch_bounds__(256) void fft_cols_kernel(float2* buf, SolveArgs a,
                     float2 y = FBFy[gi];
                     fr.x += y.x; fr.y += y.y;
                     d[c * HS + r] = fr;
-                    float2 x1 = cmul(FB[gi], fr);
-                    fbr.x += x1.x; fbr.y += x1.y;
-                    invw += F2B[gi];
+                    sx.add(cmul(FB[gi], fr));
+                    sw.add(F2B[gi]);
                 }
+            float2 fbr = sx.sum();
+            float invw = sw.sum();
             fbr.x *= inv_n; fbr.y *= inv_n; invw *= inv_n;
             float den = invw + a.alpha;
             float2 q = make_float2(fbr.x / den, fbr.y / den);
@@ -178,9 +180,11 @@ __global__ __launch_bounds__(256) void fft_cols_kernel(float2* buf, SolveArgs a,
 static int ilog2i(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 static bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
+// H <= 1024: the column kernels hold CW columns of H + 1 points in LDS, ((H/2) + CW*(H+1))*8 bytes = 135 KB at H = 1024 (264 KB at 2048 would
+// exceed the 160 KB of a CU).  The row kernels hold one W-point row (W <= 2048: 24 KB).
 static Status check_dims(int H, int W) {
-    if (!pow2(H) || !pow2(W) || H < 16 || W < 16 || H > 2048 || W > 2048)
-        return Status{DPIR_ERR_UNSUPPORTED, "fft prox: H and W must be powers of two in [16, 2048]"};
+    if (!pow2(H) || !pow2(W) || H < 16 || W < 16 || H > 1024 || W > 2048)
+        return Status{DPIR_ERR_UNSUPPORTED, "fft prox: H must be a power of two in [16, 1024] and W one in [16, 2048]"};
     return Status{};
 }
 

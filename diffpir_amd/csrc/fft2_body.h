@@ -360,30 +360,31 @@ __device__ __forceinline__ void cfft_cols_body(float2* sm2, int plane, int strip
         const float2* FB = a.FB + (size_t)n_img * N * WP + col;
         const float2* FBFy = a.FBFy + (size_t)plane * N * WP + col;
         // v <- FR = FBFy + F(alpha x); rows u + a Hs of one thread are k2 = k2p + KH a: fold them while FB * FR is formed
-        float2 sacc[KH];
 #pragma unroll
-        for (int i = 0; i < KH; ++i) sacc[i] = make_float2(0.f, 0.f);
+        for (int k2 = 0; k2 < RJ; ++k2) v[k2] = cadd(PF ? fy[k2] : FBFy[(size_t)(t + R * k2) * WP], v[k2]);
 #pragma unroll
-        for (int k2 = 0; k2 < RJ; ++k2) {
-            const size_t off = (size_t)(t + R * k2) * WP;
-            v[k2] = cadd(PF ? fy[k2] : FBFy[off], v[k2]);
-            sacc[k2 % KH] = cadd(sacc[k2 % KH], cmul2(FB[off], v[k2]));
+        for (int i = 0; i < KH; ++i) {                                    // the sf row aliases k2 = i + KH a of each folded value, summed pairwise
+            float2 ts[sf];
+#pragma unroll
+            for (int al = 0; al < sf; ++al) ts[al] = cmul2(FB[(size_t)(t + R * (i + KH * al)) * WP], v[i + KH * al]);
+            sfold[c * Hs + t + R * i] = tree_sum<sf>(ts);
         }
-#pragma unroll
-        for (int i = 0; i < KH; ++i) sfold[c * Hs + t + R * i] = sacc[i];
         __syncthreads();
         const float inv_n = 1.0f / (float)(sf * sf);
         for (int item = threadIdx.x; item < ngrp * Hs; item += THREADS) {
             const int ql = item / Hs, p = item - ql * Hs, pm = (Hs - p) % Hs;
             const int q = s0 / sf + ql;
-            float2 acc = make_float2(0.f, 0.f);
+            float2 ts[sf];                                                // ... and the sf column aliases, pairwise: a tree over all sf^2
+#pragma unroll
             for (int b = 0; b < sf; ++b) {
                 const int cc = ql * sf + b;
                 const int cm = a.slot_col[s0 + cc];
-                if (cm < 0) continue;
-                if (cm >> 16) { const float2 z = sfold[cc * Hs + pm]; acc.x += z.x; acc.y -= z.y; }       // mirrored alias: conj of the mirrored row
-                else acc = cadd(acc, sfold[cc * Hs + p]);
+                float2 z = make_float2(0.f, 0.f);
+                if (cm >= 0 && (cm >> 16)) { z = sfold[cc * Hs + pm]; z.y = -z.y; }                   // mirrored alias: conj of the mirrored row
+                else if (cm >= 0) z = sfold[cc * Hs + p];
+                ts[b] = z;
             }
+            const float2 acc = tree_sum<sf>(ts);
             float2 r = make_float2(0.f, 0.f);
             if (q < QW) {
                 const float den = a.invW[((size_t)n_img * Hs + p) * QW + q] + alpha;

@@ -64,14 +64,16 @@ __global__ void fold_f2b4_kernel(const float* F2B, const int* slot_col, int N, i
         const int p = (int)((i / QW) % Hs);
         const size_t n = i / ((size_t)QW * Hs);
         const float* pl = F2B + n * (size_t)NC * N;
-        float acc = 0.f;
-        for (int b = 0; b < sf; ++b) {
+        // pairwise over the sf x sf aliases (sf 2 or 4), as the solve sums FB * FR (fft_regs.h, tree_sum)
+        auto alias_col = [&](int b) -> float {
             const int slot = sf * q + b;
             const int cm = slot < NC ? slot_col[slot] : -1;
-            if (cm < 0) continue;
+            if (cm < 0) return 0.f;
             const int base_row = (cm >> 16) ? (Hs - p) % Hs : p;          // |FB|^2 is real: the mirrored alias is just the mirrored row
-            for (int a = 0; a < sf; ++a) acc += pl[(size_t)slot * N + pos4(base_row + a * Hs)];
-        }
+            auto at = [&](int a) { return pl[(size_t)slot * N + pos4(base_row + a * Hs)]; };
+            return sf == 2 ? at(0) + at(1) : (at(0) + at(1)) + (at(2) + at(3));
+        };
+        const float acc = sf == 2 ? alias_col(0) + alias_col(1) : (alias_col(0) + alias_col(1)) + (alias_col(2) + alias_col(3));
         invW[i] = acc / (float)(sf * sf);
     }
 }
@@ -172,6 +174,7 @@ Status launch_cfft4_cols(hipStream_t s, const float2* tw, int N, float2* buf, co
     return invalid("cfft4_cols: N must be 256 or 512");
 }
 Status launch_fold_f2b4(hipStream_t s, const float* F2B, const int* slot_col, int N, int NC, int sf, float* invW, int B) {
+    if (sf != 2 && sf != 4) return invalid("fold_f2b4: sf must be 2 or 4");
     const size_t total = (size_t)B * (N / sf) * (N / sf / 2 + 1);
     hipLaunchKernelGGL(fold_f2b4_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, F2B, slot_col, N, NC, sf, invW, total);
     DPIR_HIP(hipGetLastError());

@@ -308,16 +308,15 @@ __device__ __forceinline__ void cols4_item_body(float2* lds, float2* fold, int p
         constexpr int Hs = N / SF, KH = R / SF;                         // KH folded values per lane
         const int QW = N / SF / 2 + 1;
         const int n_img = plane / 3;
-        float2 sacc[KH];
 #pragma unroll
-        for (int i = 0; i < KH; ++i) sacc[i] = make_float2(0.f, 0.f);
+        for (int j = 0; j < R; ++j) v[j] = cadd(fy[j], v[j]);
 #pragma unroll
-        for (int j = 0; j < R; ++j) {
-            v[j] = cadd(fy[j], v[j]);
-            sacc[j % KH] = cadd(sacc[j % KH], cmul2(fb[j], v[j]));
+        for (int i = 0; i < KH; ++i) {                                  // the SF row aliases j = i + KH a of each folded value, summed pairwise
+            float2 t[SF];
+#pragma unroll
+            for (int al = 0; al < SF; ++al) t[al] = cmul2(fb[i + KH * al], v[i + KH * al]);
+            fold[wave * Hs + lane + 64 * i] = tree_sum<SF>(t);
         }
-#pragma unroll
-        for (int i = 0; i < KH; ++i) fold[wave * Hs + lane + 64 * i] = sacc[i];
         __syncthreads();
         // R[p] of this slot's fold group: sum over the group's sf slots (mirrored aliases: conj of the mirrored row), / (sf^2 (invW + alpha))
         const int cmine = live ? a.slot_col[s] : -1;
@@ -330,15 +329,17 @@ __device__ __forceinline__ void cols4_item_body(float2* lds, float2* fold, int p
             const int p0 = lane + 64 * i;                               // the row (mod Hs) this lane needs R for ...
             const int p = mir ? (Hs - p0) % Hs : p0;                    // ... which for a mirrored slot is R[(Hs - p) % Hs] conjugated
             const int pm = (Hs - p) % Hs;
-            float2 acc = make_float2(0.f, 0.f);
+            float2 t[SF];                                               // ... and the SF column aliases, pairwise: a tree over all SF^2
 #pragma unroll
             for (int b = 0; b < SF; ++b) {
                 const int sb = q * SF + b;
                 const int cm = sb < NC ? a.slot_col[sb] : -1;
-                if (cm < 0) continue;
-                if (cm >> 16) { const float2 z = fold[(w0 + b) * Hs + pm]; acc.x += z.x; acc.y -= z.y; }
-                else acc = cadd(acc, fold[(w0 + b) * Hs + p]);
+                float2 z = make_float2(0.f, 0.f);
+                if (cm >= 0 && (cm >> 16)) { z = fold[(w0 + b) * Hs + pm]; z.y = -z.y; }
+                else if (cm >= 0) z = fold[(w0 + b) * Hs + p];
+                t[b] = z;
             }
+            const float2 acc = tree_sum<SF>(t);
             float2 rr = make_float2(0.f, 0.f);
             if (live && q < QW) {
                 const float den = a.invW[((size_t)n_img * Hs + p) * QW + q] + alpha;

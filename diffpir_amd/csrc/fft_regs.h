@@ -6,6 +6,35 @@ __device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(
 __device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
 __device__ __forceinline__ float2 cmul2(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 __device__ __forceinline__ float2 cmulc2(float2 a, float2 b) { return make_float2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }  // a*conj(b)
+// Pairwise (balanced-tree) sum of a power-of-two number of terms fed one at a time, the way torch's reductions sum.  The sf > 1 solve needs it
+// (utils_sisr.py:70-71, torch.mean over the sf^2 aliases): the alias mean of FB * FR is cancelled against FR and the remainder divided by alpha
+// (down to ~1e-6), so the mean must be as exact as the reference's.  A sequential fp32 sum of sf^2 terms is off by ~sf^2 ulp even when the terms
+// are equal (1 x 1 PSF: FB = 1, F(S^T y) periodic over the aliases), which a tree sums exactly.  Feed zeros for absent terms: the tree stays
+// balanced.  At most 2^(LEVELS - 1) terms.
+__device__ __forceinline__ float padd(float a, float b) { return a + b; }
+__device__ __forceinline__ float2 padd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+template <typename T, int LEVELS> struct PairSum {
+    T s[LEVELS];
+    int top = 0;
+    unsigned n = 0;
+    __device__ __forceinline__ void add(T x) {
+        for (unsigned k = n++; k & 1u; k >>= 1) x = padd(s[--top], x);
+        s[top++] = x;
+    }
+    __device__ __forceinline__ T sum() const {      // a power-of-two count leaves one partial sum
+        T r = s[top - 1];
+        for (int i = top - 2; i >= 0; --i) r = padd(s[i], r);
+        return r;
+    }
+};
+// The same tree over N terms held in registers (N a compile-time power of two): t[0] <- sum, t is overwritten.
+template <int N, typename T> __device__ __forceinline__ T tree_sum(T* t) {
+#pragma unroll
+    for (int h = N / 2; h >= 1; h /= 2)
+#pragma unroll
+        for (int i = 0; i < h; ++i) t[i] = padd(t[i], t[i + h]);
+    return t[0];
+}
 template <bool INV> __device__ __forceinline__ float2 mul_mi(float2 a) {   // a * (-i) forward, a * (+i) inverse
     return INV ? make_float2(-a.y, a.x) : make_float2(a.y, -a.x);
 }

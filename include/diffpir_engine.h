@@ -136,7 +136,12 @@ int dpir_unet_read_tap(dpir_engine* e, const char* layer, float* host_dst, size_
 
 /* ---- data-fidelity operators ------------------------------------------------------------- */
 /* Replaces sr.pre_calculate(y, k, sf) (utils/utils_sisr.py:78-95): y_dev [B,3,H/sf,W/sf] in [0,1],
- * k_dev [B,1,kh,kw]; builds FB, F2B, FBFy (full c2c spectra of size HxW) in an engine-owned object. */
+ * k_dev [B,1,kh,kw]; builds FB, F2B, FBFy (full c2c spectra of size HxW) in an engine-owned object.
+ * Supported: 256 x 256 and 512 x 512 and 64 x 64 with sf 1, 2 or 4; otherwise H a power of two in [16, 1024], W one in [16, 2048] and
+ * sf 1, 2, 4, 8 or 16 (the generic kernels of csrc/fft.hip: H is bounded by the LDS of their column pass).  Checked here before anything
+ * is allocated or launched: DPIR_ERR_INVALID when sf does not divide H and W, B < 1, or the PSF is empty or larger than the image;
+ * DPIR_ERR_UNSUPPORTED for any other sf or image size.  dpir_run_loop applies the same shape checks before it allocates the spectra (after
+ * its own workspaces) and the PSF check before the first prox launch (after the loop's initialisation launches). */
 int dpir_prox_fft_precalc(dpir_engine* e, const float* y_dev, const float* k_dev, int kh, int kw,
                           int sf, int B, int H, int W, dpir_prox** out);
 void dpir_prox_free(dpir_engine* e, dpir_prox* p);
