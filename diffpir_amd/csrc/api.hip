@@ -3,7 +3,6 @@
 // the header; this file only validates, dispatches to the launchers and keeps the error string.
 #include "engine.h"
 #include "grad.h"
-#include "fft4_wave.h"
 #include <math.h>
 #include <string.h>
 #include <stdlib.h>
@@ -25,8 +24,6 @@ static int fail(dpir_engine* e, const Status& s) {
         if (_h != hipSuccess)                                                             \
             return fail((e), Status{DPIR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_h)}); \
     } while (0)
-
-static void prox_release(dpir::ProxState* st);
 
 // f16x3 operand range guard: called where the ABI synchronises anyway (dpir_sync, D2H copies).  A non-zero count means
 // at least that many wave-lanes clamped an activation to the f16 range since the last check: the images are wrong.
@@ -88,61 +85,6 @@ __global__ void range_clear_kernel(unsigned long long* ctr) { *ctr &= ~((1ull <<
 static void range_clear(dpir_engine* e) {
     if (e->range_ctr && e->precision != 0) hipLaunchKernelGGL(range_clear_kernel, dim3(1), dim3(1), 0, e->stream, e->range_ctr);
 }
-static int ilog2u(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-
-Status dpir_engine::fft_plan(int N, FftPlan* out) {
-    auto it = fft_plans.find(N);
-    if (it != fft_plans.end()) { *out = it->second; return Status{}; }
-    if (N < 2 || (N & (N - 1))) return Status{DPIR_ERR_UNSUPPORTED, "FFT size must be a power of two"};
-    std::vector<float2> tw(N / 2);
-    for (int k = 0; k < N / 2; ++k) {
-        double a = -2.0 * M_PI * (double)k / (double)N;
-        tw[k] = make_float2((float)cos(a), (float)sin(a));
-    }
-    FftPlan p; p.N = N; p.logN = ilog2u(N);
-    void* d = nullptr;
-    DPIR_HIP(hipMalloc(&d, tw.size() * sizeof(float2)));
-    DPIR_HIP(hipMemcpy(d, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
-    p.tw = reinterpret_cast<float2*>(d);
-    fft_plans[N] = p;
-    *out = p;
-    return Status{};
-}
-
-Status dpir_engine::fft2_table(int N, const float2** out) {
-    auto it = fft2_tw.find(N);
-    if (it != fft2_tw.end()) { *out = it->second; return Status{}; }
-    std::vector<float2> tw(N);
-    for (int m = 0; m < N; ++m) {
-        double a = -2.0 * M_PI * (double)m / (double)N;
-        tw[m] = make_float2((float)cos(a), (float)sin(a));
-    }
-    if (N == 256 || N == 512) { tw.resize(N + wave_tw_count(N)); wave_tw_fill(N, tw.data(), tw.data() + N); }   // fft4_wave.h: per-lane constants behind the table
-    void* d = nullptr;
-    DPIR_HIP(hipMalloc(&d, tw.size() * sizeof(float2)));
-    DPIR_HIP(hipMemcpy(d, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
-    fft2_tw[N] = reinterpret_cast<float2*>(d);
-    *out = fft2_tw[N];
-    return Status{};
-}
-
-Status dpir_engine::fft2_map(int N, int sf, const Fft2Map** out, bool colmajor) {
-    auto key = std::make_pair(N, sf + (colmajor ? 16 : 0));
-    auto it = fft2_maps.find(key);
-    if (it == fft2_maps.end()) {
-        Fft2Map m;
-        if (colmajor) fft4_build_map(N, sf, m.h_slot_col, m.h_col_slot);
-        else fft2_build_map(N, sf, m.h_slot_col, m.h_col_slot);
-        DPIR_HIP(hipMalloc((void**)&m.slot_col, m.h_slot_col.size() * sizeof(int)));
-        DPIR_HIP(hipMalloc((void**)&m.col_slot, m.h_col_slot.size() * sizeof(int)));
-        DPIR_HIP(hipMemcpy(m.slot_col, m.h_slot_col.data(), m.h_slot_col.size() * sizeof(int), hipMemcpyHostToDevice));
-        DPIR_HIP(hipMemcpy(m.col_slot, m.h_col_slot.data(), m.h_col_slot.size() * sizeof(int), hipMemcpyHostToDevice));
-        it = fft2_maps.emplace(key, std::move(m)).first;
-    }
-    *out = &it->second;
-    return Status{};
-}
-
 Status dpir_engine::resizer(int in_len, int sf, ResizerTab* out) {
     auto key = std::make_pair(in_len, sf);
     auto it = resizers.find(key);
@@ -159,6 +101,26 @@ Status dpir_engine::resizer(int in_len, int sf, ResizerTab* out) {
     t.w = reinterpret_cast<float*>(dw); t.idx = reinterpret_cast<int*>(di);
     resizers[key] = t;
     *out = t;
+    return Status{};
+}
+
+Status dpir::capture_graph(dpir_engine* e, const std::function<Status()>& record, hipGraphExec_t* out) {
+    bool prof_on = e->prof.on, taps_on = e->collect_taps;
+    e->prof.on = false; e->collect_taps = false; e->ws.frozen = true;
+    hipGraph_t graph = nullptr;
+    Status cs;
+    hipError_t herr = hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal);
+    if (herr != hipSuccess) cs = Status{DPIR_ERR_HIP, std::string("hipStreamBeginCapture: ") + hipGetErrorString(herr)};
+    else {
+        cs = record();
+        herr = hipStreamEndCapture(e->stream, &graph);
+        if (cs.ok() && herr != hipSuccess) cs = Status{DPIR_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(herr)};
+    }
+    e->ws.frozen = false; e->prof.on = prof_on; e->collect_taps = taps_on;
+    if (!cs.ok()) { if (graph) (void)hipGraphDestroy(graph); return cs; }
+    herr = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    if (herr != hipSuccess) return Status{DPIR_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(herr)};
     return Status{};
 }
 
@@ -212,9 +174,7 @@ void dpir_destroy(dpir_engine* e) {
     (void)hipStreamSynchronize(e->stream);
     unet_free(e);
     e->ws.release();
-    for (auto& kv : e->fft_plans) (void)hipFree(kv.second.tw);
-    for (auto& kv : e->fft2_tw) (void)hipFree(kv.second);
-    for (auto& kv : e->fft2_maps) { (void)hipFree(kv.second.slot_col); (void)hipFree(kv.second.col_slot); }
+    e->prox_cache.release();
     for (auto& kv : e->resizers) { (void)hipFree(kv.second.w); (void)hipFree(kv.second.idx); }
     for (void* p : e->user_allocs) (void)hipFree(p);
     e->invalidate_graphs();
@@ -401,124 +361,15 @@ int dpir_unet_vjp(dpir_engine* e, const float* x, const int64_t* t_host, const i
     return DPIR_OK;
 }
 
-// ------------------------------------------------------------------------------------------ FFT prox
-// Shape checks of every prox path, before anything is allocated or launched.  The generic kernels (fft.hip) hold a 16-column strip of H + 1 rows in
-// LDS: H <= 1024 (135 KB at 1024; 2048 would need 264 KB of the 160 KB per CU).
-static Status prox_check(int sf, int B, int H, int W) {
-    if (B < 1) return invalid("pre_calculate: B must be >= 1");
-    if (sf < 1 || H % sf || W % sf) return invalid("pre_calculate: image size not divisible by sf");
-    if (fft2_supported(H, W, sf)) return Status{};
-    if (sf != 1 && sf != 2 && sf != 4 && sf != 8 && sf != 16) return Status{DPIR_ERR_UNSUPPORTED, "fft prox: sf must be 1, 2, 4, 8 or 16"};
-    auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
-    if (!pow2(H) || !pow2(W) || H < 16 || W < 16 || H > 1024 || W > 2048)
-        return Status{DPIR_ERR_UNSUPPORTED, "fft prox: H must be a power of two in [16, 1024] and W one in [16, 2048]"};
-    return Status{};
-}
-
-static Status prox_check_psf(int kh, int kw, int H, int W) {
-    if (kh < 1 || kw < 1) return invalid("pre_calculate: empty PSF");
-    if (kh > H || kw > W) return invalid("PSF larger than the image");
-    return Status{};
-}
-
-static Status prox_precalc(dpir_engine* e, const float* y, const float* k, int kh, int kw, int sf, int B, int H, int W, ProxState* st) {
-    DPIR_TRY(prox_check(sf, B, H, W));
-    DPIR_TRY(prox_check_psf(kh, kw, H, W));
-    hipStream_t s = e->stream;
-    ProfScope ps(&e->prof, PC_FFT);
-    if (st->half) {
-        // half-spectrum register-FFT path (fft2.hip): FB = rfft2(p2o-embedded PSF), FBFy = conj(FB) * rfft2(y)
-        const float2* tw = nullptr;
-        DPIR_TRY(e->fft2_table(W, &tw));
-        float* psf = nullptr;
-        DPIR_TRY(e->ws.getT("prox#psf", (size_t)B * H * W, &psf));
-        SolveArgs none{};
-        DPIR_TRY(launch_psf_embed_real(s, k, kh, kw, psf, B, H, W));
-        if (st->colmajor) {      // wave-per-transform kernels, column-major spectra (fft4.hip)
-            const int NC = st->WP;
-            DPIR_TRY(launch_rfft4_rows(s, tw, W, psf, 1.f, 0.f, 1.f, nullptr, st->FB, B, NC, nullptr, 0, st->slot_col));
-            DPIR_TRY(launch_cfft4_cols(s, tw, W, st->FB, none, false, B, NC));
-            const float* ysrc4 = y;
-            if (sf > 1) {
-                float* yup = nullptr;
-                DPIR_TRY(e->ws.getT("prox#yup", (size_t)B * 3 * H * W, &yup));
-                DPIR_TRY(launch_upsample_real(s, y, sf, yup, B * 3, H / sf, W / sf));
-                ysrc4 = yup;
-            }
-            DPIR_TRY(launch_rfft4_rows(s, tw, W, ysrc4, 1.f, 0.f, 1.f, nullptr, st->FBFy, B * 3, NC, nullptr, 0, st->slot_col));
-            DPIR_TRY(launch_cfft4_cols(s, tw, W, st->FBFy, none, false, B * 3, NC));
-            DPIR_TRY(launch_precalc_finish2(s, st->FB, st->FBFy, st->F2B, B, (size_t)H * NC));
-            if (sf > 1) DPIR_TRY(launch_fold_f2b4(s, st->F2B, st->slot_col, W, NC, sf, st->invW, B));
-            return Status{};
-        }
-        DPIR_TRY(launch_rfft_rows(s, tw, psf, 1.f, 0.f, 1.f, nullptr, st->FB, B, W, nullptr, 0, st->slot_col));
-        DPIR_TRY(launch_cfft_cols(s, tw, st->FB, none, false, B, H));
-        const float* ysrc = y;
-        if (sf > 1) {      // F(zero-stuffed y) (utils_sisr.py:84-85)
-            float* yup = nullptr;
-            DPIR_TRY(e->ws.getT("prox#yup", (size_t)B * 3 * H * W, &yup));
-            DPIR_TRY(launch_upsample_real(s, y, sf, yup, B * 3, H / sf, W / sf));
-            ysrc = yup;
-        }
-        DPIR_TRY(launch_rfft_rows(s, tw, ysrc, 1.f, 0.f, 1.f, nullptr, st->FBFy, B * 3, W, nullptr, 0, st->slot_col));
-        DPIR_TRY(launch_cfft_cols(s, tw, st->FBFy, none, false, B * 3, H));
-        DPIR_TRY(launch_precalc_finish2(s, st->FB, st->FBFy, st->F2B, B, (size_t)H * st->WP));
-        if (sf > 1) DPIR_TRY(launch_fold_f2b(s, st->F2B, st->slot_col, H, sf, st->invW, B));
-        return Status{};
-    }
-    FftPlan ph, pw;
-    DPIR_TRY(e->fft_plan(H, &ph));
-    DPIR_TRY(e->fft_plan(W, &pw));
-    DPIR_TRY(launch_psf_embed(s, k, kh, kw, st->FB, B, H, W));
-    DPIR_TRY(launch_fft_rows(s, pw, st->FB, nullptr, 1.f, 0.f, B, H, W, false));
-    DPIR_TRY(launch_fft_cols(s, ph, st->FB, B, H, W, false));
-    DPIR_TRY(launch_upsample_embed(s, y, sf, st->FBFy, B * 3, H / sf, W / sf));
-    DPIR_TRY(launch_fft_rows(s, pw, st->FBFy, nullptr, 1.f, 0.f, B * 3, H, W, false));
-    DPIR_TRY(launch_fft_cols(s, ph, st->FBFy, B * 3, H, W, false));
-    DPIR_TRY(launch_precalc_finish(s, st->FB, st->FBFy, st->F2B, B, H, W));
-    return Status{};
-}
-
-static Status prox_alloc(dpir_engine* e, int sf, int B, int H, int W, ProxState* st) {
-    DPIR_TRY(prox_check(sf, B, H, W));
-    st->B = B; st->H = H; st->W = W; st->sf = sf;
-    st->half = fft2_supported(H, W, sf);
-    st->colmajor = e->prox_mode == 1 && fft4_supported(H, W, sf);
-    st->WP = st->colmajor ? fft4_columns(W, sf) : (st->half ? fft2_padded_width(W) : W);
-    size_t hw = (size_t)H * st->WP;
-    if (hipMalloc((void**)&st->FB, B * hw * sizeof(float2)) != hipSuccess ||
-        hipMalloc((void**)&st->F2B, B * hw * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&st->FBFy, 3 * B * hw * sizeof(float2)) != hipSuccess)
-        return Status{DPIR_ERR_NOMEM, "pre_calculate: hipMalloc failed"};
-    st->invW = nullptr; st->slot_col = nullptr; st->col_slot = nullptr; st->h_col_slot = nullptr;
-    if (st->half && sf > 1) {
-        const dpir_engine::Fft2Map* m = nullptr;
-        DPIR_TRY(e->fft2_map(W, sf, &m, st->colmajor));
-        st->slot_col = m->slot_col; st->col_slot = m->col_slot; st->h_col_slot = &m->h_col_slot;
-        if (hipMalloc((void**)&st->invW, (size_t)B * (H / sf) * (W / sf / 2 + 1) * sizeof(float)) != hipSuccess)
-            return Status{DPIR_ERR_NOMEM, "pre_calculate: hipMalloc failed"};
-    }
-    return Status{};
-}
-static void prox_release(ProxState* st) {
-    if (st->FB) (void)hipFree(st->FB);
-    if (st->F2B) (void)hipFree(st->F2B);
-    if (st->FBFy) (void)hipFree(st->FBFy);
-    if (st->invW) (void)hipFree(st->invW);
-    st->FB = nullptr; st->F2B = nullptr; st->FBFy = nullptr; st->invW = nullptr;
-}
-
+// ------------------------------------------------------------------------------------------ FFT prox (prox.hip)
 int dpir_prox_fft_precalc(dpir_engine* e, const float* y, const float* k, int kh, int kw, int sf, int B, int H, int W, dpir_prox** out) {
     if (!e || !y || !k || !out) return fail(e, invalid("dpir_prox_fft_precalc: null argument"));
     (void)hipSetDevice(e->device);
     *out = nullptr;
     dpir_prox* p = new (std::nothrow) dpir_prox();
     if (!p) return fail(e, Status{DPIR_ERR_NOMEM, "out of host memory"});
-    Status s = prox_check(sf, B, H, W);                   // every shape check before anything is allocated
-    if (s.ok()) s = prox_check_psf(kh, kw, H, W);
-    if (s.ok()) s = prox_alloc(e, sf, B, H, W, &p->st);
-    if (s.ok()) s = prox_precalc(e, y, k, kh, kw, sf, B, H, W, &p->st);
-    if (!s.ok()) { prox_release(&p->st); delete p; return fail(e, s); }
+    Status s = prox_create(e, y, k, kh, kw, sf, B, H, W, &p->st);
+    if (!s.ok()) { delete p; return fail(e, s); }
     *out = p;
     return DPIR_OK;
 }
@@ -529,106 +380,10 @@ void dpir_prox_free(dpir_engine* e, dpir_prox* p) {
     delete p;
 }
 
-static unsigned brev(unsigned v, int bits) {
-    unsigned r = 0;
-    for (int i = 0; i < bits; ++i) r |= ((v >> i) & 1u) << (bits - 1 - i);
-    return r;
-}
-
 int dpir_prox_read(dpir_engine* e, const dpir_prox* p, int which, void* host_dst, size_t cap_bytes) {
     if (!e || !p || !host_dst) return fail(e, invalid("dpir_prox_read: null argument"));
-    const ProxState& st = p->st;
-    size_t hw = (size_t)st.H * st.W;
-    size_t planes = which == 2 ? (size_t)3 * st.B : (size_t)st.B;
-    if (st.half) {
-        if (which < 0 || which > 2) return fail(e, invalid("dpir_prox_read: which must be 0, 1 or 2"));
-        size_t esz = which == 1 ? sizeof(float) : sizeof(float2);
-        if (cap_bytes < planes * hw * esz) return fail(e, invalid("dpir_prox_read: destination too small"));
-        size_t shw = (size_t)st.H * st.WP;
-        std::vector<char> tmp(planes * shw * esz);
-        const void* src = which == 0 ? (const void*)st.FB : (which == 1 ? (const void*)st.F2B : (const void*)st.FBFy);
-        int rc = dpir_d2h(e, tmp.data(), src, tmp.size());
-        if (rc != DPIR_OK) return rc;
-        // natural[u][v] = stored[u][v] for v <= W/2, conj(stored[(H-u)%H][W-v]) beyond (Hermitian spectra of real signals)
-        for (size_t pl = 0; pl < planes; ++pl)
-            for (int u = 0; u < st.H; ++u)
-                for (int v = 0; v < st.W; ++v) {
-                    bool mir = v > st.W / 2;
-                    int su = mir ? (st.H - u) % st.H : u, sv = mir ? st.W - v : v;
-                    if (st.h_col_slot) sv = (*st.h_col_slot)[sv];           // sf > 1: alias-grouped column order
-                    const char* sp = tmp.data() + (pl * shw + (st.colmajor ? (size_t)sv * st.H + fft4_row_pos(su) : (size_t)su * st.WP + sv)) * esz;
-                    char* dp = reinterpret_cast<char*>(host_dst) + (pl * hw + (size_t)u * st.W + v) * esz;
-                    memcpy(dp, sp, esz);
-                    if (mir && which != 1) reinterpret_cast<float*>(dp)[1] = -reinterpret_cast<float*>(dp)[1];
-                }
-        return DPIR_OK;
-    }
-    size_t esz = which == 1 ? sizeof(float) : sizeof(float2);
-    const void* src = which == 0 ? (const void*)st.FB : (which == 1 ? (const void*)st.F2B : (const void*)st.FBFy);
-    if (which < 0 || which > 2) return fail(e, invalid("dpir_prox_read: which must be 0, 1 or 2"));
-    if (cap_bytes < planes * hw * esz) return fail(e, invalid("dpir_prox_read: destination too small"));
-    std::vector<char> tmp(planes * hw * esz);
-    int rc = dpir_d2h(e, tmp.data(), src, tmp.size());
-    if (rc != DPIR_OK) return rc;
-    // stored layout is bit-reversed along both axes (fft.hip): natural[u][v] = stored[brev(u)][brev(v)]
-    int lh = ilog2u(st.H), lw = ilog2u(st.W);
-    char* dst = reinterpret_cast<char*>(host_dst);
-    for (size_t pl = 0; pl < planes; ++pl)
-        for (int u = 0; u < st.H; ++u)
-            for (int v = 0; v < st.W; ++v)
-                memcpy(dst + (pl * hw + (size_t)u * st.W + v) * esz,
-                       tmp.data() + (pl * hw + (size_t)brev(u, lh) * st.W + brev(v, lw)) * esz, esz);
+    API_TRY(e, prox_read(e, p->st, which, host_dst, cap_bytes));
     return DPIR_OK;
-}
-
-// The half-spectrum prox passes described by `a` (rows forward -> columns with the solve -> rows inverse) on the layout the spectra were built in:
-// wave-per-transform kernels on the column-major spectrum (fft4.hip, 256 x 256) or the two-pass register kernels (fft2.hip).
-static Status prox_passes(dpir_engine* e, const ProxState& st, const ProxPassArgs& a) {
-    hipStream_t s = e->stream;
-    const int P = st.B * 3, N = st.W;
-    const RenoiseArgs ra{a.rn.xt, a.rn.sp, a.rn.lp, a.rn.n1, a.rn.n2, a.rn.stride, a.rn.with_n1};
-    if (st.colmajor) {
-        DPIR_TRY(launch_rfft4_rows(s, a.tw, st.W, a.x, a.pa, a.pb, a.pm, a.sp, a.hbuf, P, st.WP, a.fu.eps6, a.fu.out_ch, a.slot_col));
-        DPIR_TRY(launch_cfft4_cols(s, a.tw, st.W, a.hbuf, a.solve, true, P, st.WP));
-        return launch_irfft4_rows(s, a.tw, st.W, a.hbuf, a.out, a.scale, a.oa, a.ob, a.blend_base, a.g, P, st.WP, a.rn.xt ? &ra : nullptr, a.col_slot);
-    }
-    DPIR_TRY(launch_rfft_rows(s, a.tw, a.x, a.pa, a.pb, a.pm, a.sp, a.hbuf, P, N, a.fu.eps6, a.fu.out_ch, a.slot_col));
-    DPIR_TRY(launch_cfft_cols(s, a.tw, a.hbuf, a.solve, true, P, st.H));
-    return launch_irfft_rows(s, a.tw, a.hbuf, a.out, a.scale, a.oa, a.ob, a.blend_base, a.g, P, N, a.rn.xt ? &ra : nullptr, a.col_slot);
-}
-
-// out = blend ? base + g*((ifft)*oa+ob - base) : (ifft)*oa+ob ; input pre-map v = (x*pa+pb)*alpha
-static Status data_solution_impl(dpir_engine* e, const ProxState& st, const float* x, float pa, float pb, float alpha, float* out,
-                                 float oa, float ob, const float* blend_base, float g, const StepDev* sp = nullptr) {
-    if (!sp && !(alpha > 0.f)) return invalid("data_solution: alpha must be > 0");
-    if (st.half) {
-        const float2* tw = nullptr;
-        DPIR_TRY(e->fft2_table(st.W, &tw));
-        float2* hbuf = nullptr;
-        DPIR_TRY(e->ws.getT("prox#hbuf", (size_t)st.B * 3 * st.H * st.WP, &hbuf));
-        ProfScope ps2(&e->prof, PC_FFT);
-        ProxPassArgs a{};
-        a.x = x; a.pa = pa; a.pb = pb; a.pm = alpha; a.sp = sp; a.fu = RowsFuse{nullptr, 0}; a.slot_col = st.slot_col;
-        a.solve = SolveArgs{st.FB, st.F2B, st.FBFy, alpha, st.sf, sp, st.invW, st.slot_col};
-        a.out = out; a.scale = 1.0f / ((float)st.H * (float)st.W); a.oa = oa; a.ob = ob;
-        a.blend_base = (blend_base && g != 1.0f) ? blend_base : nullptr; a.g = g;
-        a.rn = RenoiseFuse{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0}; a.col_slot = st.col_slot;
-        a.hbuf = hbuf; a.tw = tw;
-        return prox_passes(e, st, a);
-    }
-    FftPlan ph, pw;
-    DPIR_TRY(e->fft_plan(st.H, &ph));
-    DPIR_TRY(e->fft_plan(st.W, &pw));
-    float2* buf = nullptr;
-    DPIR_TRY(e->ws.getT("prox#buf", (size_t)st.B * 3 * st.H * st.W, &buf));
-    hipStream_t s = e->stream;
-    ProfScope ps(&e->prof, PC_FFT);
-    DPIR_TRY(launch_fft_rows_real3(s, pw, buf, x, pa, pb, alpha, st.B * 3, st.H, st.W, sp));
-    SolveArgs a{st.FB, st.F2B, st.FBFy, alpha, st.sf, sp};
-    DPIR_TRY(launch_fft_cols_solve(s, ph, buf, a, st.B, st.H, st.W));
-    float scale = 1.0f / ((float)st.H * (float)st.W);
-    DPIR_TRY(launch_ifft_rows_real(s, pw, buf, out, scale, oa, ob, blend_base, g, st.B * 3, st.H, st.W));
-    return Status{};
 }
 
 int dpir_set_prox_launch(dpir_engine* e, int mode) {
@@ -641,57 +396,19 @@ int dpir_set_prox_launch(dpir_engine* e, int mode) {
 int dpir_data_solution(dpir_engine* e, const dpir_prox* p, const float* x, float alpha, float* out) {
     if (!e || !p || !x || !out) return fail(e, invalid("dpir_data_solution: null argument"));
     (void)hipSetDevice(e->device);
-    API_TRY(e, data_solution_impl(e, p->st, x, 1.f, 0.f, alpha, out, 1.f, 0.f, nullptr, 0.f));
+    API_TRY(e, prox_data_solution(e, p->st, x, 1.f, 0.f, alpha, out, 1.f, 0.f, nullptr, 0.f));
     return DPIR_OK;
 }
 int dpir_prox_fft_apply(dpir_engine* e, const dpir_prox* p, float* x0, float tau, float guidance) {
     if (!e || !p || !x0) return fail(e, invalid("dpir_prox_fft_apply: null argument"));
     (void)hipSetDevice(e->device);
-    API_TRY(e, data_solution_impl(e, p->st, x0, 0.5f, 0.5f, tau, x0, 2.f, -1.f, x0, guidance));
+    API_TRY(e, prox_data_solution(e, p->st, x0, 0.5f, 0.5f, tau, x0, 2.f, -1.f, x0, guidance));
     return DPIR_OK;
 }
-
-// measurement: n back-to-back applies between two events on the engine stream, eagerly or as ONE captured graph (what the restoration
-// loop replays: no host launch cost, no per-apply event records) -> device microseconds per apply, launch boundaries included
 int dpir_prox_fft_apply_timed(dpir_engine* e, const dpir_prox* p, float* x0, float tau, float guidance, int n, int use_graph, float* us_per_apply) {
     if (!e || !p || !x0 || !us_per_apply || n < 1) return fail(e, invalid("dpir_prox_fft_apply_timed: bad argument"));
     (void)hipSetDevice(e->device);
-    API_TRY(e, data_solution_impl(e, p->st, x0, 0.5f, 0.5f, tau, x0, 2.f, -1.f, x0, guidance));       // allocates the workspace, warms the code
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    API_HIP(e, hipEventCreate(&ev0));
-    API_HIP(e, hipEventCreate(&ev1));
-    hipGraphExec_t exec = nullptr;
-    Status st;
-    const bool prof_on = e->prof.on;
-    e->prof.on = false;
-    if (use_graph) {
-        hipGraph_t graph = nullptr;
-        e->ws.frozen = true;
-        hipError_t herr = hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal);
-        if (herr != hipSuccess) st = Status{DPIR_ERR_HIP, std::string("hipStreamBeginCapture: ") + hipGetErrorString(herr)};
-        else {
-            for (int i = 0; i < n && st.ok(); ++i) st = data_solution_impl(e, p->st, x0, 0.5f, 0.5f, tau, x0, 2.f, -1.f, x0, guidance);
-            herr = hipStreamEndCapture(e->stream, &graph);
-            if (st.ok() && herr != hipSuccess) st = Status{DPIR_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(herr)};
-        }
-        e->ws.frozen = false;
-        if (st.ok() && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) st = Status{DPIR_ERR_HIP, "hipGraphInstantiate failed"};
-        if (graph) (void)hipGraphDestroy(graph);
-        if (st.ok() && hipGraphLaunch(exec, e->stream) != hipSuccess) st = Status{DPIR_ERR_HIP, "hipGraphLaunch failed"};      // warm-up replay
-    }
-    if (st.ok()) {
-        (void)hipEventRecord(ev0, e->stream);
-        if (use_graph) { if (hipGraphLaunch(exec, e->stream) != hipSuccess) st = Status{DPIR_ERR_HIP, "hipGraphLaunch failed"}; }
-        else for (int i = 0; i < n && st.ok(); ++i) st = data_solution_impl(e, p->st, x0, 0.5f, 0.5f, tau, x0, 2.f, -1.f, x0, guidance);
-        (void)hipEventRecord(ev1, e->stream);
-        if (hipEventSynchronize(ev1) != hipSuccess) st = Status{DPIR_ERR_HIP, "hipEventSynchronize failed"};
-        float ms = 0.f;
-        if (st.ok() && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) *us_per_apply = ms * 1e3f / (float)n;
-    }
-    e->prof.on = prof_on;
-    if (exec) (void)hipGraphExecDestroy(exec);
-    (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1);
-    API_TRY(e, st);
+    API_TRY(e, prox_apply_timed(e, p->st, x0, tau, guidance, n, use_graph != 0, us_per_apply));
     return DPIR_OK;
 }
 
@@ -897,7 +614,7 @@ Status loop_init(dpir_engine* e, const dpir_loop_desc& d, const LoopBufs& b, Pro
         DPIR_TRY(launch_init_x(s, src, d.task == DPIR_TASK_INPAINT ? d.mask_dev : nullptr, n0, d.sa_start, d.s1m_start, b.x, total));
     }
     if (d.task == DPIR_TASK_DEBLUR || d.task == DPIR_TASK_SR_BLUR)
-        DPIR_TRY(prox_precalc(e, d.y_dev, d.k_dev, d.kh, d.kw, d.sf, B, H, W, prox));
+        DPIR_TRY(prox_precalc(e, d.y_dev, d.k_dev, d.kh, d.kw, prox));
     return Status{};
 }
 
@@ -915,25 +632,9 @@ Status loop_step(dpir_engine* e, const dpir_loop_desc& d, const LoopBufs& b, Pro
     }
     if (!b.film) hipLaunchKernelGGL(fill_t_kernel, dim3((B + 255) / 256), dim3(256), 0, s, b.t_dev, b.cur, B);
     DPIR_TRY(unet_forward(e, b.x, b.t_dev, b.y_dev, b.out6, B, H, W, b.film, b.film ? b.cur : nullptr));
-    // FFT data step on the half-spectrum path, fused into three launches: eps -> clamped x0 in the row-FFT prologue, spectral
-    // solve between the column FFTs, re-noise (+ Philox) in the inverse row-FFT epilogue.  x0 is never materialised.
-    if (!last && d.generate_mode == 0 && !d.first_order && (d.task == DPIR_TASK_DEBLUR || d.task == DPIR_TASK_SR_BLUR) && prox->half && d.guidance == 1.0f) {
-        if (with_n1 && d.noise_n1_dev && !d.noise_n2_dev) return invalid("host n1 noise requires host n2 noise");
-        const float2* tw = nullptr;
-        DPIR_TRY(e->fft2_table(prox->W, &tw));
-        float2* hbuf = nullptr;
-        DPIR_TRY(e->ws.getT("prox#hbuf", (size_t)prox->B * 3 * prox->H * prox->WP, &hbuf));
-        ProfScope ps(&e->prof, PC_FFT);
-        ProxPassArgs a{};
-        a.x = b.x; a.pa = 0.5f; a.pb = 0.5f; a.pm = 1.f; a.sp = b.cur; a.fu = RowsFuse{b.out6, e->net.desc.out_channels}; a.slot_col = prox->slot_col;
-        a.solve = SolveArgs{prox->FB, prox->F2B, prox->FBFy, 1.f, prox->sf, b.cur, prox->invW, prox->slot_col};
-        a.out = b.x0; a.scale = 1.0f / ((float)H * (float)W); a.oa = 2.f; a.ob = -1.f; a.blend_base = nullptr; a.g = 1.f;
-        a.rn = RenoiseFuse{b.x, b.cur, b.lp, d.noise_n1_dev, d.noise_n2_dev, d.noise_n2_dev ? total : 0, with_n1 ? 1 : 0}; a.col_slot = prox->col_slot;
-        a.hbuf = hbuf; a.tw = tw;
-        DPIR_TRY(prox_passes(e, *prox, a));
-        DPIR_HIP(hipGetLastError());
-        return Status{};
-    }
+    bool fused = false;       // the data step and the re-noise inside the prox's own three launches (half layouts): nothing is left to do here
+    DPIR_TRY(prox_fused_step(e, *prox, d, last, with_n1, b.x, b.out6, b.x0, b.cur, b.lp, &fused));
+    if (fused) return Status{};
     {
         ProfScope ps(&e->prof, PC_ELEM);
         DPIR_TRY(launch_xstart(s, b.x, b.out6, e->net.desc.out_channels, 0.f, 0.f, b.x0, B, H * W, b.cur));
@@ -949,7 +650,7 @@ Status loop_step(dpir_engine* e, const dpir_loop_desc& d, const LoopBufs& b, Pro
     } else if (d.task == DPIR_TASK_SR_CUBIC) {
         DPIR_TRY(prox_ibp_impl(e, b.x0, d.y_dev, 0.f, d.gamma, d.in_iter, d.sf, B, H, W, b.cur, b.lp));
     } else {
-        DPIR_TRY(data_solution_impl(e, *prox, b.x0, 0.5f, 0.5f, 1.f, b.x0, 2.f, -1.f, b.x0, d.guidance, b.cur));
+        DPIR_TRY(prox_data_solution(e, *prox, b.x0, 0.5f, 0.5f, 1.f, b.x0, 2.f, -1.f, b.x0, d.guidance, b.cur));
     }
     const float *n1 = nullptr, *n2 = nullptr;
     size_t stride = 0;
@@ -963,27 +664,6 @@ Status loop_step(dpir_engine* e, const dpir_loop_desc& d, const LoopBufs& b, Pro
     if (with_n1 && d.noise_n1_dev && !d.noise_n2_dev) return invalid("host n1 noise requires host n2 noise");
     DPIR_TRY(launch_renoise(s, b.x, b.x0, RenoiseCoef{}, n1, n2, total, b.cur, stride, b.lp));
     DPIR_HIP(hipGetLastError());
-    return Status{};
-}
-
-Status capture_step(dpir_engine* e, const dpir_loop_desc& d, const LoopBufs& b, ProxState* prox, bool last, bool with_n1,
-                    hipGraphExec_t* out) {
-    bool prof_on = e->prof.on, taps_on = e->collect_taps;
-    e->prof.on = false; e->collect_taps = false; e->ws.frozen = true;
-    hipGraph_t graph = nullptr;
-    Status cs;
-    hipError_t herr = hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal);
-    if (herr != hipSuccess) cs = Status{DPIR_ERR_HIP, std::string("hipStreamBeginCapture: ") + hipGetErrorString(herr)};
-    else {
-        cs = loop_step(e, d, b, prox, last, with_n1);
-        herr = hipStreamEndCapture(e->stream, &graph);
-        if (cs.ok() && herr != hipSuccess) cs = Status{DPIR_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(herr)};
-    }
-    e->ws.frozen = false; e->prof.on = prof_on; e->collect_taps = taps_on;
-    if (!cs.ok()) { if (graph) (void)hipGraphDestroy(graph); return cs; }
-    herr = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (herr != hipSuccess) return Status{DPIR_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(herr)};
     return Status{};
 }
 }  // namespace
@@ -1041,13 +721,14 @@ static int run_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_st
     if (hoist_film) API_TRY(e, e->ws.getT("loop#film", (size_t)n_steps * e->net.film_rows, &b.film));
     bool need_prox = d.task == DPIR_TASK_DEBLUR || d.task == DPIR_TASK_SR_BLUR;
     ProxState& prox = e->loop_prox;
-    // sf decides the spectrum layout (half-spectrum register FFT vs bit-reversed c2c): a change of sf re-allocates too
-    if (need_prox && (prox.B != B || prox.H != H || prox.W != W || prox.sf != d.sf || prox.half != fft2_supported(H, W, d.sf) ||
-                      prox.colmajor != (e->prox_mode == 1 && fft4_supported(H, W, d.sf)) || !prox.FB)) {
-        API_HIP(e, hipStreamSynchronize(e->stream));
-        prox_release(&prox);
-        e->invalidate_graphs();
-        API_TRY(e, prox_alloc(e, d.sf, B, H, W, &prox));
+    if (need_prox) {
+        bool reallocated = false;
+        const Status ps = prox_ensure(e, d.sf, B, H, W, &prox, &reallocated);
+        if (reallocated) {        // the captured steps hold the addresses of the spectra that went
+            API_HIP(e, hipStreamSynchronize(e->stream));
+            e->invalidate_graphs();
+        }
+        API_TRY(e, ps);
     }
 
     // per-step scalar table and the per-batch device block -> device (two small H2D copies per batch)
@@ -1108,7 +789,7 @@ static int run_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_st
                 API_TRY(e, loop_step(e, d, b, &prox, last, with_n1));
                 API_HIP(e, hipStreamSynchronize(e->stream));
                 hipGraphExec_t exec = nullptr;
-                API_TRY(e, capture_step(e, d, b, &prox, last, with_n1, &exec));
+                API_TRY(e, capture_graph(e, [&] { return loop_step(e, d, b, &prox, last, with_n1); }, &exec));
                 if (e->graphs.size() >= dpir_engine::kMaxGraphs) {        // evict the least recently used graph
                     size_t lru = 0;
                     for (size_t q = 1; q < e->graphs.size(); ++q) if (e->graphs[q].last_use < e->graphs[lru].last_use) lru = q;

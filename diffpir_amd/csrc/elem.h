@@ -1,4 +1,4 @@
-// Declarations for elem.hip / fft.hip launchers.
+// Declarations for the elem.hip / degrade.hip / fft.hip / fft2.hip / fft4.hip launchers (the FFT prox above them: prox.h).
 #pragma once
 #include "common.h"
 
@@ -87,42 +87,26 @@ Status launch_precalc_finish(hipStream_t s, const float2* FB, float2* FBFy_inout
 
 // fft2.hip: half-spectrum register FFT path (sf = 1, N = 64 / 256).  twN = W_N^m table (N entries, device)
 bool fft2_supported(int H, int W, int sf);
-int fft2_padded_width(int W);
 // eps6 != null (loop only): the row source is x0 = clamp(c1 x - c2 eps) computed on the fly from x and the UNet output
 Status launch_rfft_rows(hipStream_t s, const float2* twN, const float* x, float pa, float pb, float pm, const StepDev* sp,
                         float2* out, int P, int N, const float* eps6 = nullptr, int out_ch = 0, const int* slot_col = nullptr);
-// fused re-noise epilogue of the inverse row pass (loop only): x_t <- renoise(x_t, x0'), noise host-fed (n2 [, n1] + step stride,
+struct RowsFuse { const float* eps6; int out_ch; };      // eps -> x0 prologue of the row pass (loop only)
+// fused re-noise epilogue of the inverse row pass (loop only; xt == null: none): x_t <- renoise(x_t, x0'), noise host-fed (n2 [, n1] + step stride,
 // pointers re-read from lp when given) or Philox (n2 == null; seed / image offset from lp)
-struct RenoiseArgs { float* xt; const StepDev* sp; const LoopDev* lp; const float* n1; const float* n2; size_t stride; int with_n1; };
+struct RenoiseFuse { float* xt; const StepDev* sp; const LoopDev* lp; const float* n1; const float* n2; size_t stride; int with_n1; };
 Status launch_irfft_rows(hipStream_t s, const float2* twN, const float2* in, float* out, float scale, float oa, float ob,
-                         const float* blend, float g, int P, int N, const RenoiseArgs* ra = nullptr, const int* col_slot = nullptr);
-// sf > 1 on the half-spectrum path: alias-grouped column permutation (host tables), alias mean of F2B, zero-stuffed real up-sampling
-void fft2_build_map(int N, int sf, std::vector<int>& slot_col, std::vector<int>& col_slot);
-Status launch_fold_f2b(hipStream_t s, const float* F2B, const int* slot_col, int N, int sf, float* invW, int B);
+                         const float* blend, float g, int P, int N, const RenoiseFuse& rn, const int* col_slot);
+// sf > 1 on the half-spectrum path: zero-stuffed real up-sampling (the alias-grouped column permutation and the alias mean of F2B: prox.hip)
 Status launch_upsample_real(hipStream_t s, const float* y, int sf, float* out, int P, int h, int w);
 Status launch_cfft_cols(hipStream_t s, const float2* twN, float2* buf, const SolveArgs& a, bool solve, int P, int N);
 Status launch_precalc_finish2(hipStream_t s, const float2* FB, float2* FBFy, float* F2B, int B, size_t hw);
 // fft4.hip: one wave per N-point transform, column-major half spectrum [plane][slot][row] (NC slots per plane); N x N = 256 x 256 or 512 x 512, sf 1 / 2 / 4
 bool fft4_supported(int H, int W, int sf);
-int fft4_columns(int W, int sf);
-int fft4_row_pos(int u);      // position of row u inside a stored column
-void fft4_build_map(int N, int sf, std::vector<int>& slot_col, std::vector<int>& col_slot);
 Status launch_rfft4_rows(hipStream_t s, const float2* tw, int N, const float* x, float pa, float pb, float pm, const StepDev* sp, float2* out, int P, int NC,
                          const float* eps6, int out_ch, const int* slot_col);
 Status launch_irfft4_rows(hipStream_t s, const float2* tw, int N, const float2* in, float* out, float scale, float oa, float ob, const float* blend, float g,
-                          int P, int NC, const RenoiseArgs* ra, const int* col_slot);
+                          int P, int NC, const RenoiseFuse& rn, const int* col_slot);
 Status launch_cfft4_cols(hipStream_t s, const float2* tw, int N, float2* buf, const SolveArgs& a, bool solve, int P, int NC);
-Status launch_fold_f2b4(hipStream_t s, const float* F2B, const int* slot_col, int N, int NC, int sf, float* invW, int B);
-// the arguments of the three half-spectrum passes (rows forward -> columns with the solve -> rows inverse), whichever kernels run them
-struct RowsFuse { const float* eps6; int out_ch; };      // eps -> x0 prologue of the row pass (loop only)
-struct RenoiseFuse { float* xt; const StepDev* sp; const LoopDev* lp; const float* n1; const float* n2; size_t stride; int with_n1; };
-struct ProxPassArgs {
-    const float* x; float pa, pb, pm; const StepDev* sp; RowsFuse fu; const int* slot_col;                       // rows forward
-    SolveArgs solve;                                                                                             // columns
-    float* out; float scale, oa, ob; const float* blend_base; float g; RenoiseFuse rn; const int* col_slot;     // rows inverse
-    float2* hbuf; const float2* tw;
-};
-
 Status launch_psf_embed_real(hipStream_t s, const float* k, int kh, int kw, float* out, int B, int H, int W);
 
 }  // namespace dpir

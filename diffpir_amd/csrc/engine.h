@@ -3,6 +3,7 @@
 #include <functional>
 #include "common.h"
 #include "elem.h"
+#include "prox.h"
 
 namespace dpir {
 
@@ -76,17 +77,6 @@ struct Tape {
     void clear() { valid = false; nodes.clear(); res.clear(); attn.clear(); }
 };
 
-struct ProxState {   // dpir_prox
-    int B = 0, H = 0, W = 0, sf = 1;
-    float2* FB = nullptr; float* F2B = nullptr; float2* FBFy = nullptr;
-    bool half = false;     // true: half spectrum [.., H, WP] (fft2.hip; columns alias-grouped when sf > 1); false: bit-reversed full c2c (fft.hip)
-    bool colmajor = false; // half spectrum stored COLUMN-major [.., WP slots, H] for the wave-per-transform kernels (fft4.hip, 256 x 256 and 512 x 512)
-    int WP = 0;            // stored row length (complex elements); colmajor: stored columns (slots) per plane
-    float* invW = nullptr; // half && sf > 1: alias mean of F2B [B][H/sf][W/sf/2+1]
-    const int* slot_col = nullptr; const int* col_slot = nullptr;     // half && sf > 1: device slot maps (engine-owned, fft2_map)
-    const std::vector<int>* h_col_slot = nullptr;                     // host copy (dpir_prox_read)
-};
-
 struct ResizerTab { int in_len = 0, out_len = 0, taps = 0; float* w = nullptr; int* idx = nullptr; };
 
 }  // namespace dpir
@@ -101,10 +91,7 @@ struct dpir_engine {
     dpir::UNet net;
     dpir::Workspace ws;          // UNet activations + loop state
     std::map<std::string, dpir::TapInfo> taps;
-    std::map<int, dpir::FftPlan> fft_plans;
-    std::map<int, float2*> fft2_tw;              // W_N^m tables (N entries) for fft2.hip
-    struct Fft2Map { int* slot_col = nullptr; int* col_slot = nullptr; std::vector<int> h_slot_col, h_col_slot; };
-    std::map<std::pair<int, int>, Fft2Map> fft2_maps;   // (N, sf [+ 16 for the column-major layout]) -> alias-grouped column permutation of the half-spectrum layout
+    dpir::ProxCache prox_cache;                  // twiddle tables and slot maps of the FFT prox (prox.hip)
     std::map<std::pair<int, int>, dpir::ResizerTab> resizers;   // (in_len, sf)
     std::vector<void*> user_allocs;
     bool collect_taps = true;
@@ -134,8 +121,8 @@ struct dpir_engine {
         graphs.clear();
     }
     unsigned long long* range_ctr = nullptr;     // f16x3 operand range guard (act.hip range_report), device
-    // how the half-spectrum data step is run (dpir_set_prox_launch): 1 = wave-per-transform kernels on a column-major spectrum (fft4.hip; 256 x 256 and 512 x 512, default),
-    // 0 = the two-pass register kernels (fft2.hip; every other size always).  cus: CU count of the device.
+    // how the half-spectrum data step is run (dpir_set_prox_launch; read by prox_layout only): 1 = wave-per-transform kernels on a column-major spectrum (fft4.hip;
+    // 256 x 256 and 512 x 512, default), 0 = the two-pass register kernels (fft2.hip; every other size always).  cus: CU count of the device.
     int prox_mode = 1; int cus = 256;
     // conv7's fused hop (Conv6Emit) is an inter-workgroup wait; when it times out (the GPU is shared with other engines / processes) the
     // engine does not fail: it switches the hop off for its lifetime and re-runs what the time-out invalidated -- the restoration loop
@@ -151,9 +138,6 @@ struct dpir_engine {
     void arm_replay(std::function<int()> fn) { ++fwd_since_sync; replay_last = std::move(fn); replay_serial = enqueue_serial(); }
     void* comm = nullptr; int comm_world = 1, comm_rank = 0;     // RCCL communicator (comm.cpp), or null
 
-    dpir::Status fft_plan(int N, dpir::FftPlan* out);
-    dpir::Status fft2_table(int N, const float2** out);
-    dpir::Status fft2_map(int N, int sf, const Fft2Map** out, bool colmajor = false);
     dpir::Status resizer(int in_len, int sf, dpir::ResizerTab* out);
 };
 

@@ -21,6 +21,7 @@
 // Algorithmic HBM bytes per image per step at 256^2: 2.50 MB; the padded half-spectrum intermediate
 // (3 x 256 x 144 x 8 B = 0.88 MB, written once and read once by each neighbour kernel) stays in L2 / Infinity Cache.
 #include "fft2_body.h"
+#include "prox.h"
 #include <vector>
 
 namespace dpir {
@@ -50,27 +51,6 @@ __global__ __launch_bounds__(THREADS) void cfft_cols_kernel(float2* buf, SolveAr
     cfft_cols_body<R, RJ, MODE, THREADS, SF, false>(sm2, plane, blockIdx.x - plane * strips, buf, a, WP, tw, NoWait{});
 }
 
-// invW[n, p, q] = mean over the sf x sf aliases of F2B (utils_sisr.py:71 `invW = mean(splits(F2B))`), from the permuted half layout
-__global__ void fold_f2b_kernel(const float* F2B, const int* slot_col, int N, int WP, int sf, float* invW, size_t total) {
-    const int Hs = N / sf, QW = N / sf / 2 + 1;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int q = (int)(i % QW);
-        const int p = (int)((i / QW) % Hs);
-        const size_t n = i / ((size_t)QW * Hs);
-        const float* pl = F2B + n * (size_t)N * WP;
-        // pairwise over the sf x sf aliases (sf 2 or 4), as the solve sums FB * FR (fft_regs.h, tree_sum)
-        auto alias_col = [&](int b) -> float {
-            const int slot = sf * q + b;
-            const int cm = slot_col[slot];
-            if (cm < 0) return 0.f;
-            const int base_row = (cm >> 16) ? (Hs - p) % Hs : p;          // |FB|^2 is real: the mirrored alias is just the mirrored row
-            auto at = [&](int a) { return pl[(size_t)(base_row + a * Hs) * WP + slot]; };
-            return sf == 2 ? at(0) + at(1) : (at(0) + at(1)) + (at(2) + at(3));
-        };
-        const float acc = sf == 2 ? alias_col(0) + alias_col(1) : (alias_col(0) + alias_col(1)) + (alias_col(2) + alias_col(3));
-        invW[i] = acc / (float)(sf * sf);
-    }
-}
 // zero-stuffed up-sampling of the measurement as a REAL image (utils_sisr.upsample, :44-52)
 __global__ void upsample_real_kernel(const float* y, int sf, float* out, int h, int w, size_t total) {
     const int H = h * sf, W = w * sf;
@@ -104,20 +84,6 @@ __global__ void psf_embed_real_kernel(const float* k, int kh, int kw, float* out
 
 // ------------------------------------------------------------------------------------------------ launchers
 bool fft2_supported(int H, int W, int sf) { return (sf == 1 || sf == 2 || sf == 4) && H == W && (H == 512 || H == 256 || H == 64); }
-// slot -> (column | mirrored << 16) or -1 (padding), and column -> canonical slot, for the alias-grouped layout of sf > 1
-void fft2_build_map(int N, int sf, std::vector<int>& slot_col, std::vector<int>& col_slot) {
-    const int WP = fft2_padded_width(N), Ws = N / sf;
-    slot_col.assign(WP, -1);
-    col_slot.assign(N / 2 + 1, -1);
-    for (int q = 0; q <= Ws / 2; ++q)
-        for (int b = 0; b < sf; ++b) {
-            const int c = q + b * Ws;
-            const int col = c <= N / 2 ? c : N - c, mir = c <= N / 2 ? 0 : 1;
-            slot_col[sf * q + b] = col | (mir << 16);
-            if (col_slot[col] < 0 || (!mir && (slot_col[col_slot[col]] >> 16))) col_slot[col] = sf * q + b;      // prefer the direct copy
-        }
-}
-int fft2_padded_width(int W) { const int cs = 16; return (W / 2 + 1 + cs - 1) / cs * cs; }   // multiple of the column strip
 
 constexpr int ROW_THREADS = 64;    // small workgroups: at B = 16 the whole prox is ~40 MB, concurrency comes from block count
 // 16 columns per strip for both sizes: a strip row is one full 128-byte line (8 columns = half lines cost ~2x the requests)
@@ -168,9 +134,7 @@ static Status irfft_rows_R(hipStream_t s, const float2* in, float* out, float sc
     return Status{};
 }
 Status launch_irfft_rows(hipStream_t s, const float2* twN, const float2* in, float* out, float scale, float oa, float ob,
-                         const float* blend, float g, int P, int N, const RenoiseArgs* ra, const int* col_slot) {
-    RenoiseFuse rn{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
-    if (ra) rn = RenoiseFuse{ra->xt, ra->sp, ra->lp, ra->n1, ra->n2, ra->stride, ra->with_n1};
+                         const float* blend, float g, int P, int N, const RenoiseFuse& rn, const int* col_slot) {
     if (N == 512) return irfft_rows_R<16, 32>(s, in, out, scale, oa, ob, blend, g, P, N, twN, rn, col_slot);
     return N == 256 ? irfft_rows_R<16, 16>(s, in, out, scale, oa, ob, blend, g, P, N, twN, rn, col_slot)
                     : irfft_rows_R<8, 8>(s, in, out, scale, oa, ob, blend, g, P, N, twN, rn, col_slot);
@@ -206,13 +170,6 @@ Status launch_cfft_cols(hipStream_t s, const float2* twN, float2* buf, const Sol
     if (N == 256) DPIR_COLS(16, 16);
     DPIR_COLS(8, 8);
 #undef DPIR_COLS
-}
-Status launch_fold_f2b(hipStream_t s, const float* F2B, const int* slot_col, int N, int sf, float* invW, int B) {
-    if (sf != 2 && sf != 4) return invalid("fold_f2b: sf must be 2 or 4");
-    const size_t total = (size_t)B * (N / sf) * (N / sf / 2 + 1);
-    hipLaunchKernelGGL(fold_f2b_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, F2B, slot_col, N, fft2_padded_width(N), sf, invW, total);
-    DPIR_HIP(hipGetLastError());
-    return Status{};
 }
 Status launch_upsample_real(hipStream_t s, const float* y, int sf, float* out, int P, int h, int w) {
     const size_t total = (size_t)P * h * sf * w * sf;

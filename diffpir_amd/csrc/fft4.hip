@@ -12,9 +12,6 @@
 // sf > 1 keeps fft2's alias-grouped SLOT order (slot sf q + b = alias b of fold group q): a workgroup's four column waves are four consecutive slots, i.e.
 // one fold group at sf = 4 and two at sf = 2; the row aliases u + a N/sf of a column live in ONE lane (registers j, since N/sf is a multiple of 64).
 #include "fft4_body.h"
-#include <vector>
-#include <algorithm>
-#include <stdlib.h>
 
 namespace dpir {
 
@@ -56,68 +53,17 @@ __global__ __launch_bounds__(THREADS4) void cfft4_cols_kernel(float2* buf, Solve
     cols4_item_body<MODE, SF, N>(sm4 + wave * wlds(N), sm4 + WAVES * wlds(N), plane, item, wave, buf, a, NC, w, NoWait4{});
 }
 
-// invW[n, p, q] = mean over the sf x sf aliases of F2B (utils_sisr.py:71), column-major slots
-__global__ void fold_f2b4_kernel(const float* F2B, const int* slot_col, int N, int NC, int sf, float* invW, size_t total) {
-    const int Hs = N / sf, QW = N / sf / 2 + 1;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int q = (int)(i % QW);
-        const int p = (int)((i / QW) % Hs);
-        const size_t n = i / ((size_t)QW * Hs);
-        const float* pl = F2B + n * (size_t)NC * N;
-        // pairwise over the sf x sf aliases (sf 2 or 4), as the solve sums FB * FR (fft_regs.h, tree_sum)
-        auto alias_col = [&](int b) -> float {
-            const int slot = sf * q + b;
-            const int cm = slot < NC ? slot_col[slot] : -1;
-            if (cm < 0) return 0.f;
-            const int base_row = (cm >> 16) ? (Hs - p) % Hs : p;          // |FB|^2 is real: the mirrored alias is just the mirrored row
-            auto at = [&](int a) { return pl[(size_t)slot * N + pos4(base_row + a * Hs)]; };
-            return sf == 2 ? at(0) + at(1) : (at(0) + at(1)) + (at(2) + at(3));
-        };
-        const float acc = sf == 2 ? alias_col(0) + alias_col(1) : (alias_col(0) + alias_col(1)) + (alias_col(2) + alias_col(3));
-        invW[i] = acc / (float)(sf * sf);
-    }
-}
-
-int fft4_row_pos(int u) { return pos4(u); }
 bool fft4_supported(int H, int W, int sf) { return H == W && (H == 256 || H == 512) && (sf == 1 || sf == 2 || sf == 4); }
-// stored columns (slots) per plane: W/2 + 1 for sf = 1, sf * (W/sf/2 + 1) alias-grouped slots otherwise
-int fft4_columns(int W, int sf) { return sf == 1 ? W / 2 + 1 : sf * (W / sf / 2 + 1); }
-// slot -> (column | mirrored << 16) or -1, column -> canonical slot: fft2's alias grouping without strip padding
-void fft4_build_map(int N, int sf, std::vector<int>& slot_col, std::vector<int>& col_slot) {
-    const int NC = fft4_columns(N, sf), Ws = N / sf;
-    slot_col.assign(NC, -1);
-    col_slot.assign(N / 2 + 1, -1);
-    for (int q = 0; q <= Ws / 2; ++q)
-        for (int b = 0; b < sf; ++b) {
-            const int c = q + b * Ws;
-            if (c >= N) continue;
-            const int col = c <= N / 2 ? c : N - c, mir = c <= N / 2 ? 0 : 1;
-            slot_col[sf * q + b] = col | (mir << 16);
-            if (col_slot[col] < 0 || (!mir && (slot_col[col_slot[col]] >> 16))) col_slot[col] = sf * q + b;      // prefer the direct copy
-        }
-}
 
 static size_t lds4(int N, bool fold, int sf) { return ((size_t)WAVES * wlds(N) + (fold ? (size_t)WAVES * (N / sf) : 0)) * sizeof(float2); }
 static size_t lds4_rows(int N, int NC) { return (size_t)RW * wlds(N) * sizeof(float2) + (size_t)NC * TST * sizeof(float4); }
-
-// dynamic LDS above 64 KB (the 512-point row passes: 8 exchange tiles + the [slot][9] line tile = 74 KB) has to be allowed per kernel, once
-template <class K> static Status allow_lds(K kernel, size_t bytes) {
-    static size_t allowed[64];                  // per instantiation (= per kernel) and device: raise the limit only when a launch needs more than was granted so far
-    if (bytes <= 64 * 1024) return Status{};
-    int dev = 0;
-    DPIR_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || bytes > allowed[dev]) {
-        DPIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-        if (dev >= 0 && dev < 64) allowed[dev] = bytes;
-    }
-    return Status{};
-}
 
 template <int N>
 static Status rows_fwd(hipStream_t s, const float2* tw, const float* x, float pa, float pb, float pm, const StepDev* sp, float2* out, int P, int NC,
                        const float* eps6, int out_ch, const int* slot_col) {
     const size_t pairs = (size_t)P * N / 2;             // a multiple of RW: no partial workgroup
-    DPIR_TRY(allow_lds(rfft4_rows_kernel<N>, lds4_rows(N, NC)));
+    static LdsAttrOnce attr;      // dynamic LDS above 64 KB (the 512-point row passes: 8 exchange tiles + the [slot][9] line tile = 74 KB) is allowed per kernel, once
+    DPIR_HIP(attr.set(reinterpret_cast<const void*>(rfft4_rows_kernel<N>), 160 * 1024));
     hipLaunchKernelGGL(rfft4_rows_kernel<N>, dim3((unsigned)(pairs / RW)), dim3(RTHREADS), lds4_rows(N, NC), s, x, pa, pb, pm, sp, out, NC, tw,
                        RowsFuse{eps6, out_ch}, slot_col);
     DPIR_HIP(hipGetLastError());
@@ -134,16 +80,15 @@ template <int N>
 static Status rows_inv(hipStream_t s, const float2* tw, const float2* in, float* out, float scale, float oa, float ob, const float* blend, float g, int P,
                        int NC, RenoiseFuse rn, const int* col_slot) {
     const size_t pairs = (size_t)P * N / 2;
-    DPIR_TRY(allow_lds(irfft4_rows_kernel<N>, lds4_rows(N, N / 2 + 1)));
+    static LdsAttrOnce attr;
+    DPIR_HIP(attr.set(reinterpret_cast<const void*>(irfft4_rows_kernel<N>), 160 * 1024));
     hipLaunchKernelGGL(irfft4_rows_kernel<N>, dim3((unsigned)(pairs / RW)), dim3(RTHREADS), lds4_rows(N, N / 2 + 1), s, in, out, scale, oa, ob, blend, g, NC,
                        tw, rn, col_slot);
     DPIR_HIP(hipGetLastError());
     return Status{};
 }
 Status launch_irfft4_rows(hipStream_t s, const float2* tw, int N, const float2* in, float* out, float scale, float oa, float ob, const float* blend, float g,
-                          int P, int NC, const RenoiseArgs* ra, const int* col_slot) {
-    RenoiseFuse rn{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
-    if (ra) rn = RenoiseFuse{ra->xt, ra->sp, ra->lp, ra->n1, ra->n2, ra->stride, ra->with_n1};
+                          int P, int NC, const RenoiseFuse& rn, const int* col_slot) {
     if (N == 256) return rows_inv<256>(s, tw, in, out, scale, oa, ob, blend, g, P, NC, rn, col_slot);
     if (N == 512) return rows_inv<512>(s, tw, in, out, scale, oa, ob, blend, g, P, NC, rn, col_slot);
     return invalid("irfft4_rows: N must be 256 or 512");
@@ -173,12 +118,4 @@ Status launch_cfft4_cols(hipStream_t s, const float2* tw, int N, float2* buf, co
     if (N == 512) return cols<512>(s, tw, buf, a, solve, P, NC);
     return invalid("cfft4_cols: N must be 256 or 512");
 }
-Status launch_fold_f2b4(hipStream_t s, const float* F2B, const int* slot_col, int N, int NC, int sf, float* invW, int B) {
-    if (sf != 2 && sf != 4) return invalid("fold_f2b4: sf must be 2 or 4");
-    const size_t total = (size_t)B * (N / sf) * (N / sf / 2 + 1);
-    hipLaunchKernelGGL(fold_f2b4_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, F2B, slot_col, N, NC, sf, invW, total);
-    DPIR_HIP(hipGetLastError());
-    return Status{};
-}
-
 }  // namespace dpir
