@@ -79,23 +79,26 @@ __global__ void degrade_finish_kernel(float* y, const float* noise, double sigma
     }
 }
 
-// per image: sum over (c, h, w) of (x0*2-1 - (gt/255*2-1))^2 and of the squared difference of the Y channels
+// per image: sum over (c, h, w) of (x0*2-1 - (gt/255*2-1))^2 and of the squared difference of the Y channels.
+// The inputs are the reference's float32 images (x0, and uint2single(gt) = (float)gt / 255); everything after them is float64: in float32 the
+// two roundings of * 2 - 1 near 1 (6e-8 each) are 1e-3 of a difference of 1e-4, which on a 63-pixel image moved PSNR-Y by 1.7e-4 dB against
+// float64 (tests/test_gpu_ops_float64.py, B 5, 7 x 9, 87.5 dB).  Identical images still give exactly 0.
 __global__ __launch_bounds__(256) void metrics_kernel(const float* x0, const uint8_t* gt, int HW, double2* out) {
     const int n = blockIdx.x;
     double s = 0.0, sy = 0.0;
     for (int p = threadIdx.x; p < HW; p += 256) {
-        float a[3], b[3];
+        double a[3], b[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            a[c] = x0[((size_t)n * 3 + c) * HW + p] * 2.0f - 1.0f;
-            b[c] = (float)gt[((size_t)n * HW + p) * 3 + c] / 255.0f * 2.0f - 1.0f;
-            const float d = a[c] - b[c];
-            s += (double)(d * d);
+            a[c] = (double)x0[((size_t)n * 3 + c) * HW + p] * 2.0 - 1.0;
+            b[c] = (double)((float)gt[((size_t)n * HW + p) * 3 + c] / 255.0f) * 2.0 - 1.0;
+            const double d = a[c] - b[c];
+            s += d * d;
         }
-        const float ya = (0.299f * a[0] + 0.587f * a[1]) + 0.114f * a[2];
-        const float yb = (0.299f * b[0] + 0.587f * b[1]) + 0.114f * b[2];
-        const float dy = ya - yb;
-        sy += (double)(dy * dy);
+        const double ya = (0.299 * a[0] + 0.587 * a[1]) + 0.114 * a[2];
+        const double yb = (0.299 * b[0] + 0.587 * b[1]) + 0.114 * b[2];
+        const double dy = ya - yb;
+        sy += dy * dy;
     }
     __shared__ double red[2][4];
 #pragma unroll

@@ -18,6 +18,13 @@
  *   - all work is enqueued on ONE engine-owned HIP stream; calls are asynchronous unless noted
  *     (dpir_sync, D2H copies).  One engine per device; an engine is not thread-safe, independent
  *     engines are.
+ *   - shapes: the stepwise entries (dpir_prox_mask, dpir_repaint_mix, dpir_renoise, dpir_finalize, dpir_randn,
+ *     dpir_bicubic_up, dpir_resize_down, dpir_prox_ibp, dpir_metrics, dpir_grad_and_value) check their shape before
+ *     anything is divided, allocated or enqueued: B, H, W (and C of dpir_randn) >= 1, H * W <= 2^29 - 1 pixels per plane
+ *     ("H * W is out of range"; the kernels decode 3 * H * W in an int; dpir_bicubic_up: (h sf) * (w sf)), and where the entry has a scale
+ *     factor sf >= 1 dividing H and W (dpir_bicubic_up: sf >= 1; its h, w are the low-resolution sizes).  A violation
+ *     returns DPIR_ERR_INVALID with a message naming the entry and leaves the engine usable.  Every entry selects the
+ *     engine's device itself (hipSetDevice), whichever device is current in the calling thread.
  */
 #ifndef DIFFPIR_ENGINE_H
 #define DIFFPIR_ENGINE_H
@@ -359,7 +366,11 @@ int dpir_degrade(dpir_engine* e, const dpir_degrade_desc* d, const uint8_t* gt_u
                  const float* noise_dev, float* y_out_dev);
 /* Replaces main_ddpir.py:482-517: per image, PSNR of x_0*2-1 against img_H/255*2-1 (utils_image.calculate_psnr_batch terms,
  * max_pixel 2, eps 1e-10) and the same on the Y channel of rgb2ycbcr_batch(only_y) (utils_image.py:470-490; its two zero
- * channels are part of the mean, as in the reference).  x0_dev [B,3,H,W] in [0,1]; outputs: HOST arrays of B floats (syncs). */
+ * channels are part of the mean, as in the reference).  x0_dev [B,3,H,W] in [0,1]; outputs: HOST arrays of B floats (syncs).
+ * Precision: the inputs are the reference's float32 images (x0 and uint2single(img_H)); the differences, the Y combination, the mean and
+ * the logarithm are evaluated in float64 and the result is rounded to float once.  This is NOT the reference's float32 evaluation of
+ * calculate_psnr_batch: it is within 2e-5 dB of the float64 value at every image size, which the float32 evaluation is not (1.7e-4 dB on
+ * a 63-pixel image at 87 dB); the two agree to 2e-5 dB on the reference's fixture.  Identical images give +inf in both. */
 int dpir_metrics(dpir_engine* e, const float* x0_dev, const uint8_t* gt_u8_dev, int B, int H, int W, float* psnr_host, float* psnr_y_host);
 
 /* ---- instrumentation --------------------------------------------------------------------- */

@@ -265,15 +265,17 @@ def resizer_contributions(in_len: int, out_len: int, scale: float):
     return w, fov.astype(np.int64)
 
 
-def resizer_apply(x, sf_inv: float):
+def resizer_apply(x, sf_inv: float, dtype=None):
     """utils_resizer.py:55-74 for a 4-D tensor and scalar scale: both spatial dims have equal
-    scale so the stable argsort processes dim 2 (H) first, then dim 3 (W)."""
+    scale so the stable argsort processes dim 2 (H) first, then dim 3 (W).
+    dtype: None keeps the reference's float32 weight tensors; pass x.dtype (torch.float64) to hold the weights in the input's precision
+    (the float64 checker of tests/ops_f64.py)."""
     out = x
     for dim in (2, 3):
         n = out.shape[dim]
         m = int(np.ceil(n * sf_inv))
         w, fov = resizer_contributions(n, m, sf_inv)
-        w_t = torch.tensor(w.T, dtype=torch.float32)                   # [taps,out]
+        w_t = torch.tensor(w.T, dtype=torch.float32 if dtype is None else dtype)   # [taps,out]
         fov_t = torch.tensor(fov.T.astype(np.int32), dtype=torch.long)   # [taps,out]
         xt = torch.transpose(out, dim, 0)
         wv = w_t.reshape(list(w_t.shape) + [1] * 3)
@@ -282,18 +284,30 @@ def resizer_apply(x, sf_inv: float):
     return out
 
 
-def prox_ibp(x0, y, rho, sf, gamma, in_iter):
-    """main_ddpir.py:401-406: iterative back-projection; up-sampler is F.interpolate default (nearest)."""
+def prox_ibp(x0, y, rho, sf, gamma, in_iter, dtype=None):
+    """main_ddpir.py:401-406: iterative back-projection; up-sampler is F.interpolate default (nearest).  dtype: see resizer_apply."""
     for _ in range(in_iter):
         x0 = x0 / 2 + 0.5
-        x0 = x0 + gamma * F.interpolate(y - resizer_apply(x0, 1.0 / sf), scale_factor=sf) / (1 + rho)
+        x0 = x0 + gamma * F.interpolate(y - resizer_apply(x0, 1.0 / sf, dtype), scale_factor=sf) / (1 + rho)
         x0 = x0 * 2 - 1
     return x0
 
 
 # ------------------------------------------------------------------ loop
-def renoise(x, x0, dt: DriverTables, t_i, t_im1, eta, zeta, n1, n2):
-    """main_ddpir.py:451-456 verbatim arithmetic order (float32 tensors x numpy float64 sqrt)."""
+def renoise(x, x0, dt: DriverTables, t_i, t_im1, eta, zeta, n1, n2, dtype=None):
+    """main_ddpir.py:451-456 verbatim arithmetic order (float32 tensors x numpy float64 sqrt).
+    dtype: None or torch.float32 is the reference's arithmetic, the text below, untouched.  torch.float64 (tensors given in it) is NOT the
+    reference expression re-evaluated in float64: it is the kernel's contract in float64 -- the seven scalar coefficients are formed as the
+    reference forms them and rounded to float32 (the values a schedule.build_steps entry hands the engine: sa_t, s1m_t, sa_p, k1, q, es,
+    k2), and only the tensor arithmetic runs in float64.  It shares that grouping with tests/ops_f64.renoise, so their 1e-12 agreement
+    checks transcription, not independence; the independent check of the grouping is the fp32 path against tests/ops_f64.renoise_f32."""
+    if dtype is not None and dtype != torch.float32:
+        eta_sigma = eta * dt.sqrt_1m_ac[t_im1] / dt.sqrt_1m_ac[t_i] * torch.sqrt(dt.betas[t_i])
+        c = lambda v: torch.as_tensor(v).float().to(dtype)          # noqa: E731
+        eps = (x - c(dt.sqrt_ac[t_i]) * x0) / c(dt.sqrt_1m_ac[t_i])
+        return c(dt.sqrt_ac[t_im1]) * x0 + c(np.sqrt(1 - zeta)) * (
+            c(torch.sqrt(dt.sqrt_1m_ac[t_im1] ** 2 - eta_sigma ** 2)) * eps + c(eta_sigma) * n1) \
+            + c(np.sqrt(zeta) * dt.sqrt_1m_ac[t_im1]) * n2
     eps = (x - dt.sqrt_ac[t_i] * x0) / dt.sqrt_1m_ac[t_i]
     eta_sigma = eta * dt.sqrt_1m_ac[t_im1] / dt.sqrt_1m_ac[t_i] * torch.sqrt(dt.betas[t_i])
     return dt.sqrt_ac[t_im1] * x0 + np.sqrt(1 - zeta) * (
