@@ -3,6 +3,7 @@
 // the header; this file only validates, dispatches to the launchers and keeps the error string.
 #include "engine.h"
 #include "grad.h"
+#include "blur.h"
 #include <math.h>
 #include <string.h>
 #include <stdlib.h>
@@ -904,7 +905,8 @@ static Status dps_residual(dpir_engine* e, const float* x_hat, const float* y, f
 
 // torch.autograd.grad(norm, x) with x_hat = x0 of the last p_sample_impl(x): the clamp mask, the direct c1 term and the network backward.
 // Leaves direct / dx_net in the workspace (norm_grad = direct + dx_net).
-static Status dps_grad_through_network(dpir_engine* e, const float* gup, const float* normv, float** direct_out, float** dxn_out) {
+static Status dps_grad_through_network(dpir_engine* e, const float* gup, const float* normv, float** direct_out, float** dxn_out,
+                                       bool norm_per_image = false) {
     const int B = e->ps_B, H = e->ps_H, W = e->ps_W, oc = e->net.desc.out_channels;
     const size_t total = (size_t)B * 3 * H * W;
     float *dout6 = nullptr, *direct = nullptr, *dxn = nullptr; unsigned char* inside = nullptr;
@@ -912,7 +914,7 @@ static Status dps_grad_through_network(dpir_engine* e, const float* gup, const f
     DPIR_TRY(e->ws.getT("dps#direct", total, &direct));
     DPIR_TRY(e->ws.getT("dps#dxn", total, &dxn));
     DPIR_TRY(e->ws.getT("dps#inside", total, &inside));
-    DPIR_TRY(launch_dps_seed(e->stream, gup, normv, inside, e->ps_c1, e->ps_c2, oc, dout6, direct, B, H * W));
+    DPIR_TRY(launch_dps_seed(e->stream, gup, normv, inside, e->ps_c1, e->ps_c2, oc, dout6, direct, B, H * W, norm_per_image));
     DPIR_TRY(unet_backward(e, dout6, dxn));
     *direct_out = direct; *dxn_out = dxn;
     return Status{};
@@ -1050,6 +1052,173 @@ int dpir_run_dps_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step*
         API_TRY(e, dps_residual(e, b.x0, d.y_dev, 2.f, -1.f, 1.f, 0.f, nullptr, sf, B, H, W, &gup, &normv));
         API_TRY(e, dps_grad_through_network(e, gup, normv, &direct, &dxn));
         API_TRY(e, launch_dps_update(s, xprev, direct, dxn, step_scale, b.x, nullptr, total));
+    }
+    {
+        ProfScope ps(&e->prof, PC_ELEM);
+        API_TRY(e, launch_finalize(s, b.x, out_f32, out_u8, B, H * W));
+    }
+    return DPIR_OK;
+}
+
+// ------------------------------------------------------------------------------------------ deblurring program: blur operator + gradient modes
+int dpir_blur_reflect(dpir_engine* e, const float* x_dev, const float* k_dev, int kh, int kw, float xa, float xb, float* out_dev, int B, int H, int W) {
+    if (!e || !x_dev || !k_dev || !out_dev) return fail(e, invalid("dpir_blur_reflect: null argument"));
+    API_TRY(e, blur_check("dpir_blur_reflect", kh, kw, B, H, W));
+    (void)hipSetDevice(e->device);
+    ProfScope ps(&e->prof, PC_ELEM);
+    API_TRY(e, launch_blur_reflect(e->stream, x_dev, k_dev, kh, xa, xb, out_dev, B, H, W));
+    return DPIR_OK;
+}
+
+static Status blur_adjoint_impl(dpir_engine* e, const float* g, const float* k, int K, float xa, float* gx, int B, int H, int W) {
+    float* pad = nullptr;
+    DPIR_TRY(e->ws.getT("blur#pad", (size_t)B * 3 * (H + K - 1) * (W + K - 1), &pad));
+    return launch_blur_reflect_adjoint(e->stream, g, k, K, xa, pad, gx, B, H, W);
+}
+
+int dpir_blur_reflect_adjoint(dpir_engine* e, const float* g_dev, const float* k_dev, int kh, int kw, float xa, float* gx_dev, int B, int H, int W) {
+    if (!e || !g_dev || !k_dev || !gx_dev) return fail(e, invalid("dpir_blur_reflect_adjoint: null argument"));
+    API_TRY(e, blur_check("dpir_blur_reflect_adjoint", kh, kw, B, H, W));
+    (void)hipSetDevice(e->device);
+    ProfScope ps(&e->prof, PC_ELEM);
+    API_TRY(e, blur_adjoint_impl(e, g_dev, k_dev, kh, xa, gx_dev, B, H, W));
+    return DPIR_OK;
+}
+
+// difference = m - Tx(x_hat) (main_ddpir_deblur.py:307-311), one norm PER IMAGE (the program restores one image at a time, so utils_model.py:392 sees a
+// batch of one), gup = Tx^T difference = 0.5 R^T C^T difference.  m = (sa (ma y + mb) + s1m noise) qa + qb.
+static Status blur_residual(dpir_engine* e, const float* x_hat, const BlurResidual& meas, const float* k, int K, int B, int H, int W,
+                            float** gup_out, float** norm_out) {
+    const size_t total = (size_t)B * 3 * H * W;
+    const int per_img = 3 * blur_tiles(H, W);
+    BlurResidual r = meas;
+    float *gup = nullptr, *normv = nullptr;
+    DPIR_TRY(e->ws.getT("blur#diff", total, &r.diff));
+    DPIR_TRY(e->ws.getT("blur#part", (size_t)B * per_img, &r.part));
+    DPIR_TRY(e->ws.getT("blur#norm", (size_t)(B < 4 ? 4 : B), &normv));
+    DPIR_TRY(e->ws.getT("blur#gup", total, &gup));
+    DPIR_TRY(launch_blur_reflect(e->stream, x_hat, k, K, 0.5f, 0.5f, nullptr, B, H, W, &r));
+    DPIR_TRY(launch_norm_fold_per_image(e->stream, r.part, per_img, B, normv));
+    DPIR_TRY(blur_adjoint_impl(e, r.diff, k, K, 0.5f, gup, B, H, W));
+    *gup_out = gup; *norm_out = normv;
+    return Status{};
+}
+
+int dpir_grad_and_value_blur(dpir_engine* e, int through_network, const float* x_hat_dev, const float* measurement_dev, const float* k_dev, int kh, int kw,
+                             float* norm_grad_out_dev, float* norm_out_dev, int B, int H, int W) {
+    if (!e || !x_hat_dev || !measurement_dev || !k_dev || !norm_grad_out_dev) return fail(e, invalid("dpir_grad_and_value_blur: null argument"));
+    API_TRY(e, blur_check("dpir_grad_and_value_blur", kh, kw, B, H, W));
+    (void)hipSetDevice(e->device);
+    const size_t total = (size_t)B * 3 * H * W;
+    if (through_network) {
+        if (!e->grad_enabled) return fail(e, Status{DPIR_ERR_STATE, "grad_and_value through the denoiser needs gradient mode: dpir_enable_grad before dpir_load_unet"});
+        if (!e->tape.valid || e->tape.serial != e->ps_serial || e->ps_serial != e->fwd_serial || e->ps_x0 != x_hat_dev || e->ps_B != B || e->ps_H != H || e->ps_W != W)
+            return fail(e, Status{DPIR_ERR_STATE, "grad_and_value(x, x_hat): x_hat must be the pred_xstart output of the LAST dpir_p_sample call on this engine "
+                                                  "(the tape of that forward is what the gradient runs through)"});
+    }
+    ProfScope ps(&e->prof, PC_ELEM);
+    float *gup = nullptr, *normv = nullptr;
+    BlurResidual meas; meas.y = measurement_dev;
+    API_TRY(e, blur_residual(e, x_hat_dev, meas, k_dev, kh, B, H, W, &gup, &normv));
+    if (through_network) {
+        float *direct = nullptr, *dxn = nullptr;
+        API_TRY(e, dps_grad_through_network(e, gup, normv, &direct, &dxn, true));
+        API_TRY(e, launch_dps_update(e->stream, nullptr, direct, dxn, 0.f, nullptr, norm_grad_out_dev, total));
+    } else {
+        API_TRY(e, launch_neg_scale_by_norm(e->stream, gup, normv, norm_grad_out_dev, total, B));
+    }
+    if (norm_out_dev) API_HIP(e, hipMemcpyAsync(norm_out_dev, normv, sizeof(float) * B, hipMemcpyDeviceToDevice, e->stream));
+    return DPIR_OK;
+}
+
+int dpir_run_deblur_grad_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, const dpir_dps_coef* coefs, int n_steps, int variant,
+                              float lambda_, const float* noise_ps_dev, const float* noise_yt_dev, float* out_f32, uint8_t* out_u8) {
+    if (!e || !dd || !steps || n_steps <= 0) return fail(e, invalid("dpir_run_deblur_grad_loop: null argument"));
+    if (variant < 0 || variant > 2) return fail(e, invalid("dpir_run_deblur_grad_loop: variant must be 0 (DPS_y0), 1 (DPS_yt) or 2 (first-order data step)"));
+    if (variant != 2 && !coefs) return fail(e, invalid("dpir_run_deblur_grad_loop: the DPS variants need the p_sample coefficients"));
+    (void)hipSetDevice(e->device);
+    const dpir_loop_desc& d = *dd;
+    if (!e->net.loaded) return fail(e, Status{DPIR_ERR_STATE, "dpir_load_unet has not been called"});
+    if (variant == 0 && !e->grad_enabled) return fail(e, Status{DPIR_ERR_STATE, "DPS_y0 needs gradient mode: dpir_enable_grad before dpir_load_unet"});
+    if (d.task != DPIR_TASK_DEBLUR || d.sf != 1) return fail(e, invalid("dpir_run_deblur_grad_loop: the deblurring program runs task deblur (sf 1) only"));
+    if (!d.y_dev || !d.k_dev) return fail(e, invalid("dpir_run_deblur_grad_loop: y and the PSF are required"));
+    API_TRY(e, blur_check("dpir_run_deblur_grad_loop", d.kh, d.kw, d.B, d.H, d.W));
+    if ((e->net.desc.num_classes > 0) != (d.labels_host != nullptr)) return fail(e, invalid("labels iff class-conditional model"));
+    const int B = d.B, H = d.H, W = d.W, K = d.kh, oc = e->net.desc.out_channels;
+    const size_t total = (size_t)B * 3 * H * W;
+    bool with_n1 = false;
+    for (int i = 0; i < n_steps; ++i) {
+        if (i > 0 && steps[i - 1].last && !steps[i].last) return fail(e, invalid("dpir_run_deblur_grad_loop: a non-final step may not follow a final step"));
+        if (variant == 2 && !steps[i].last && steps[i].es != 0.f) with_n1 = true;
+    }
+    if (with_n1 && d.noise_n2_dev && !d.noise_n1_dev) return fail(e, invalid("dpir_run_deblur_grad_loop: eta != 0 with host noise needs noise_n1_dev"));
+    hipStream_t s = e->stream;
+    range_clear(e);
+    LoopBufs b{};
+    float* xprev = nullptr;
+    API_TRY(e, e->ws.getT("loop#x", total, &b.x));
+    API_TRY(e, e->ws.getT("loop#x0", total, &b.x0));
+    API_TRY(e, e->ws.getT("loop#out6", (size_t)B * oc * H * W, &b.out6));
+    API_TRY(e, e->ws.getT("loop#n1", total, &b.n1));
+    API_TRY(e, e->ws.getT("loop#n2", total, &b.n2));
+    API_TRY(e, e->ws.getT("dps#xprev", total, &xprev));
+    API_TRY(e, upload_ints(e, "loop#y", d.labels_host, B, &b.y_dev));
+    // init (main_ddpir_deblur.py:228-231): y noised from its own level t_y up to t_start; the two coefficients come from the host
+    {
+        ProfScope ps(&e->prof, PC_ELEM);
+        const float* n0 = d.noise_init_dev;
+        if (!n0) { API_TRY(e, launch_randn(s, b.n2, d.seed, 0, d.image_offset, B, (size_t)3 * H * W)); n0 = b.n2; }
+        API_TRY(e, launch_init_x(s, d.y_dev, nullptr, n0, d.sa_start, d.s1m_start, b.x, total));
+    }
+    for (int i = 0; i < n_steps; ++i) {
+        const dpir_step& st = steps[i];
+        if (st.last && d.skip_dead_final_eval) continue;
+        std::vector<int64_t> tv(B, st.t);
+        int* t_dev = nullptr;
+        API_TRY(e, upload_ints(e, "loop#tt", tv.data(), B, &t_dev));
+        if (st.last) {                                            // the final denoiser call is dead (main_ddpir_deblur.py:284, 339, 360)
+            API_TRY(e, unet_forward(e, b.x, t_dev, b.y_dev, b.out6, B, H, W));
+            continue;
+        }
+        float *gup = nullptr, *normv = nullptr;
+        BlurResidual meas; meas.y = d.y_dev;                      // measurement = y (:312, :324)
+        if (variant == 2) {
+            // first-order data step (:305-314) in place of the closed-form prox, then the usual re-noise (:339-347)
+            API_TRY(e, unet_forward(e, b.x, t_dev, b.y_dev, b.out6, B, H, W, nullptr, nullptr, true));
+            ProfScope ps(&e->prof, PC_ELEM);
+            API_TRY(e, launch_xstart(s, b.x, b.out6, oc, st.c1, st.c2, b.x0, B, H * W));
+            API_TRY(e, blur_residual(e, b.x0, meas, d.k_dev, K, B, H, W, &gup, &normv));
+            API_TRY(e, launch_grad_step(s, b.x0, gup, normv, 1.f, st.tau, 1.f, b.x0, total, nullptr, B));
+            const float *n1 = nullptr, *n2 = nullptr;
+            if (st.es != 0.f) {
+                if (d.noise_n1_dev) n1 = d.noise_n1_dev + (size_t)i * total;
+                else { API_TRY(e, launch_randn(s, b.n1, d.seed, (uint64_t)4 * i + 1, d.image_offset, B, (size_t)3 * H * W)); n1 = b.n1; }
+            }
+            if (d.noise_n2_dev) n2 = d.noise_n2_dev + (size_t)i * total;
+            else { API_TRY(e, launch_randn(s, b.n2, d.seed, (uint64_t)4 * i + 2, d.image_offset, B, (size_t)3 * H * W)); n2 = b.n2; }
+            API_TRY(e, launch_renoise(s, b.x, b.x0, coef_of(st), n1, n2, total));
+            continue;
+        }
+        const float* nz = noise_ps_dev ? noise_ps_dev + (size_t)i * total : nullptr;
+        if (!nz) { ProfScope ps(&e->prof, PC_ELEM); API_TRY(e, launch_randn(s, b.n2, d.seed, (uint64_t)4 * (i + 1), d.image_offset, B, (size_t)3 * H * W)); nz = b.n2; }
+        PSampleCoef cf{st.c1, st.c2, coefs[i].pc1, coefs[i].pc2, coefs[i].min_log, coefs[i].max_log, st.t != 0 ? 1.0f : 0.0f,
+                       d.ddim_sample, coefs[i].sa_prev, coefs[i].s1m_prev};
+        API_TRY(e, p_sample_impl(e, b.x, t_dev, b.y_dev, cf, nz, b.out6, xprev, b.x0, B, H, W));
+        ProfScope ps(&e->prof, PC_ELEM);
+        if (variant == 1) {
+            // DPS_yt (:329-336): y_t = sa_t (2y - 1) + s1m_t n, measured as y_t / 2 + 0.5 against Tx(xt), differentiated w.r.t. xt itself
+            const float* ny = noise_yt_dev ? noise_yt_dev + (size_t)i * total : nullptr;
+            if (!ny) { API_TRY(e, launch_randn(s, b.n1, d.seed, (uint64_t)4 * (i + 1) + 1, d.image_offset, B, (size_t)3 * H * W)); ny = b.n1; }
+            meas.ma = 2.f; meas.mb = -1.f; meas.sa = st.sa_t; meas.s1m = st.s1m_t; meas.noise = ny; meas.qa = 0.5f; meas.qb = 0.5f;
+            API_TRY(e, blur_residual(e, xprev, meas, d.k_dev, K, B, H, W, &gup, &normv));
+            API_TRY(e, launch_grad_step(s, xprev, gup, normv, lambda_, st.tau, 0.35f, b.x, total, nullptr, B));
+            continue;
+        }
+        // DPS_y0 (:323-327): x = xt - d || y - Tx(x0) || / d x, through the clamp and the denoiser, unit step
+        float *direct = nullptr, *dxn = nullptr;
+        API_TRY(e, blur_residual(e, b.x0, meas, d.k_dev, K, B, H, W, &gup, &normv));
+        API_TRY(e, dps_grad_through_network(e, gup, normv, &direct, &dxn, true));
+        API_TRY(e, launch_dps_update(s, xprev, direct, dxn, 1.f, b.x, nullptr, total));
     }
     {
         ProfScope ps(&e->prof, PC_ELEM);

@@ -43,14 +43,15 @@ Status launch_psample(hipStream_t s, const float* x, const float* out6, int out_
 // norm_out == nullptr: only the partial sums are produced (the caller folds / all-reduces them: launch_norm_fold_ssq, launch_norm_sqrt)
 Status launch_diff_norm(hipStream_t s, const float* y, float ma, float mb, const float* down, float* diff, size_t total, double* part, int nparts,
                         float* norm_out, float sa = 1.f, float s1m = 0.f, const float* noise = nullptr, const LoopDev* lp = nullptr);
+// images != 0: norm holds one value per image (norm[n] scales image n: the deblurring program's per-image norm); 0: norm[0] is the whole batch's
 Status launch_grad_step(hipStream_t s, const float* src, const float* gup, const float* norm, float lam, float rho, float tail, float* dst, size_t total,
-                        const StepDev* sp = nullptr);
+                        const StepDev* sp = nullptr, int images = 0);
 // out = -gup / norm  (d || m - A(x) || / d x for a linear operator A, gup = A^T (m - A(x)))
-Status launch_neg_scale_by_norm(hipStream_t s, const float* gup, const float* norm, float* out, size_t total);
+Status launch_neg_scale_by_norm(hipStream_t s, const float* gup, const float* norm, float* out, size_t total, int images = 0);
 Status launch_band_resample_T(hipStream_t s, const float* gout, const float* w, const int* idx, int taps, int P, int L_in, int L_out, int inner,
                               float scale, float* gin);
 Status launch_dps_seed(hipStream_t s, const float* gup, const float* norm, const unsigned char* inside, float c1, float c2, int out_ch, float* dout6,
-                       float* direct, int B, int HW);
+                       float* direct, int B, int HW, bool norm_per_image = false);
 Status launch_dps_update(hipStream_t s, const float* xprev, const float* direct, const float* dx_net, float step_scale, float* x, float* grad_out,
                          size_t total);
 

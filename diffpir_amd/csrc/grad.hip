@@ -583,14 +583,16 @@ Status launch_band_resample_T(hipStream_t s, const float* gout, const float* w, 
 }
 
 // g0 = -gup / norm (d norm / d x0);  d_out6[:, 0:3] = -c2 inside g0,  d_out6[:, 3:] = 0;  direct[i] = c1 inside g0
+// norm_per_image: norm[n] is image n's own residual norm (the deblurring program restores one image at a time), else norm[0] is the batch's
 __global__ void dps_seed_kernel(const float* gup, const float* norm, const unsigned char* inside, float c1, float c2, int out_ch, float* dout6,
-                                float* direct, int HW, size_t total6) {
+                                float* direct, int HW, size_t total6, int norm_per_image) {
 #pragma clang fp contract(off)
-    const float inv = norm[0] > 0.f ? 1.0f / norm[0] : 0.f;
+    float inv = norm[0] > 0.f ? 1.0f / norm[0] : 0.f;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total6; e += (size_t)gridDim.x * blockDim.x) {
         const size_t n = e / ((size_t)out_ch * HW), r = e - n * (size_t)out_ch * HW;
         const size_t c = r / HW, p = r - c * HW;
         if (c >= 3) { dout6[e] = 0.f; continue; }
+        if (norm_per_image) inv = norm[n] > 0.f ? 1.0f / norm[n] : 0.f;
         const size_t i = (n * 3 + c) * HW + p;
         const float g0 = inside[i] ? -(gup[i] * inv) : 0.f;
         dout6[e] = -(c2 * g0);
@@ -598,9 +600,10 @@ __global__ void dps_seed_kernel(const float* gup, const float* norm, const unsig
     }
 }
 Status launch_dps_seed(hipStream_t s, const float* gup, const float* norm, const unsigned char* inside, float c1, float c2, int out_ch, float* dout6,
-                       float* direct, int B, int HW) {
+                       float* direct, int B, int HW, bool norm_per_image) {
     const size_t total6 = (size_t)B * out_ch * HW;
-    hipLaunchKernelGGL(dps_seed_kernel, dim3((unsigned)((total6 + 255) / 256)), dim3(256), 0, s, gup, norm, inside, c1, c2, out_ch, dout6, direct, HW, total6);
+    hipLaunchKernelGGL(dps_seed_kernel, dim3((unsigned)((total6 + 255) / 256)), dim3(256), 0, s, gup, norm, inside, c1, c2, out_ch, dout6, direct, HW, total6,
+                       norm_per_image ? 1 : 0);
     DPIR_HIP(hipGetLastError());
     return Status{};
 }
@@ -621,14 +624,17 @@ Status launch_dps_update(hipStream_t s, const float* xprev, const float* direct,
     return Status{};
 }
 
-__global__ void neg_scale_by_norm_kernel(const float* gup, const float* norm, float* out, size_t total) {
+// per_img != 0: blockIdx.y is the image, norm[blockIdx.y] its own norm and total the size of one image
+__global__ void neg_scale_by_norm_kernel(const float* gup, const float* norm, float* out, size_t total, size_t per_img) {
 #pragma clang fp contract(off)
+    if (per_img) { const size_t o = (size_t)blockIdx.y * per_img; gup += o; out += o; norm += blockIdx.y; }
     const float nv = norm[0];
     const float inv = nv > 0.f ? 1.0f / nv : 0.f;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) out[i] = -(gup[i] * inv);
 }
-Status launch_neg_scale_by_norm(hipStream_t s, const float* gup, const float* norm, float* out, size_t total) {
-    hipLaunchKernelGGL(neg_scale_by_norm_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, gup, norm, out, total);
+Status launch_neg_scale_by_norm(hipStream_t s, const float* gup, const float* norm, float* out, size_t total, int images) {
+    const size_t per = images ? total / images : 0, cnt = images ? per : total;
+    hipLaunchKernelGGL(neg_scale_by_norm_kernel, dim3((unsigned)((cnt + 255) / 256), images ? images : 1), dim3(256), 0, s, gup, norm, out, cnt, per);
     DPIR_HIP(hipGetLastError());
     return Status{};
 }
@@ -636,11 +642,12 @@ Status launch_neg_scale_by_norm(hipStream_t s, const float* gup, const float* no
 // x <- x - norm_grad * coef, norm_grad = -gup / norm (gradient of || m - A(x) || w.r.t. x), coef = norm * scale / rho:
 //   first-order data step  (main_ddpir.py:428):  x0 = x0 - norm_grad * norm / rhos[t_i]                        (scale = 1)
 //   DPS_yt                 (main_ddpir.py:444):  x  = xt - norm_grad * lambda * norm / rhos[t_i] * 0.35        (evaluated in that order)
-// rho from the device step block when sp != null.
+// rho from the device step block when sp != null.  per_img != 0: blockIdx.y is the image, norm[blockIdx.y] its own norm, total one image's size.
 __global__ void grad_step_kernel(const float* src, const float* gup, const float* norm, float lam, float rho, float tail, float* dst, size_t total,
-                                 const StepDev* sp) {
+                                 const StepDev* sp, size_t per_img) {
 #pragma clang fp contract(off)
     if (sp) rho = sp->tau;
+    if (per_img) { const size_t o = (size_t)blockIdx.y * per_img; src += o; gup += o; dst += o; norm += blockIdx.y; }
     const float nv = norm[0];
     const float inv = nv > 0.f ? 1.0f / nv : 0.f;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -649,8 +656,10 @@ __global__ void grad_step_kernel(const float* src, const float* gup, const float
     }
 }
 Status launch_grad_step(hipStream_t s, const float* src, const float* gup, const float* norm, float lam, float rho, float tail, float* dst, size_t total,
-                        const StepDev* sp) {
-    hipLaunchKernelGGL(grad_step_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, gup, norm, lam, rho, tail, dst, total, sp);
+                        const StepDev* sp, int images) {
+    const size_t per = images ? total / images : 0, cnt = images ? per : total;
+    hipLaunchKernelGGL(grad_step_kernel, dim3((unsigned)((cnt + 255) / 256), images ? images : 1), dim3(256), 0, s, src, gup, norm, lam, rho, tail, dst, cnt,
+                       sp, per);
     DPIR_HIP(hipGetLastError());
     return Status{};
 }

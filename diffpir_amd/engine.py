@@ -84,6 +84,12 @@ class DeviceArray:
         out = DeviceArray(self.engine, self.shape, np.float32)
         e = self.engine
         if isinstance(other, DeviceArray):
+            if other.size not in (1, self.size) and len(self.shape) == 4 and other.shape == self.shape[:1]:
+                # one value per image (the per-image `norm` of the deblurring program's grad_and_value): image n against other[n]
+                per = self.size // self.shape[0]
+                for n in range(self.shape[0]):
+                    e._check(e.lib.dpir_ewise(e.h, op, self.ptr + 4 * n * per, other.ptr + 4 * n, 1, 0.0, out.ptr + 4 * n * per, per))
+                return out
             if other.size not in (1, self.size):
                 raise EngineError(f"shape mismatch: {self.shape} vs {other.shape}")
             e._check(e.lib.dpir_ewise(e.h, op, self.ptr, other.ptr, other.size, 0.0, out.ptr, self.size))
@@ -205,6 +211,14 @@ class Engine:
         B, _, H, W = x_hat.shape
         g, nv = self.empty((B, 3, H, W)), self.empty((1,))
         self._check(self.lib.dpir_grad_and_value(self.h, 1 if through_network else 0, _ptr(x_hat), _ptr(measurement), int(sf), g.ptr, nv.ptr, B, H, W))
+        return g, nv
+
+    def grad_and_value_blur(self, through_network: bool, x_hat, measurement, k, kh: int, kw: int):
+        """(norm_grad [B,3,H,W], norm [B]) of || measurement_n - Tx(x_hat)_n ||_2, one norm per image (dpir_grad_and_value_blur)."""
+        B, _, H, W = x_hat.shape
+        g, nv = self.empty((B, 3, H, W)), self.empty((B,))
+        self._check(self.lib.dpir_grad_and_value_blur(self.h, 1 if through_network else 0, _ptr(x_hat), _ptr(measurement), _ptr(k), int(kh), int(kw),
+                                                      g.ptr, nv.ptr, B, H, W))
         return g, nv
 
     def load_unet(self, desc: "_lib.UNetDesc", state_dict: Dict[str, np.ndarray]):

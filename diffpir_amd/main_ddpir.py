@@ -65,7 +65,8 @@ def loop_config(config, lambda_, zeta) -> restore.LoopConfig:
                               model_output_type=config.model_output_type, sub_1_analytic=config.sub_1_analytic,
                               ddim_sample=config.ddim_sample, iter_num_U=config.iter_num_U,
                               noise_init_img=config.get("noise_init_img", "max"),
-                              skip_noise_model_t=bool(config.get("skip_noise_model_t", False)))
+                              skip_noise_model_t=bool(config.get("skip_noise_model_t", False)),
+                              driver=config.get("driver", "main_ddpir"))
 
 
 def sweeps(config):
@@ -268,6 +269,11 @@ def main(argv=None):
             u8_local = eng.empty((hi - lo, H, W, 3), np.uint8)          # engine-owned result buffer (send side of the all-gather)
             drawn = None
             dps_mode = cfg.generate_mode in ("DPS_y0", "DPS_yt")
+            # driver: main_ddpir_deblur -- the standalone deblurring program's gradient modes pull their noise through noise_fn and run eagerly on one GPU
+            deb_grad = cfg.driver == "main_ddpir_deblur" and (dps_mode or not cfg.sub_1_analytic)
+            if deb_grad and world > 1:
+                raise NotImplementedError("driver main_ddpir_deblur: the gradient modes are single-GPU")
+            dps_mode = dps_mode or deb_grad
             ddist.check_dps_sharding(eng, cfg, n_b, world)
             dps_nf = None
             if noise == "host" and dps_mode:
@@ -294,7 +300,7 @@ def main(argv=None):
                                      noise_level_img=config.noise_level_img, sf=config.sf, sr_mode=config.sr_mode, seed=config.seed + 1,
                                      image_offset=i0 + lo)
                 out_f32 = restore.restore_batch(eng, cfg, y, k=ops.get("k"), mask=None if dps_mode else ops.get("mask"), noise_source=noise,
-                                                predrawn=drawn, noise_fn=dps_nf, seed=config.seed, image_offset=i0 + lo, use_graph=use_graph, out_u8=u8_local, _cache=cache,
+                                                predrawn=drawn, noise_fn=dps_nf, seed=config.seed, image_offset=i0 + lo, use_graph=use_graph and not deb_grad, out_u8=u8_local, _cache=cache,
                                                 skip_dead_final_eval=bool(config.get("engine_skip_dead_final_eval", False)))
                 psnr_i, psnr_y_i = dgr.metrics(eng, out_f32, ops["gt"])            # dpir_metrics: per-image PSNR / PSNR-Y
                 per_img = np.stack([psnr_i, psnr_y_i], 1).astype(np.float64)

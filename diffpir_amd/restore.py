@@ -53,6 +53,10 @@ class LoopConfig:
     iter_num_U: int = 1
     noise_init_img: object = "max"      # 'max' -> t_start = T-1, else a noise level in /255 units (main_ddpir.py:197-200)
     skip_noise_model_t: bool = False    # main_ddpir.py:192-195, 391
+    # which reference program's semantics the loop follows: "main_ddpir" (every task; refuses the gradient modes for deblurring, as that
+    # program does) or "main_ddpir_deblur" (the standalone deblurring program: the reflect-padded blur operator in DPS_y0 / DPS_yt / the
+    # first-order data step, its t_y initialisation of x in every mode, one image's own residual norm)
+    driver: str = "main_ddpir"
 
     @property
     def sigma(self):
@@ -68,6 +72,15 @@ class LoopConfig:
         raise ValueError(f"unknown task {self.task}")
 
     def check_supported(self):
+        if self.driver not in DRIVERS:
+            raise ValueError(f"driver={self.driver!r}: expected one of {DRIVERS}")
+        if self.driver == "main_ddpir_deblur":
+            if self.task != "deblur":
+                raise ValueError("driver='main_ddpir_deblur' is the standalone deblurring program: task must be 'deblur'")
+            if self.generate_mode not in ("DiffPIR", "DPS_y0", "DPS_yt") or self.model_output_type != "pred_xstart" or self.iter_num_U != 1:
+                raise NotImplementedError("driver='main_ddpir_deblur' runs generate_mode DiffPIR (sub_1_analytic true or false), DPS_y0 and DPS_yt with "
+                                          "model_output_type=pred_xstart, iter_num_U=1")
+            return
         # ddim_sample is accepted: with model_output_type=pred_xstart it selects the same x0 prediction and the same number
         # of RNG draws as p_sample (utils_model.py:219-240; tests/golden/model_fn.npz).  iter_num_U > 1 cannot be mirrored:
         # the reference raises IndexError on `seq[i+1]` at its last step (main_ddpir.py:448-451 with u < iter_num_U-1).
@@ -89,6 +102,7 @@ class LoopConfig:
             raise NotImplementedError("generate_mode repaint / vanilla are inpainting modes in the reference")
 
 
+DRIVERS = ("main_ddpir", "main_ddpir_deblur")
 GENERATE_MODES = {"DiffPIR": 0, "repaint": 1, "vanilla": 2, "DPS_y0": 3, "DPS_yt": 4}
 
 
@@ -97,6 +111,19 @@ def t_start_of(cfg: LoopConfig, reduced) -> int:
     if cfg.noise_init_img == "max":
         return cfg.num_train_timesteps - 1
     return find_nearest(reduced, 2 * float(cfg.noise_init_img) / 255)
+
+
+def start_coefficients(cfg: LoopConfig, dt):
+    """(sa, s1m) of the initial x = sa (2y - 1) + s1m randn_like(y), float32.  main_ddpir.py:315 places y at t_start as if it were clean;
+    main_ddpir_deblur.py:228-231 noises it from its own level t_y up to t_start, on the driver's float32 tables."""
+    t_start = t_start_of(cfg, dt.reduced)
+    sa, s1m = np.float32(dt.sqrt_ac[t_start]), np.float32(dt.sqrt_1m_ac[t_start])
+    if cfg.driver != "main_ddpir_deblur":
+        return sa, s1m
+    t_y = find_nearest(dt.reduced, 2 * cfg.noise_level_img)
+    eff = np.float32(sa / np.float32(dt.sqrt_ac[t_y]))
+    s1m_y = np.float32(dt.sqrt_1m_ac[t_y])
+    return eff, np.sqrt(np.float32(np.float32(s1m * s1m) - np.float32(np.float32(eff * eff) * np.float32(s1m_y * s1m_y))), dtype=np.float32)
 
 
 def _steps(cfg: LoopConfig):
@@ -148,6 +175,10 @@ def restore_batch(engine: Engine, cfg: LoopConfig, y, k=None, mask=None, labels=
     Returns a DeviceArray [B,3,H,W] = x_0 in [0,1] (un-clamped, main_ddpir.py:470), and the u8 NHWC
     array as well when return_u8."""
     cfg.check_supported()
+    if cfg.driver == "main_ddpir_deblur" and (cfg.generate_mode != "DiffPIR" or not cfg.sub_1_analytic):
+        if predrawn is not None or mask is not None or use_graph:
+            raise NotImplementedError("the deblurring program's gradient modes take host noise through noise_fn, no mask and no step graph")
+        return _restore_deblur_grad(engine, cfg, y, k, labels, noise_source, noise_fn, seed, image_offset, skip_dead_final_eval, out_f32, out_u8, return_u8)
     if cfg.generate_mode in ("DPS_y0", "DPS_yt"):
         if predrawn is not None or mask is not None:
             raise NotImplementedError("DPS modes take host noise through noise_fn (their draw order differs from the DiffPIR loop's) and no mask")
@@ -172,8 +203,7 @@ def restore_batch(engine: Engine, cfg: LoopConfig, y, k=None, mask=None, labels=
     if k is not None:
         d.kh, d.kw = k.shape[2], k.shape[3]
     d.in_iter, d.gamma, d.guidance = cfg.inIter, cfg.gamma, cfg.guidance_scale
-    t_start = t_start_of(cfg, dt.reduced)
-    d.sa_start, d.s1m_start = float(dt.sqrt_ac[t_start]), float(dt.sqrt_1m_ac[t_start])
+    d.sa_start, d.s1m_start = [float(v) for v in start_coefficients(cfg, dt)]
     d.y_dev, d.k_dev, d.mask_dev = _ptr(y), _ptr(k), _ptr(mask)
     lab = None
     if labels is not None:
@@ -226,7 +256,78 @@ def dps_host_noise_shapes(cfg: LoopConfig, steps, B: int, H: int, W: int):
         shapes.append((B, 3, H, W))
         if cfg.generate_mode == "DPS_yt" and not st["last"]:
             shapes.append((B, 3, h, w))
+        if cfg.driver == "main_ddpir_deblur" and cfg.generate_mode == "DiffPIR" and not st["last"]:
+            shapes += [(B, 3, H, W)] * 2          # the re-noise's two draws (main_ddpir_deblur.py:346-347), analytic and first-order alike
     return shapes
+
+
+def _restore_deblur_grad(engine, cfg, y, k, labels, noise_source, noise_fn, seed, image_offset, skip_dead_final_eval, out_f32, out_u8, return_u8):
+    """driver 'main_ddpir_deblur', generate_mode DPS_y0 / DPS_yt / DiffPIR with sub_1_analytic false: dpir_run_deblur_grad_loop.  Host noise is
+    drawn batch-shaped in the loop's order (dps_host_noise_shapes); image n uses slice n."""
+    from .schedule import DiffusionTables
+    variant = {"DPS_y0": 0, "DPS_yt": 1, "DiffPIR": 2}[cfg.generate_mode]
+    if variant == 0 and not engine.grad:
+        raise EngineError("generate_mode DPS_y0 needs Engine.enable_grad() before the model is loaded")
+    if k is None:
+        raise EngineError("the deblurring program needs the PSFs k [B,1,K,K]")
+    dt, steps, arr = _steps(cfg)
+    dtab = DiffusionTables.make(cfg.num_train_timesteps)
+    coefs = (_lib.DpsCoef * len(steps))()
+    for i, st in enumerate(steps):
+        coefs[i].pc1, coefs[i].pc2, coefs[i].min_log, coefs[i].max_log = [float(v) for v in dtab.dps_coef(st["t"])]
+        coefs[i].sa_prev, coefs[i].s1m_prev = [float(v) for v in dtab.ddim_coef(st["t"])]
+    yd = engine.to_device(y, np.float32) if isinstance(y, np.ndarray) else y
+    kd = engine.to_device(k, np.float32) if isinstance(k, np.ndarray) else k
+    B, _, H, W = yd.shape
+    shape = (B, 3, H, W)
+    d = _lib.LoopDesc()
+    d.task, d.B, d.H, d.W, d.sf = TASKS["deblur"], B, H, W, 1
+    d.kh, d.kw = kd.shape[2], kd.shape[3]
+    d.sa_start, d.s1m_start = [float(v) for v in start_coefficients(cfg, dt)]
+    d.y_dev, d.k_dev = _ptr(yd), _ptr(kd)
+    lab = None
+    if labels is not None:
+        lab = np.ascontiguousarray(labels, dtype=np.int64)
+        d.labels_host = lab.ctypes.data
+    keep = [yd, kd]
+    nps = nyt = None
+    if noise_source == "host":
+        if noise_fn is None:
+            raise EngineError("noise_source='host' needs noise_fn")
+        if variant == 2:
+            init, n1, n2 = draw_host_noise(noise_fn, steps, shape, cfg.eta != 0)
+            keep += [engine.to_device(init), engine.to_device(n2)]
+            d.noise_init_dev, d.noise_n2_dev = keep[-2].ptr, keep[-1].ptr
+            if n1 is not None:
+                keep.append(engine.to_device(n1))
+                d.noise_n1_dev = keep[-1].ptr
+        else:
+            init = np.asarray(noise_fn(shape), dtype=np.float32)
+            ps, yt = [], []
+            for st in steps:
+                ps.append(np.asarray(noise_fn(shape), dtype=np.float32))
+                yt.append(np.asarray(noise_fn(shape), dtype=np.float32) if variant == 1 and not st["last"] else None)
+            di, nps = engine.to_device(init), engine.to_device(np.stack(ps))
+            keep += [di, nps]
+            if variant == 1:
+                nyt = engine.to_device(np.stack([np.zeros(shape, np.float32) if a is None else a for a in yt]))
+                keep.append(nyt)
+            d.noise_init_dev = di.ptr
+    elif noise_source != "device":
+        raise ValueError("noise_source must be 'host' or 'device'")
+    d.seed, d.image_offset = seed, image_offset
+    d.skip_dead_final_eval = int(skip_dead_final_eval)
+    d.generate_mode = GENERATE_MODES[cfg.generate_mode]
+    d.first_order = 1 if variant == 2 else 0
+    d.ddim_sample = 1 if cfg.ddim_sample else 0
+    if out_f32 is None:
+        out_f32 = engine.empty(shape)
+    if out_u8 is None and return_u8:
+        out_u8 = engine.empty((B, H, W, 3), np.uint8)
+    engine._check(engine.lib.dpir_run_deblur_grad_loop(engine.h, C.byref(d), arr, coefs, len(steps), variant, float(cfg.lambda_),
+                                                       _ptr(nps), _ptr(nyt), _ptr(out_f32), _ptr(out_u8)))
+    engine.sync()
+    return (out_f32, out_u8) if return_u8 else out_f32
 
 
 def _restore_dps(engine, cfg, y, labels, noise_source, noise_fn, seed, image_offset, skip_dead_final_eval, out_f32, out_u8, return_u8):
@@ -303,6 +404,7 @@ def restore_batch_stepwise(model, diffusion, cfg: LoopConfig, y, k=None, mask=No
     lib, hnd = eng.lib, eng.h
     x = eng.empty(shape)
     dps = "DPS" in cfg.generate_mode
+    deb = cfg.driver == "main_ddpir_deblur"      # main_ddpir_deblur.py's loop body: Tx as degrade_op, measurement y in [0, 1], t_y initialisation
     # (3) initialize x (main_ddpir.py:293-315)
     if cfg.task == "sr":
         degrade_op = Resizer(shape, 1 / cfg.sf, engine=eng)
@@ -311,11 +413,14 @@ def restore_batch_stepwise(model, diffusion, cfg: LoopConfig, y, k=None, mask=No
         xs = src.numpy()
     elif cfg.task == "deblur":
         xs = y.numpy()
+        if deb:
+            from .utils_deblur import BlurOperator
+            degrade_op = BlurOperator(k, engine=eng)            # Tx (main_ddpir_deblur.py:307-311, 317-321)
     else:
         xs = y.numpy() * mask.numpy().astype(np.float32)
-    t_start = t_start_of(cfg, dt.reduced)
+    sa0, s1m0 = start_coefficients(cfg, dt)                     # main_ddpir.py:315 / main_ddpir_deblur.py:228-231
     n0 = np.asarray(noise_fn(shape), np.float32)
-    x.copy_from(dt.sqrt_ac[t_start] * (np.float32(2) * xs - np.float32(1)) + dt.sqrt_1m_ac[t_start] * n0)
+    x.copy_from(sa0 * (np.float32(2) * xs - np.float32(1)) + s1m0 * n0)
     if cfg.task in ("sr", "deblur") and not (cfg.task == "sr" and cfg.sr_mode == "cubic") and not dps and cfg.sub_1_analytic:
         FB, FBC, F2B, FBFy = sr.pre_calculate(y, k, cfg.sf, engine=eng)
     kwargs = {} if labels is None else {"y": labels}
@@ -340,14 +445,16 @@ def restore_batch_stepwise(model, diffusion, cfg: LoopConfig, y, k=None, mask=No
             if st["last"]:
                 continue
             tau = np.float32(st["tau"])                         # rhos[t_i]
-            if cfg.generate_mode == "DPS_y0":                   # main_ddpir.py:434-438
-                measurement = 2 * y - 1
+            if cfg.generate_mode == "DPS_y0":                   # main_ddpir.py:434-438 / main_ddpir_deblur.py:323-327
+                measurement = y if deb else 2 * y - 1
                 norm_grad, norm = utils_model.grad_and_value(operator=degrade_op, x=x, x_hat=x0, measurement=measurement)
                 x = xt - norm_grad * 1.
                 x = x.detach_()
                 continue
             if cfg.generate_mode == "DPS_yt":                   # main_ddpir.py:439-445
                 y_t = dt.sqrt_ac[t_i] * (2 * y - 1) + dt.sqrt_1m_ac[t_i] * draw(y)
+                if deb:                                         # main_ddpir_deblur.py:331
+                    y_t = y_t / 2 + 0.5
                 measurement = y_t
                 norm_grad, norm = utils_model.grad_and_value(operator=degrade_op, x=xt, x_hat=xt, measurement=measurement)
                 x = xt - norm_grad * cfg.lambda_ * norm / tau * 0.35
@@ -357,12 +464,16 @@ def restore_batch_stepwise(model, diffusion, cfg: LoopConfig, y, k=None, mask=No
                 pass                                            # no data-fidelity step outside DiffPIR mode (main_ddpir.py:385)
             elif not cfg.sub_1_analytic:                        # main_ddpir.py:420-430 (task sr)
                 x0 = x0.requires_grad_()
-                measurement = 2 * y - 1
+                measurement = y if deb else 2 * y - 1           # main_ddpir_deblur.py:312
                 norm_grad, norm = utils_model.grad_and_value(operator=degrade_op, x=x0, x_hat=x0, measurement=measurement)
                 x0 = x0 - norm_grad * norm / tau
                 x0 = x0.detach_()
             elif cfg.task == "inpaint":
                 eng._check(lib.dpir_prox_mask(hnd, x0.ptr, _ptr(y), _ptr(mask), float(tau), cfg.guidance_scale, B, H, W))
+            elif deb:
+                # main_ddpir_deblur.py:291-295 through the entry that replaces those lines as a whole (dpir_prox_fft_apply): the kernels and the
+                # roundings of dpir_run_loop's data step, which at guidance_scale 1 writes 2 data_solution(.) - 1 without forming x0 + 1 (. - x0)
+                eng._check(lib.dpir_prox_fft_apply(hnd, FB.spectra.handle, x0.ptr, float(tau), float(cfg.guidance_scale)))
             elif cfg.task == "deblur" or cfg.sr_mode == "blur":
                 x0_p = eng.empty(shape)
                 eng._check(lib.dpir_finalize(hnd, x0.ptr, x0_p.ptr, None, B, H, W))          # x0/2+.5

@@ -93,10 +93,16 @@ def model_fn(x, noise_level, model_diffusion, vec_t=None, model_out_type='pred_x
 
 def grad_and_value(operator, x, x_hat, measurement):
     """utils/utils_model.py:390-394 -- (d ||measurement - operator(x_hat)|| / d x, the norm) -- for the operator the reference can run it
-    with: utils_resizer.Resizer (task sr, main_ddpir.py:294).  `x is x_hat`: the gradient w.r.t. the operator's own argument
+    with: utils_resizer.Resizer (task sr, main_ddpir.py:294) -- and for utils_deblur.BlurOperator, the Tx of main_ddpir_deblur.py.  `x is x_hat`: the gradient w.r.t. the operator's own argument
     (first-order data step :425, DPS_yt :443).  Otherwise x must be the input and x_hat the pred_xstart output of the LAST
     model_fn(..., 'pred_x_prev_and_start') call (DPS_y0 :436): the gradient runs through the clamp and the denoiser's tape."""
     from .utils_resizer import Resizer
+    from .utils_deblur import BlurOperator
+    if isinstance(operator, BlurOperator):
+        # main_ddpir_deblur.py:312, 324, 334: Tx of the standalone deblurring program; measurement in [0, 1]; the norm is per image (that
+        # program restores one image at a time)
+        eng = x_hat.engine
+        return eng.grad_and_value_blur(x is not x_hat, x_hat, measurement, operator.psf(x_hat.shape[0]), operator.kh, operator.kw)
     if not isinstance(operator, Resizer):
         raise NotImplementedError("grad_and_value: the engine differentiates through diffpir_amd.utils_resizer.Resizer (the reference's deblurring "
                                   "degrade_op raises at main_ddpir.py:302 and inpainting has none)")

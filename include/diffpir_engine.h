@@ -327,6 +327,38 @@ int dpir_eps_from_xstart(dpir_engine* e, const float* x_dev, const float* x0_dev
 int dpir_grad_and_value(dpir_engine* e, int through_network, const float* x_hat_dev, const float* measurement_dev, int sf,
                         float* norm_grad_out_dev, float* norm_out_dev, int B, int H, int W);
 
+/* ---- the standalone deblurring program's gradient modes (main_ddpir_deblur.py) ------------------------------------------------ */
+/* main_ddpir.py cannot run DPS_y0 / DPS_yt / the first-order data step for deblurring (its batched-k einsum raises at :302), and the entries
+ * above keep refusing it.  The reference's second driver, main_ddpir_deblur.py, does run them, with its own operator and initialisation;
+ * the entries below are that program's semantics, selected explicitly.
+ *
+ * dpir_blur_reflect replaces Tx (main_ddpir_deblur.py:307-311, 317-321): F.conv2d(ReflectionPad2d(K // 2)(x / 2 + 0.5), eye(3) (x) k), :179-180:
+ *   out[n,c,i,j] = sum_{a,b} k[n,a,b] v[n,c, r_H(i+a-p), r_W(j+b-p)],  v = x xa + xb,  p = K / 2,  r_L the reflection -t -> t, L-1+t -> L-1-t
+ *   (cross-correlation, the edge sample not repeated).  x_dev, out_dev [B,3,H,W]; k_dev [B,1,kh,kw], one PSF per image.  The loop passes
+ *   xa = xb = 0.5.  fp32 fmaf accumulation in ascending (a, b) order, independent of tiling and batch: image n equals the same image run alone.
+ * dpir_blur_reflect_adjoint replaces what torch.autograd derives from Tx inside utils_model.grad_and_value (utils/utils_model.py:390-394):
+ *   gx = xa R^T C^T g (the transposed correlation on the padded grid, the reflected border folded back), a gather without atomics.
+ * Both return DPIR_ERR_INVALID before anything is allocated or enqueued when kh != kw, K is even (the reference's output would not have y's
+ * size), K / 2 >= H or W (ReflectionPad2d refuses it) or B <= 0, and DPIR_ERR_UNSUPPORTED for K > 79. */
+int dpir_blur_reflect(dpir_engine* e, const float* x_dev, const float* k_dev, int kh, int kw, float xa, float xb, float* out_dev, int B, int H, int W);
+int dpir_blur_reflect_adjoint(dpir_engine* e, const float* g_dev, const float* k_dev, int kh, int kw, float xa, float* gx_dev, int B, int H, int W);
+/* utils_model.grad_and_value(operator=Tx, x, x_hat, measurement) as main_ddpir_deblur.py:312, 324, 334 call it: difference = measurement - Tx(x_hat),
+ * measurement_dev [B,3,H,W] in [0,1] (y, or y_t / 2 + 0.5).  The program restores one image at a time, so the norm is PER IMAGE:
+ * norm_out_dev [B] (may be NULL), norm_grad_out_dev[n] = d norm_n / d x_n.  through_network and its tape preconditions as dpir_grad_and_value. */
+int dpir_grad_and_value_blur(dpir_engine* e, int through_network, const float* x_hat_dev, const float* measurement_dev, const float* k_dev, int kh, int kw,
+                             float* norm_grad_out_dev, float* norm_out_dev, int B, int H, int W);
+/* The loop of main_ddpir_deblur.py:257-360 in its gradient modes, task DPIR_TASK_DEBLUR, sf 1, k_dev required:
+ *   variant 0 'DPS_y0' (:323-327): xt, x0 = p_sample(x);  x = xt - d || y - Tx(x0) || / d x  (through the denoiser; gradient mode), no re-noising;
+ *   variant 1 'DPS_yt' (:329-336): y_t = sa_t (2y-1) + s1m_t n;  x = xt - d || (y_t/2+.5) - Tx(xt) || / d xt * lambda * norm / rho_t * 0.35, no re-noising;
+ *   variant 2 first-order data step (sub_1_analytic false, :305-314): x0 = pred_xstart;  x0 <- x0 - d || y - Tx(x0) || / d x0 * norm / rho_t, then the
+ *             DiffPIR re-noise (:339-347; noise_n1_dev / noise_n2_dev of the descriptor, [n_steps - 1, B,3,H,W], or device Philox).
+ * norm is each image's own.  The initial x = sa_start (2y-1) + s1m_start n0 takes the descriptor's coefficients, which the host computes from t_y
+ * (:228-231): sqrt_ac[t_start] / sqrt_ac[t_y] and sqrt(s1m[t_start]^2 - that^2 s1m[t_y]^2) on the driver's float32 tables.  The analytic DiffPIR
+ * mode of that program is dpir_run_loop with the same two coefficients.  coefs_host (variants 0, 1), noise_ps_dev, noise_yt_dev [n_steps, B,3,H,W]
+ * and the Philox streams as dpir_run_dps_loop.  Eager launches (no step graph); single GPU. */
+int dpir_run_deblur_grad_loop(dpir_engine* e, const dpir_loop_desc* d, const dpir_step* steps_host, const dpir_dps_coef* coefs_host, int n_steps,
+                              int variant, float lambda_, const float* noise_ps_dev, const float* noise_yt_dev, float* out_f32_dev, uint8_t* out_u8_dev);
+
 /* ---- multi-GPU: the one collective of the path ------------------------------ */
 /* One process and one engine per GPU; images are block-partitioned over ranks, no exchange inside the loop (the reference is
  * single-GPU: main_ddpir.py:135 sets world_size and never uses it).  After a batch, ONE all-gather of the uint8 results over
