@@ -159,6 +159,8 @@ def load_debug():
         fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]
     d.dpir_debug_conv7_check.argtypes = [C.c_void_p] + [C.c_int] * 10 + [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_ulonglong),
                                                                         C.POINTER(C.c_float), C.POINTER(C.c_int)]
+    d.dpir_debug_conv5_layer.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 7 + [C.POINTER(C.c_int)]
+    d.dpir_debug_conv5_layer.restype = C.c_int
     for n in ("dpir_debug_conv_bench", "dpir_debug_victim", "dpir_debug_victim_alu", "dpir_debug_victim_fft_pk", "dpir_debug_victim_fft_nopk",
               "dpir_debug_conv7_check"):
         getattr(d, n).restype = C.c_int

@@ -193,9 +193,13 @@ struct Conv5Args {
     // blocked [B][2*ceil(C/16)][HW][8] f16 (act.hip's layout); requires prm == null (the 1x1 itself multiplies the raw input)
     const float4* emit_prm = nullptr; void* emit_hi = nullptr; void* emit_lo = nullptr;
     const float* out_scale_dev = nullptr;      // optional device scalar folded into the output scale (dgrad)
+    int force_tile = 0;                        // tests only: 1 = the 128 x 256 tile, 2 = the 64 x 128 tile, whatever the workgroup count; 0 = launch_conv5 decides
 };
 constexpr int kConv5EmitMaxC = 384;            // channels of the GroupNorm table the plane-emitting variant stages in LDS
 bool conv5_supported(int B, int Cout, int H, int W, bool has_prm = false);
+// true when launch_conv5 runs this launch on the small (64 co x 128 px) tile: shapes the large tile leaves most of the chip idle on,
+// including some conv5_supported refuses (the 8 x 8 layers at the benched batches)
+bool conv5_small_supported(int B, int ca, int cb, int Cout, int H, int W, bool has_prm = false);
 Status launch_conv5(hipStream_t s, const Conv5Args& a);
 float pack_weights_f16x3_1x1(const float* w_oi, int cout, int cin, std::vector<uint16_t>& out);
 // conv8.hip: GroupNorm affine + SiLU + f16 split + 3x3 convolution to <= 16 output channels in one kernel (the network's output layer)

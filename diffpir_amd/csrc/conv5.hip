@@ -4,6 +4,10 @@
 // one 1 KiB piece per channel row; the virtual concat is resolved per piece) and each lane splits its own B fragment
 // (8 channels of one pixel) into f16 hi/lo on the VALU, which runs beside the f16 MFMA pipe.
 // Tile: 128 output channels x 256 flattened pixels, 4 waves x (128 co x 64 px).  X is read from HBM once per 128 output channels.
+// Small tile: 64 output channels x 128 pixels, 4 waves x (64 co x 32 px), for launches whose 128 x 256 tiling leaves most of the chip
+// idle (the 1x1 layers at 8^2 .. 32^2: 16 .. 128 workgroups on 256 CUs, each walking the whole K serially).  Same kernel body, same
+// chunk order and the same MFMA sequence per accumulator element, so both tiles give the same bits; the tile is chosen per launch
+// (launch_conv5: DPIR_CONV5_SMALL, DPIR_CONV5_SMALL_BELOW).  Flattened pixels run across images, so at 8^2 a pixel tile is two whole images.
 //
 // Pipeline (r3).  The K loop runs on a THREE-stage LDS ring (24 KiB per stage: 16 KiB activations + 8 KiB weights; <= 80 KiB per
 // workgroup, two workgroups per CU) with the DMA of chunk c+2 issued while chunk c is multiplied, ordered by the wave's own counted
@@ -28,8 +32,9 @@ struct Conv5K {
     const float4* prm;
     const char* w16; const float* bias; float* out; const float* res;
     int B, Cout, HW;
-    int n_chunks, n_co_blocks;
-    int n_tiles, pair_xcd;            // 256-pixel tiles; co-blocks of a tile on one XCD (n_co_blocks > 1)
+    int n_chunks, n_co_blocks;        // n_co_blocks: output-channel blocks of the TILE (128 or 64 channels)
+    int n_wblocks;                    // 128-channel blocks of the weight pack (pack_weights_f16x3_1x1)
+    int n_tiles, pair_xcd;            // pixel tiles; co-blocks of a tile on one XCD (n_co_blocks > 1)
     long long total_px;
     float out_scale;
     const float* out_scale_dev;       // optional device scalar multiplied into out_scale (dgrad)
@@ -53,20 +58,19 @@ __device__ __forceinline__ float gn_apply(float v, const float4 m, bool silu) {
 // compiler's waitcnt pass then does not put `s_waitcnt vmcnt(0)` in front of every ds_read that follows an LDS-DMA instruction (it
 // cannot tell which DMA a read depends on and waits for all of them, i.e. for the prefetch just issued); the counted waits in the
 // caller are the real ordering.
-template <bool HAS_PRM, bool X1, bool EMIT>
+template <bool HAS_PRM, bool X1, bool EMIT, int WCO, int WPX, int TPX>
 __device__ __forceinline__ bool conv5_chunk(const float* __restrict__ xs, const half8* __restrict__ wh, const float4* __restrict__ ps,
-                                            const float4* __restrict__ eprm, const int (&pxl)[2], const int (&pimg)[2], bool silu, bool emit_wg,
-                                            _Float16* __restrict__ ehi, _Float16* __restrict__ elo, const size_t (&eoff)[2], size_t echunk,
-                                            floatx16 (&acc)[4][2]) {
-    constexpr int WCO = 4, WPX = 2;
-    const half8* wl = wh + 256;
+                                            const float4* __restrict__ eprm, const int (&pxl)[WPX], const int (&pimg)[WPX], bool silu, bool emit_wg,
+                                            _Float16* __restrict__ ehi, _Float16* __restrict__ elo, const size_t (&eoff)[WPX], size_t echunk,
+                                            floatx16 (&acc)[WCO][WPX]) {
+    const half8* wl = wh + 2 * (32 * WCO);      // lo halves: two k-half planes of the tile's channels further on
     bool bad = false;
     half8 bh[WPX], bl[WPX];
 #pragma unroll
     for (int j = 0; j < WPX; ++j) {
         float v[8];
 #pragma unroll
-        for (int jj = 0; jj < 8; ++jj) v[jj] = xs[jj * 256 + pxl[j]];
+        for (int jj = 0; jj < 8; ++jj) v[jj] = xs[jj * TPX + pxl[j]];
         if (HAS_PRM) {
 #pragma unroll
             for (int jj = 0; jj < 8; ++jj) v[jj] = gn_apply(v[jj], ps[pimg[j] * 16 + jj], silu);
@@ -120,14 +124,17 @@ __device__ __forceinline__ bool conv5_chunk(const float* __restrict__ xs, const 
     return bad;
 }
 
-template <bool HAS_PRM, bool X1, bool EMIT>
-__global__ __launch_bounds__(256, 2) void conv5_mfma_kernel(Conv5K p) {
+// The kernel body of both tiles.  WCO x WPX: 32 x 32 MFMA blocks per wave (output channels x pixels); the tile is 32 WCO channels x
+// 128 WPX pixels (4 waves side by side along the pixels).  NST: ring stages, the DMA runs NST - 1 chunks ahead of the MFMAs.
+template <bool HAS_PRM, bool X1, bool EMIT, int WCO, int WPX, int NST>
+__device__ __forceinline__ void conv5_body(const Conv5K p) {
     static_assert(!(HAS_PRM && EMIT), "the emitting variant multiplies the raw input");
+    static_assert(!EMIT || (WCO == 4 && WPX == 2 && NST == 3), "planes are emitted by the 128 x 256 tile only");
+    static_assert((WPX == 1 || WPX == 2) && (WCO == 2 || WCO == 4) && NST >= 3 && NST <= 4, "tile / ring shapes the DMA split is written for");
 #if defined(__HIP_DEVICE_COMPILE__)
-    constexpr int WCO = 4, WPX = 2;
-    constexpr int NST = 3;                   // ring stages: DMA runs two chunks ahead of the MFMAs
-    constexpr int XBYTES = 16 * 1024;        // [16 ch][256 px] fp32
-    constexpr int WBYTES = 8 * 1024;         // [hi|lo][k-half][128 co][8] f16
+    constexpr int TCO = 32 * WCO, TPX = 128 * WPX;
+    constexpr int XBYTES = 16 * TPX * 4;     // [16 ch][TPX px] fp32
+    constexpr int WBYTES = TCO * 64;         // [hi|lo][k-half][TCO co][8] f16
     constexpr int PBYTES = HAS_PRM ? 1024 : 0;   // [4 images][16 ch] GroupNorm table rows of the chunk
     constexpr int STAGE = XBYTES + WBYTES + PBYTES;
     constexpr int NSTORE = EMIT ? (X1 ? WPX : 2 * WPX) : 0;     // plane stores per wave and chunk (emitting workgroups)
@@ -135,7 +142,7 @@ __global__ __launch_bounds__(256, 2) void conv5_mfma_kernel(Conv5K p) {
     // LDS-DMA instruction writes and puts `s_waitcnt vmcnt(0)` in front of the first ds_read after every prefetch (seen in the ISA of
     // the first plane-emitting version: the prefetch distance was zero).
     __shared__ __attribute__((aligned(16))) char smem5[NST * STAGE + 512 + (EMIT ? kConv5EmitMaxC * 16 : 0)];
-    float* bias_sh = reinterpret_cast<float*>(smem5 + NST * STAGE);        // this co-block's 128 bias values
+    float* bias_sh = reinterpret_cast<float*>(smem5 + NST * STAGE);        // this co-block's bias values
     // EMIT: the GroupNorm table of the tile's image, staged once (a 256-pixel tile lies inside one image: HW % 256 == 0); read
     // back as half-wave broadcasts -- per-lane global loads of it (16 per chunk) made the kernel request-bound
     float4* eprm_sh = reinterpret_cast<float4*>(smem5 + NST * STAGE + 512);
@@ -158,7 +165,7 @@ __global__ __launch_bounds__(256, 2) void conv5_mfma_kernel(Conv5K p) {
         co_blk = bid % p.n_co_blocks;
         tile = bid / p.n_co_blocks;
     }
-    const int px0 = tile * 256;             // B * HW < 2^31 (launch_conv5): 32-bit pixel arithmetic
+    const int px0 = tile * TPX;             // B * HW < 2^31 (launch_conv5): 32-bit pixel arithmetic
     const int C = p.ca + p.cb;
     const int HW = p.HW;
     const int total_px = (int)p.total_px;
@@ -172,12 +179,18 @@ __global__ __launch_bounds__(256, 2) void conv5_mfma_kernel(Conv5K p) {
     const __amdgpu_buffer_rsrc_t rs_b = rsrc_uniform(p.sb ? p.sb : p.sa, p.sb ? p.bytes_b : 0u);
     const __amdgpu_buffer_rsrc_t rs_w = rsrc_uniform(p.w16, p.bytes_w);
     const __amdgpu_buffer_rsrc_t rs_p = rsrc_uniform(HAS_PRM ? (const void*)p.prm : (const void*)p.w16, HAS_PRM ? p.bytes_prm : 0u);
-    const int gq = px0 + 4 * lane;
+    // One DMA instruction fills 1 KiB of a stage = RPI channel rows of the tile: lane -> (row lr of the instruction, 4 pixels).  The
+    // rows of an instruction share a descriptor: with RPI > 1 the concat boundary is a multiple of RPI (conv5_small_shape_ok).
+    constexpr int RPI = 256 / TPX, LPR = 64 / RPI;
+    constexpr int XPW = 4 / RPI;            // activation DMA instructions per wave and chunk
+    constexpr int WPW = WBYTES / 1024 / 4;  // weight pieces per wave and chunk
+    const int lr = lane / LPR;
+    const int gq = px0 + 4 * (lane % LPR);
     const bool q_ok = gq < total_px;
     const int qn = q_ok ? gq / HW : 0;
     const int qp = q_ok ? gq - qn * HW : 0;
-    const unsigned voffA = q_ok ? (unsigned)(((size_t)qn * p.ca * HW + qp) * 4) : kOutOfRange;
-    const unsigned voffB = q_ok ? (unsigned)(((size_t)qn * p.cb * HW + qp) * 4) : kOutOfRange;
+    const unsigned voffA = q_ok ? (unsigned)(((size_t)qn * p.ca * HW + (size_t)lr * HW + qp) * 4) : kOutOfRange;
+    const unsigned voffB = q_ok ? (unsigned)(((size_t)qn * p.cb * HW + (size_t)lr * HW + qp) * 4) : kOutOfRange;
     const unsigned lane16 = (unsigned)lane * 16u;
     // GroupNorm rows of the chunk: lane -> (image n_tile + lane / 16, channel lane % 16)
     const unsigned voffP = (HAS_PRM && n_tile + (lane >> 4) < p.B) ? (unsigned)(((size_t)(n_tile + (lane >> 4)) * C + (lane & 15)) * 16) : kOutOfRange;
@@ -185,18 +198,22 @@ __global__ __launch_bounds__(256, 2) void conv5_mfma_kernel(Conv5K p) {
     auto issue_dma = [&](int chunk, int st) __attribute__((always_inline)) {
         char* stage = smem5 + st * STAGE;
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int cc = wave * 4 + u;
-            const int c = chunk * 16 + cc;
+        for (int u = 0; u < XPW; ++u) {
+            const int cc = wave * XPW + u;
+            const int c = chunk * 16 + cc * RPI;         // first channel row of the instruction
             char* dst = stage + cc * 1024;
-            if (c < p.ca) BLDS6(rs_a, dst, voffA, (unsigned)c * (unsigned)HW * 4u);
-            else BLDS6(rs_b, dst, c < C ? voffB : kOutOfRange, (unsigned)(c - p.ca) * (unsigned)HW * 4u);
+            if (c < p.ca) BLDS6(rs_a, dst, (RPI == 1 || c + lr < p.ca) ? voffA : kOutOfRange, (unsigned)c * (unsigned)HW * 4u);
+            else BLDS6(rs_b, dst, c + lr < C ? voffB : kOutOfRange, (unsigned)(c - p.ca) * (unsigned)HW * 4u);
         }
-        const unsigned wsoff = (unsigned)(chunk * p.n_co_blocks + co_blk) * (unsigned)WBYTES;
+        // the pack holds 128-channel blocks [hi|lo][k-half][128 co][8]: a 64-channel tile takes one half of each of the four planes
+        constexpr int WPLANE = TCO * 16;
+        const unsigned wsoff = TCO == 128 ? (unsigned)(chunk * p.n_co_blocks + co_blk) * 8192u
+                                          : (unsigned)(chunk * p.n_wblocks + (co_blk >> 1)) * 8192u + (unsigned)(co_blk & 1) * (unsigned)WPLANE;
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int piece = wave * 2 + u;
-            BLDS6(rs_w, stage + XBYTES + piece * 1024, lane16 + piece * 1024, wsoff);
+        for (int u = 0; u < WPW; ++u) {
+            const int piece = wave * WPW + u;
+            const int pb = piece * 1024;
+            BLDS6(rs_w, stage + XBYTES + pb, lane16 + (pb / WPLANE) * 2048 + pb % WPLANE, wsoff);
         }
         if (prm_wave) BLDS6(rs_p, stage + XBYTES + WBYTES, voffP, (unsigned)chunk * 256u);
     };
@@ -206,7 +223,7 @@ __global__ __launch_bounds__(256, 2) void conv5_mfma_kernel(Conv5K p) {
     size_t eoff[WPX];                      // EMIT: entry index of (image, k-group 0, pixel) in the planes
 #pragma unroll
     for (int j = 0; j < WPX; ++j) {
-        pxl[j] = wave * 64 + j * 32 + l31;
+        pxl[j] = wave * (32 * WPX) + j * 32 + l31;
         const int g = px0 + pxl[j];
         const int pn = g < total_px ? g / HW : n_tile;
         pimg[j] = pn - n_tile;             // 0 .. 3: image slot of the staged GroupNorm rows
@@ -228,26 +245,30 @@ __global__ __launch_bounds__(256, 2) void conv5_mfma_kernel(Conv5K p) {
         silu = __builtin_amdgcn_readfirstlane(p.eprm[0].w != 0.f ? 1 : 0) != 0;
     }
     if (HAS_PRM) silu = __builtin_amdgcn_readfirstlane(p.prm[0].w != 0.f ? 1 : 0) != 0;
-    if (tid < 128) bias_sh[tid] = co_blk * 128 + tid < p.Cout ? p.bias[co_blk * 128 + tid] : 0.f;
+    if (tid < TCO) bias_sh[tid] = co_blk * TCO + tid < p.Cout ? p.bias[co_blk * TCO + tid] : 0.f;
     __builtin_amdgcn_sched_barrier(0);
     issue_dma(0, 0);
     if (p.n_chunks > 1) issue_dma(1, 1);
+    if (NST > 3 && p.n_chunks > 2) issue_dma(2, 2);
     int st = 0;                              // ring stage of the current chunk
     for (int chunk = 0; chunk < p.n_chunks; ++chunk) {
         // ---- this wave's pieces of the current chunk have landed.  Vector-memory operations complete in issue order and, counted
         // back from here, the wave has issued: [plane stores of chunk-1] <- [DMA of chunk+1] <- [plane stores of chunk-2] <- [DMA of chunk]
+        // (four stages: the DMAs of chunk+1 and chunk+2 may still be in flight)
+        constexpr int NDMA = XPW + WPW;          // DMA instructions per wave and chunk (one more in the wave that fetches the GroupNorm rows)
         __builtin_amdgcn_sched_barrier(0);
         if (chunk + 1 >= p.n_chunks) wait_vmcnt<0>();
-        else if (emit_wg && chunk > 0) wait_vmcnt<6 + NSTORE>();
-        else if (prm_wave) wait_vmcnt<7>();
-        else wait_vmcnt<6>();
+        else if (NST > 3 && chunk + 2 < p.n_chunks) { if (prm_wave) wait_vmcnt<2 * NDMA + 2>(); else wait_vmcnt<2 * NDMA>(); }
+        else if (emit_wg && chunk > 0) wait_vmcnt<NDMA + NSTORE>();
+        else if (prm_wave) wait_vmcnt<NDMA + 1>();
+        else wait_vmcnt<NDMA>();
         barrier_lds_only();                      // ... and everyone's; every wave is also done reading the stage refilled next
-        if (chunk + 2 < p.n_chunks) issue_dma(chunk + 2, st == 0 ? 2 : st - 1);
+        if (chunk + NST - 1 < p.n_chunks) issue_dma(chunk + NST - 1, st == 0 ? NST - 1 : st - 1);
         __builtin_amdgcn_sched_barrier(0);
 
         const char* stage = smem5 + st * STAGE;
-        bad |= conv5_chunk<HAS_PRM, X1, EMIT>(reinterpret_cast<const float*>(stage) + (8 * half) * 256,
-                                              reinterpret_cast<const half8*>(stage + XBYTES) + half * 128 + l31,
+        bad |= conv5_chunk<HAS_PRM, X1, EMIT, WCO, WPX, TPX>(reinterpret_cast<const float*>(stage) + (8 * half) * TPX,
+                                              reinterpret_cast<const half8*>(stage + XBYTES) + half * TCO + l31,
                                               reinterpret_cast<const float4*>(stage + XBYTES + WBYTES) + 8 * half,
                                               eprm_sh + chunk * 16 + 8 * half, pxl, pimg, silu, emit_wg,
                                               p.ehi, p.elo, eoff, (size_t)chunk * 2 * HW, acc);
@@ -264,15 +285,17 @@ __global__ __launch_bounds__(256, 2) void conv5_mfma_kernel(Conv5K p) {
     // wave-private LDS slab (the operand buffers are free) so that a lane owns 4 consecutive pixels of one channel:
     // 32 float4 stores per wave, each instruction writing four 256-byte runs.
     __syncthreads();                                   // every wave is done reading the operand buffers
-    constexpr int SROW = 68;                           // slab row: 64 pixels + 4 floats of padding (16-byte aligned rows)
+    constexpr int SROW = 32 * WPX + 4;                 // slab row: the wave's pixels + 4 floats of padding (16-byte aligned rows)
     static_assert(4 * 32 * SROW * 4 <= NST * STAGE, "epilogue slabs alias the ring");
+    constexpr int L4 = 8 * WPX;                        // lanes per slab row (4 pixels each)
+    constexpr int NPS = 32 / (64 / L4);                // passes over a 32-channel block
     float* slab = reinterpret_cast<float*>(smem5) + wave * (32 * SROW);
-    const int row_l = lane >> 4, c4 = lane & 15;
-    const int g4 = px0 + wave * 64 + 4 * c4;           // HW % 4 == 0 (conv5_supported): the 4 pixels share an image
+    const int row_l = lane / L4, c4 = lane % L4;
+    const int g4 = px0 + wave * (32 * WPX) + 4 * c4;   // HW % 4 == 0 (conv5_supported): the 4 pixels share an image
     const bool ok4 = g4 < total_px;
     const int n4 = ok4 ? g4 / HW : 0;
     const size_t base4 = (size_t)n4 * p.Cout * HW + (size_t)(g4 - n4 * HW);
-    const int co0 = co_blk * 128;
+    const int co0 = co_blk * TCO;
     const float osc = p.out_scale_dev ? p.out_scale * p.out_scale_dev[0] : p.out_scale;
     // No global load between the stores: a load's `s_waitcnt vmcnt(0)` also waits for every store issued before it (the counter
     // is shared and completes in order), which chained the 32 stores of a wave behind one another's write latency.  The bias comes
@@ -284,18 +307,18 @@ __global__ __launch_bounds__(256, 2) void conv5_mfma_kernel(Conv5K p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 slab[((r & 3) + 8 * (r >> 2) + 4 * half) * SROW + j * 32 + l31] = acc[i][j][r];
-        float4 rr[8];
+        float4 rr[NPS];
         if (p.res) {
 #pragma unroll
-            for (int ps = 0; ps < 8; ++ps) {
-                const int co = co0 + i * 32 + ps * 4 + row_l;
+            for (int ps = 0; ps < NPS; ++ps) {
+                const int co = co0 + i * 32 + ps * (64 / L4) + row_l;
                 rr[ps] = (ok4 && co < p.Cout) ? *reinterpret_cast<const float4*>(p.res + base4 + (size_t)co * HW) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
             wait_vmcnt<0>();             // once per block, so that the compiler does not wait (for the previous store too) before every add
         }
 #pragma unroll
-        for (int ps = 0; ps < 8; ++ps) {
-            const int row = ps * 4 + row_l;
+        for (int ps = 0; ps < NPS; ++ps) {
+            const int row = ps * (64 / L4) + row_l;
             const int co = co0 + i * 32 + row;
             const float4 a4 = *reinterpret_cast<const float4*>(slab + row * SROW + 4 * c4);
             const float bz = bias_sh[i * 32 + row];
@@ -309,29 +332,75 @@ __global__ __launch_bounds__(256, 2) void conv5_mfma_kernel(Conv5K p) {
 #endif
 }
 
+// 128 co x 256 px, three-stage ring
+template <bool HAS_PRM, bool X1, bool EMIT>
+__global__ __launch_bounds__(256, 2) void conv5_mfma_kernel(Conv5K p) { conv5_body<HAS_PRM, X1, EMIT, 4, 2, 3>(p); }
+// 64 co x 128 px, four-stage ring (13 KiB per stage: three workgroups per CU)
+template <bool HAS_PRM, bool X1>
+__global__ __launch_bounds__(256, 2) void conv5_small_mfma_kernel(Conv5K p) { conv5_body<HAS_PRM, X1, false, 2, 1, 4>(p); }
+
+// what both tiles need: float4 stores inside one image, and the GroupNorm rows of a tile staged for at most 4 images (PBYTES)
+static bool conv5_shape_ok(int H, int W, bool has_prm) {
+    if ((H * W) % 4) return false;
+    return !(has_prm && (H * W) % 64);
+}
+
 bool conv5_supported(int B, int Cout, int H, int W, bool has_prm) {
     const long long px = (long long)B * H * W;
-    if ((H * W) % 4) return false;
-    // the GroupNorm rows of a tile are staged for at most 4 images (conv5.hip PBYTES)
-    if (has_prm && (H * W) % 64) return false;
-    // enough workgroups to occupy the chip; smaller problems stay on the split-K fp32 kernel
+    if (!conv5_shape_ok(H, W, has_prm)) return false;
+    // enough workgroups to occupy the chip; smaller problems stay on the small tile or the split-K fp32 kernel
     return ((px + 255) / 256) * ((Cout + 127) / 128) >= 32;
 }
 
+// DPIR_CONV5_SMALL=0: every launch on the 128 x 256 tile (the dispatch before the small tile existed).  DPIR_CONV5_SMALL_BELOW: the
+// small tile is taken when the 128 x 256 tiling gives fewer workgroups than this.
+static bool conv5_small_enabled() {
+    static const bool on = !(getenv("DPIR_CONV5_SMALL") && atoi(getenv("DPIR_CONV5_SMALL")) == 0);
+    return on;
+}
+static long long conv5_small_below() {
+    static const long long v = getenv("DPIR_CONV5_SMALL_BELOW") ? atoll(getenv("DPIR_CONV5_SMALL_BELOW")) : 512;
+    return v;
+}
+// the small tile's DMA instructions cover two channel rows: a virtual concat must not split a pair (4: room for a 64-pixel tile)
+static bool conv5_small_shape_ok(int ca, int cb, int H, int W, bool has_prm) {
+    return conv5_shape_ok(H, W, has_prm) && !(cb > 0 && ca % 4);
+}
+
+bool conv5_small_supported(int B, int ca, int cb, int Cout, int H, int W, bool has_prm) {
+    const long long px = (long long)B * H * W;
+    if (!conv5_small_enabled() || !conv5_small_shape_ok(ca, cb, H, W, has_prm)) return false;
+    if (((px + 255) / 256) * ((Cout + 127) / 128) >= conv5_small_below()) return false;
+    return ((px + 127) / 128) * ((Cout + 63) / 64) >= 32;       // same floor as the large tile: below it the split-K fp32 kernel
+}
+
 Status launch_conv5(hipStream_t s, const Conv5Args& a) {
-    if (!conv5_supported(a.B, a.Cout, a.H, a.W, a.prm != nullptr)) return Status{DPIR_ERR_UNSUPPORTED, "conv5: shape not tiled"};
+    const int ca = a.src.ca, cb = a.src.b ? a.src.cb : 0;
+    const bool has_prm = a.prm != nullptr;
+    // tile: the large one wherever it fills the chip (and for the plane-emitting variant), the small one below that
+    bool small;
+    if (a.force_tile) {                       // tests: the workgroup floors do not apply
+        small = a.force_tile == 2;
+        if (small ? (!conv5_small_shape_ok(ca, cb, a.H, a.W, has_prm) || a.emit_hi) : !conv5_shape_ok(a.H, a.W, has_prm))
+            return Status{DPIR_ERR_UNSUPPORTED, "conv5: shape not tiled"};
+    } else {
+        small = !a.emit_hi && conv5_small_supported(a.B, ca, cb, a.Cout, a.H, a.W, has_prm);
+        if (!small && !conv5_supported(a.B, a.Cout, a.H, a.W, has_prm)) return Status{DPIR_ERR_UNSUPPORTED, "conv5: shape not tiled"};
+    }
+    const int tpx = small ? 128 : 256, tco = small ? 64 : 128;
     Conv5K k;
-    k.sa = a.src.a; k.sb = a.src.b; k.ca = a.src.ca; k.cb = a.src.b ? a.src.cb : 0; k.prm = a.prm;
+    k.sa = a.src.a; k.sb = a.src.b; k.ca = ca; k.cb = cb; k.prm = a.prm;
     k.w16 = reinterpret_cast<const char*>(a.w16); k.bias = a.bias; k.out = a.out; k.res = a.res;
     k.B = a.B; k.Cout = a.Cout; k.HW = a.H * a.W;
     const int C = k.ca + k.cb;
     k.n_chunks = (C + 15) / 16;
-    k.n_co_blocks = (a.Cout + 127) / 128;
+    k.n_co_blocks = (a.Cout + tco - 1) / tco;
+    k.n_wblocks = (a.Cout + 127) / 128;
     k.total_px = (long long)a.B * a.H * a.W;
     if (k.total_px >= (1ll << 31) - 256) return invalid("conv5: more than 2^31 pixels in the batch");
     // buffer descriptors address 32-bit byte offsets
     const unsigned long long ba = (unsigned long long)k.total_px * k.ca * 4, bb = (unsigned long long)k.total_px * k.cb * 4;
-    const unsigned long long bw = (unsigned long long)k.n_chunks * k.n_co_blocks * 8192, bp = (unsigned long long)a.B * C * 16;
+    const unsigned long long bw = (unsigned long long)k.n_chunks * k.n_wblocks * 8192, bp = (unsigned long long)a.B * C * 16;
     if (ba >= (1ull << 32) || bb >= (1ull << 32) || bw >= (1ull << 32))
         return invalid("conv5: an input tensor exceeds the 4 GiB buffer-descriptor range; reduce the batch");
     k.bytes_a = (unsigned)ba; k.bytes_b = (unsigned)bb; k.bytes_w = (unsigned)bw; k.bytes_prm = (unsigned)bp;
@@ -341,7 +410,7 @@ Status launch_conv5(hipStream_t s, const Conv5Args& a) {
     k.range_ctr = a.range_ctr;
     k.eprm = a.emit_prm; k.ehi = reinterpret_cast<_Float16*>(a.emit_hi); k.elo = reinterpret_cast<_Float16*>(a.emit_lo);
     k.eC8 = 2 * k.n_chunks;
-    k.n_tiles = (int)((k.total_px + 255) / 256);
+    k.n_tiles = (int)((k.total_px + tpx - 1) / tpx);
     static const bool pair_env = !(getenv("DPIR_CONV5_PAIR") && atoi(getenv("DPIR_CONV5_PAIR")) == 0);
     k.pair_xcd = pair_env && k.n_co_blocks > 1 ? 1 : 0;
     const unsigned blocks = k.pair_xcd ? (unsigned)((k.n_tiles + 7) / 8 * 8 * k.n_co_blocks) : (unsigned)(k.n_tiles * k.n_co_blocks);
@@ -350,6 +419,12 @@ Status launch_conv5(hipStream_t s, const Conv5Args& a) {
         if ((a.H * a.W) % 256 || C % 16 || C > kConv5EmitMaxC) return invalid("conv5: the plane-emitting variant needs H*W % 256 == 0 and a multiple of 16, at most 384, input channels");
         if (a.x1) hipLaunchKernelGGL((conv5_mfma_kernel<false, true, true>), dim3(blocks), dim3(256), 0, s, k);
         else hipLaunchKernelGGL((conv5_mfma_kernel<false, false, true>), dim3(blocks), dim3(256), 0, s, k);
+    } else if (small) {
+        if (a.x1) {
+            if (a.prm) hipLaunchKernelGGL((conv5_small_mfma_kernel<true, true>), dim3(blocks), dim3(256), 0, s, k);
+            else hipLaunchKernelGGL((conv5_small_mfma_kernel<false, true>), dim3(blocks), dim3(256), 0, s, k);
+        } else if (a.prm) hipLaunchKernelGGL((conv5_small_mfma_kernel<true, false>), dim3(blocks), dim3(256), 0, s, k);
+        else hipLaunchKernelGGL((conv5_small_mfma_kernel<false, false>), dim3(blocks), dim3(256), 0, s, k);
     } else if (a.x1) {
         if (a.prm) hipLaunchKernelGGL((conv5_mfma_kernel<true, true, false>), dim3(blocks), dim3(256), 0, s, k);
         else hipLaunchKernelGGL((conv5_mfma_kernel<false, true, false>), dim3(blocks), dim3(256), 0, s, k);

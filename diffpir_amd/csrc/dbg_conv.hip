@@ -224,6 +224,68 @@ int dpir_debug_conv7_check(dpir_engine* e, int B, int Cin, int Cout, int H, int 
     return DPIR_OK;
 }
 
+// One 1x1 layer on caller-supplied host operands through the forward's own dispatch (Fwd::conv, unet.hip): conv5 on the tile
+// launch_conv5 picks (tile 0) or on a forced tile (1 = 128 x 256, 2 = 64 x 128), the general fp32 kernel where conv5 refuses the shape.
+int dpir_debug_conv5_layer(dpir_engine* e, int B, int ca, int cb, int Cout, int H, int W, int tile, const float* xa, const float* xb,
+                           const float* w, const float* bias, const float* prm, const float* res, float* out, int* path_out) {
+    if (!e || !xa || !w || !bias || !out || !path_out || B <= 0 || ca <= 0 || cb < 0 || (cb > 0 && !xb) || Cout <= 0 || tile < 0 || tile > 2) return DPIR_ERR_INVALID;
+    if (e->precision == 0) return fail(e, invalid("conv5 layer: the engine is in f32 mode"));
+    (void)hipSetDevice(e->device);
+    const int C = ca + cb, HW = H * W;
+    const size_t na = (size_t)B * ca * HW, nb = (size_t)B * cb * HW, no = (size_t)B * Cout * HW;
+    float *dxa = nullptr, *dxb = nullptr, *dbias = nullptr, *dout = nullptr, *dres = nullptr, *dw = nullptr, *partial = nullptr; float4* dprm = nullptr;
+    API_TRY(e, e->ws.getT("c5#xa", na, &dxa));
+    API_TRY(e, e->ws.getT("c5#xb", nb + 1, &dxb));
+    API_TRY(e, e->ws.getT("c5#b", (size_t)round_up(Cout, 64), &dbias));
+    API_TRY(e, e->ws.getT("c5#o", no, &dout));
+    API_TRY(e, e->ws.getT("c5#res", no, &dres));
+    API_TRY(e, e->ws.getT("c5#prm", (size_t)B * C, &dprm));
+    API_HIP(e, hipMemcpy(dxa, xa, na * 4, hipMemcpyHostToDevice));
+    if (cb) API_HIP(e, hipMemcpy(dxb, xb, nb * 4, hipMemcpyHostToDevice));
+    API_HIP(e, hipMemset(dbias, 0, (size_t)round_up(Cout, 64) * 4));
+    API_HIP(e, hipMemcpy(dbias, bias, (size_t)Cout * 4, hipMemcpyHostToDevice));
+    if (prm) API_HIP(e, hipMemcpy(dprm, prm, (size_t)B * C * 16, hipMemcpyHostToDevice));
+    if (res) API_HIP(e, hipMemcpy(dres, res, no * 4, hipMemcpyHostToDevice));
+    API_HIP(e, hipMemset(dout, 0xFF, no * 4));
+    std::vector<uint16_t> w16v;
+    const float w16_scale = pack_weights_f16x3_1x1(w, Cout, C, w16v);
+    void* wp = nullptr;
+    API_TRY(e, e->ws.get("c5#w16", w16v.size() * 2, &wp));
+    API_HIP(e, hipMemcpy(wp, w16v.data(), w16v.size() * 2, hipMemcpyHostToDevice));
+    const bool has_prm = prm != nullptr;
+    const bool use5 = !(has_prm && C % 16) && (tile != 0 || conv5_supported(B, Cout, H, W, has_prm) || conv5_small_supported(B, ca, cb, Cout, H, W, has_prm));
+    Status st;
+    if (use5) {
+        Conv5Args a5;
+        a5.src = CatSrc{dxa, ca, cb ? dxb : nullptr, cb}; a5.prm = has_prm ? dprm : nullptr; a5.w16 = wp; a5.w16_scale = w16_scale;
+        a5.bias = dbias; a5.out = dout; a5.res = res ? dres : nullptr; a5.B = B; a5.Cout = Cout; a5.H = H; a5.W = W;
+        a5.x1 = e->precision == 2; a5.force_tile = tile;
+        *path_out = tile ? tile : (conv5_small_supported(B, ca, cb, Cout, H, W, has_prm) ? 2 : 1);
+        st = launch_conv5(e->stream, a5);
+    } else {
+        // load_conv's packing of the fp32 operand: [CinP][taps][CoutP]
+        const int coutp = round_up(Cout, 64), cinp = round_up(C, 16);
+        std::vector<float> packed((size_t)cinp * coutp, 0.f);
+        for (int co = 0; co < Cout; ++co)
+            for (int ci = 0; ci < C; ++ci) packed[(size_t)ci * coutp + co] = w[(size_t)co * C + ci];
+        API_TRY(e, e->ws.getT("c5#w", packed.size(), &dw));
+        API_HIP(e, hipMemcpy(dw, packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
+        API_TRY(e, e->ws.getT("conv#partial", (size_t)16 * 1024 * 1024, &partial));
+        ConvArgs a;
+        a.src.a = dxa; a.src.ca = ca; a.src.b = cb ? dxb : nullptr; a.src.cb = cb; a.src.Hs = H; a.src.Ws = W; a.src.mode = 0;
+        a.src.prm = has_prm ? dprm : nullptr;
+        a.w = dw; a.bias = dbias; a.out = dout; a.res = res ? dres : nullptr; a.res_mode = 0;
+        a.B = B; a.Cin = C; a.Cout = Cout; a.CoutP = coutp; a.H = H; a.W = W; a.ks = 1;
+        a.partial = partial; a.partial_capacity = (size_t)16 * 1024 * 1024;
+        *path_out = 0;
+        st = launch_conv(e->stream, a);
+    }
+    API_TRY(e, st);
+    API_HIP(e, hipStreamSynchronize(e->stream));
+    API_HIP(e, hipMemcpy(out, dout, no * 4, hipMemcpyDeviceToHost));
+    return DPIR_OK;
+}
+
 int dpir_debug_conv7_emit_supported(dpir_engine* e, int B, int Cout, int H, int W, int* capacity_out) {
     if (!e) return 0;
     (void)hipSetDevice(e->device);

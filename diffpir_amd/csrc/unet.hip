@@ -416,8 +416,9 @@ struct Fwd {
                 const Conv6Emit* emit = nullptr) {
         const bool x1 = e->precision == 2;        // f16x1: single-product mode, hi halves only
         // an unfinished split-K output is finished before anything but the fused prologue reads it (or reuses the slab buffer)
-        const bool use5 = cw.w16 && cw.ks == 1 && mode == 0 && (!res || res_mode == 0) && conv5_supported(B, cw.cout, Ho, Wo, prm != nullptr) &&
-                          !(prm && in.C() % 16);   // no slab buffer
+        const bool use5 = cw.w16 && cw.ks == 1 && mode == 0 && (!res || res_mode == 0) && !(prm && in.C() % 16) &&
+                          (conv5_supported(B, cw.cout, Ho, Wo, prm != nullptr) ||
+                           conv5_small_supported(B, in.ca, in.b ? in.cb : 0, cw.cout, Ho, Wo, prm != nullptr));   // no slab buffer
         if (pending.partial && (is_pending(in.a) || is_pending(in.b) || is_pending(res) || !use5)) DPIR_TRY(resolve());
         // the output layer (128 -> 6): GroupNorm / SiLU / split happen in the convolution's own LDS fill (conv8.hip); grad mode keeps the
         // planes route (the backward pass reads act#s16)

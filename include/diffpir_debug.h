@@ -31,6 +31,13 @@ int dpir_debug_conv7_check(dpir_engine* e, int B, int Cin, int Cout, int H, int 
 /* 1 when a 3x3 launch of this shape may take conv7's fused GroupNorm hop (Conv6Emit), 0 when the dispatch falls back to the unfused path;
  * *capacity_out = resident EMIT workgroups of the device (CUs x occupancy) the waiting-set limit is derived from. */
 int dpir_debug_conv7_emit_supported(dpir_engine* e, int B, int Cout, int H, int W, int* capacity_out);
+/* One 1x1 convolution layer on host operands through the forward's dispatch: out[B][Cout][H][W] = W[Cout][ca+cb] * concat(xa, xb)
+ * (+ bias, + res); prm: optional [B][ca+cb][4] {mean, scale, shift, SiLU flag} GroupNorm prologue; res: optional residual of the output's
+ * shape.  tile 0: launch_conv5's own choice (DPIR_CONV5_SMALL), or the general fp32 kernel where conv5 refuses the shape; 1 / 2: the
+ * 128 x 256 / 64 x 128 conv5 tile whatever the workgroup count.  *path_out = 0 fp32 kernel, 1 / 2 the conv5 tile that ran.  The engine's
+ * precision (f16x3 / f16x1) selects the products. */
+int dpir_debug_conv5_layer(dpir_engine* e, int B, int ca, int cb, int Cout, int H, int W, int tile, const float* xa, const float* xb,
+                           const float* w, const float* bias, const float* prm, const float* res, float* out, int* path_out);
 #ifdef __cplusplus
 }
 #endif
