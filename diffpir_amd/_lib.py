@@ -44,6 +44,15 @@ class LoopDesc(C.Structure):
                 ("noise_rp_dev", C.c_void_p), ("ddim_sample", C.c_int32)]
 
 
+class InpaintRow(C.Structure):
+    """dpir_inpaint_row: one sub-step (i, u) of main_ddpir_inpainting.py's loop (schedule.build_inpaint_rows)."""
+    _fields_ = [("t", C.c_int32), ("last", C.c_int32), ("pos", C.c_int32), ("back", C.c_int32),
+                ("c1", C.c_float), ("c2", C.c_float), ("tau", C.c_float), ("sa_t", C.c_float), ("s1m_t", C.c_float), ("sa_p", C.c_float),
+                ("k1", C.c_float), ("q", C.c_float), ("es", C.c_float), ("k2", C.c_float),
+                ("sae", C.c_float), ("sb", C.c_float), ("sa_n", C.c_float), ("s1m_n", C.c_float),
+                ("mix_next", C.c_int32), ("reserved", C.c_int32)]
+
+
 class DpsCoef(C.Structure):
     _fields_ = [("pc1", C.c_float), ("pc2", C.c_float), ("min_log", C.c_float), ("max_log", C.c_float), ("sa_prev", C.c_float), ("s1m_prev", C.c_float)]
 
@@ -122,6 +131,9 @@ SIGNATURES = {
     "dpir_degrade": (C.c_int, [C.c_void_p, C.POINTER(DegradeDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dpir_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dpir_run_loop": (C.c_int, [C.c_void_p, C.POINTER(LoopDesc), C.POINTER(Step), C.c_int, C.c_void_p, C.c_void_p]),
+    "dpir_inpaint_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(InpaintRow), C.c_int, C.c_float,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "dpir_run_inpaint_loop": (C.c_int, [C.c_void_p, C.POINTER(LoopDesc), C.POINTER(InpaintRow), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dpir_prof_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "dpir_prof_reset": (C.c_int, [C.c_void_p]),
     "dpir_prof_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -4,6 +4,7 @@
 #include "engine.h"
 #include "grad.h"
 #include "blur.h"
+#include "inpaint.h"
 #include <math.h>
 #include <string.h>
 #include <stdlib.h>
@@ -705,8 +706,10 @@ extern "C" {
 
 static int run_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, int n_steps, float* out_f32, uint8_t* out_u8);
 
-int dpir_run_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, int n_steps, float* out_f32, uint8_t* out_u8) {
-    int rc = run_loop_once(e, dd, steps, n_steps, out_f32, out_u8);
+// Runs a whole-loop call and, in the f16 modes with the fused hop on, looks at the guard word afterwards: on a hop time-out the loop is run again
+// on the unfused path.  Shared by dpir_run_loop and dpir_run_inpaint_loop.
+static int run_with_hop_guard(dpir_engine* e, const std::function<int()>& once) {
+    int rc = once();
     static const bool fuse_env_off = getenv("DPIR_FUSE_H1") && atoi(getenv("DPIR_FUSE_H1")) == 0;       // unet.hip: the hop is not used at all
     if (rc != DPIR_OK || !e->range_ctr || e->precision == 0 || e->fuse_h1_off || fuse_env_off || e->grad_enabled) return rc;
     // the fused hop may have run: look at the guard word now (the caller synchronises right after the loop anyway) and, on a time-out,
@@ -715,7 +718,38 @@ int dpir_run_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* ste
     if (int r2 = read_range(e, &n)) return r2;
     e->fwd_since_sync = 0; e->replay_last = nullptr;
     if (!fuse_timeout_latch(e, n)) return DPIR_OK;      // plain range excursions stay in the counter for dpir_sync / dpir_d2h to report
-    return run_loop_once(e, dd, steps, n_steps, out_f32, out_u8);
+    return once();
+}
+
+int dpir_run_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, int n_steps, float* out_f32, uint8_t* out_u8) {
+    return run_with_hop_guard(e, [&] { return run_loop_once(e, dd, steps, n_steps, out_f32, out_u8); });
+}
+
+// The captured-step cache shared by dpir_run_loop and dpir_run_inpaint_loop: the graph for `key` (ws_generation is filled in here), or -- on a
+// miss -- `step` run eagerly once as a warm-up (every workspace buffer exists before capture; it is a real step of the loop, its result is kept:
+// *ran = true), then captured and cached, evicting the least recently used entry but never `keep_a` / `keep_b` (the partner graph of the same loop).
+static int cached_step_graph(dpir_engine* e, dpir_engine::GraphKey key, const std::function<Status()>& step, hipGraphExec_t keep_a, hipGraphExec_t keep_b,
+                             hipGraphExec_t* out, bool* ran) {
+    *ran = false;
+    key.ws_generation = e->ws.generation;
+    for (auto& ge : e->graphs)
+        if (memcmp(&ge.key, &key, sizeof(key)) == 0) { ge.last_use = ++e->graph_clock; *out = ge.exec; return DPIR_OK; }
+    API_TRY(e, step());
+    API_HIP(e, hipStreamSynchronize(e->stream));
+    hipGraphExec_t exec = nullptr;
+    API_TRY(e, capture_graph(e, step, &exec));
+    if (e->graphs.size() >= dpir_engine::kMaxGraphs) {
+        size_t lru = 0;
+        for (size_t q = 1; q < e->graphs.size(); ++q) if (e->graphs[q].last_use < e->graphs[lru].last_use) lru = q;
+        if (e->graphs[lru].exec == keep_a || e->graphs[lru].exec == keep_b) lru = (lru + 1) % e->graphs.size();
+        (void)hipGraphExecDestroy(e->graphs[lru].exec);
+        e->graphs.erase(e->graphs.begin() + lru);
+    }
+    key.ws_generation = e->ws.generation;       // the settled generation: the warm-up may have allocated
+    dpir_engine::GraphEntry ge; ge.key = key; ge.exec = exec; ge.last_use = ++e->graph_clock;
+    e->graphs.push_back(ge);
+    *out = exec; *ran = true;
+    return DPIR_OK;
 }
 
 static int run_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, int n_steps, float* out_f32, uint8_t* out_u8) {
@@ -802,42 +836,15 @@ static int run_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_st
         }
         hipGraphExec_t& g = last ? g_last : g_step;
         if (!g) {
-            auto make_key = [&]() {
-                dpir_engine::GraphKey k{};
-                k.task = d.task; k.B = B; k.H = H; k.W = W; k.sf = d.sf; k.in_iter = d.in_iter; k.generate_mode = d.generate_mode;
-                k.kind = (last ? 1 : 0) | (with_n1 ? 2 : 0) | (d.first_order ? 4 : 0);
-                k.host_n1 = d.noise_n1_dev != nullptr; k.host_n2 = d.noise_n2_dev != nullptr; k.host_rp = d.noise_rp_dev != nullptr;
-                k.has_labels = d.labels_host != nullptr;
-                k.gamma = d.gamma; k.guidance = d.guidance; k.ws_generation = e->ws.generation;
-                return k;
-            };
-            auto find = [&](const dpir_engine::GraphKey& k) -> dpir_engine::GraphEntry* {
-                for (auto& ge : e->graphs) if (memcmp(&ge.key, &k, sizeof(k)) == 0) return &ge;
-                return nullptr;
-            };
-            dpir_engine::GraphEntry* hit = find(make_key());
-            if (!hit) {
-                // warm-up: run this step eagerly once so that every workspace buffer exists before capture
-                // (it is a real step of the loop: its result is kept and the graph is used from the next one)
-                API_TRY(e, loop_step(e, d, b, &prox, last, with_n1));
-                API_HIP(e, hipStreamSynchronize(e->stream));
-                hipGraphExec_t exec = nullptr;
-                API_TRY(e, capture_graph(e, [&] { return loop_step(e, d, b, &prox, last, with_n1); }, &exec));
-                if (e->graphs.size() >= dpir_engine::kMaxGraphs) {        // evict the least recently used graph
-                    size_t lru = 0;
-                    for (size_t q = 1; q < e->graphs.size(); ++q) if (e->graphs[q].last_use < e->graphs[lru].last_use) lru = q;
-                    // never the partner graph of this very loop
-                    if (e->graphs[lru].exec == g_step || e->graphs[lru].exec == g_last) lru = (lru + 1) % e->graphs.size();
-                    (void)hipGraphExecDestroy(e->graphs[lru].exec);
-                    e->graphs.erase(e->graphs.begin() + lru);
-                }
-                dpir_engine::GraphEntry ge; ge.key = make_key(); ge.exec = exec; ge.last_use = ++e->graph_clock;   // key: the settled generation
-                e->graphs.push_back(ge);
-                g = exec;
-                continue;   // this step was executed eagerly
-            }
-            hit->last_use = ++e->graph_clock;
-            g = hit->exec;
+            dpir_engine::GraphKey k{};
+            k.task = d.task; k.B = B; k.H = H; k.W = W; k.sf = d.sf; k.in_iter = d.in_iter; k.generate_mode = d.generate_mode;
+            k.kind = (last ? 1 : 0) | (with_n1 ? 2 : 0) | (d.first_order ? 4 : 0);
+            k.host_n1 = d.noise_n1_dev != nullptr; k.host_n2 = d.noise_n2_dev != nullptr; k.host_rp = d.noise_rp_dev != nullptr;
+            k.has_labels = d.labels_host != nullptr;
+            k.gamma = d.gamma; k.guidance = d.guidance;
+            bool ran = false;
+            if (int rc = cached_step_graph(e, k, [&] { return loop_step(e, d, b, &prox, last, with_n1); }, g_step, g_last, &g, &ran)) return rc;
+            if (ran) continue;   // this step was executed eagerly
         }
         ProfScope ps(&e->prof, PC_LOOP);
         API_HIP(e, hipGraphLaunch(g, e->stream));
@@ -847,6 +854,163 @@ static int run_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_st
         API_TRY(e, launch_finalize(e->stream, b.x, out_f32, out_u8, B, H * W));
     }
     return DPIR_OK;
+}
+
+// ------------------------------------------------------------------------------------------ inpainting with resampling (main_ddpir_inpainting.py)
+static InpaintRowDev row_dev_of(const dpir_inpaint_row& r, int s) {
+    InpaintRowDev o{};
+    o.st = StepDev{r.t, r.last, r.pos, 0, r.c1, r.c2, r.tau, r.sa_t, r.s1m_t, r.sa_p, r.k1, r.q, r.es, r.k2};
+    o.s = s; o.back = r.back; o.mix_next = r.mix_next; o.pad = 0;
+    o.sae = r.sae; o.sb = r.sb; o.sa_n = r.sa_n; o.s1m_n = r.s1m_n;
+    return o;
+}
+
+int dpir_inpaint_step(dpir_engine* e, float* x, const float* eps, int eps_ch, const float* y, const uint8_t* mask, const dpir_inpaint_row* row,
+                      int generate_mode, float guidance, const float* n1, const float* n2, const float* n_back, const float* n_rp_next,
+                      uint64_t seed, int64_t image_offset, int substep, float* x0_out, int B, int H, int W) {
+    if (!e || !x || !eps || !y || !mask || !row) return fail(e, invalid("dpir_inpaint_step: null argument"));
+    API_TRY(e, check_shape("dpir_inpaint_step", B, H, W));
+    if (eps_ch != 3 && eps_ch != 6) return fail(e, invalid("dpir_inpaint_step: eps_channels must be 3 or 6"));
+    if (generate_mode < 0 || generate_mode > 2) return fail(e, invalid("dpir_inpaint_step: generate_mode must be 0 (DiffPIR), 1 (repaint) or 2 (vanilla)"));
+    if (substep < 0) return fail(e, invalid("dpir_inpaint_step: substep must be >= 0"));
+    const bool host = n2 != nullptr;
+    if (!host && (n1 || n_back || n_rp_next)) return fail(e, invalid("dpir_inpaint_step: host noise needs n2 (all four null selects device noise)"));
+    if (host && !row->last) {
+        if (row->es != 0.f && !n1) return fail(e, invalid("dpir_inpaint_step: eta_sigma != 0 needs n1"));
+        if (row->back && !n_back) return fail(e, invalid("dpir_inpaint_step: a set-back row needs n_back"));
+    }
+    if (host && generate_mode == 1 && row->mix_next && !n_rp_next) return fail(e, invalid("dpir_inpaint_step: the repaint mix needs n_repaint_next"));
+    (void)hipSetDevice(e->device);
+    ProfScope ps(&e->prof, PC_ELEM);
+    InpaintStepArgs a{};
+    a.x = x; a.eps = eps; a.eps_ch = eps_ch; a.y = y; a.mask = mask; a.mode = generate_mode; a.guidance = guidance;
+    a.device_noise = host ? 0 : 1; a.n1 = n1; a.n2 = n2; a.nback = n_back; a.nrp_next = n_rp_next;
+    a.seed = seed; a.image_offset = image_offset; a.x0_out = x0_out; a.row = nullptr; a.row_val = row_dev_of(*row, substep); a.lp = nullptr; a.B = B; a.HW = H * W; a.cus = e->cus;
+    API_TRY(e, launch_inpaint_step(e->stream, a));
+    return DPIR_OK;
+}
+
+static int run_inpaint_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_inpaint_row* rows, int n_rows, const float* noise_back,
+                                 float* out_f32, uint8_t* out_u8) {
+    if (!e || !dd || !rows || n_rows <= 0) return fail(e, invalid("dpir_run_inpaint_loop: null argument"));
+    (void)hipSetDevice(e->device);
+    const dpir_loop_desc& d = *dd;
+    if (!e->net.loaded) return fail(e, Status{DPIR_ERR_STATE, "dpir_load_unet has not been called"});
+    API_TRY(e, check_shape("dpir_run_inpaint_loop", d.B, d.H, d.W));
+    if (d.task != DPIR_TASK_INPAINT || d.sf != 1) return fail(e, invalid("dpir_run_inpaint_loop: the standalone inpainting program's loop: task must be inpainting, sf 1"));
+    if (!d.y_dev || !d.mask_dev) return fail(e, invalid("dpir_run_inpaint_loop: y and mask are required"));
+    if (d.generate_mode < 0 || d.generate_mode > 2) return fail(e, invalid("dpir_run_inpaint_loop: generate_mode must be 0 (DiffPIR), 1 (repaint) or 2 (vanilla)"));
+    if (d.first_order) return fail(e, Status{DPIR_ERR_UNSUPPORTED, "sub_1_analytic: false is a TODO in the reference (main_ddpir_inpainting.py:280-283)"});
+    if ((e->net.desc.num_classes > 0) != (d.labels_host != nullptr)) return fail(e, invalid("labels iff class-conditional model"));
+    const int B = d.B, H = d.H, W = d.W;
+    const size_t total = (size_t)B * 3 * H * W;
+    const bool host = d.noise_n2_dev != nullptr;
+    bool with_n1 = false, any_back = false;
+    int n_pos = 0;
+    for (int r = 0; r < n_rows; ++r) {
+        const dpir_inpaint_row& w = rows[r];
+        if (!w.last && w.es != 0.f) with_n1 = true;
+        if (!w.last && w.back) any_back = true;
+        if (r > 0 && rows[r - 1].last && !w.last) return fail(e, invalid("dpir_run_inpaint_loop: a non-final row may not follow a final row"));
+        if (w.pos < 0 || w.pos >= n_rows || (r > 0 && (w.pos < rows[r - 1].pos || w.pos > rows[r - 1].pos + 1)) || (r == 0 && w.pos != 0))
+            return fail(e, invalid("dpir_run_inpaint_loop: pos must start at 0 and grow by 0 or 1 per row"));
+        if ((w.mix_next != 0) != (r + 1 < n_rows)) return fail(e, invalid("dpir_run_inpaint_loop: mix_next must be 1 on every row but the last"));
+        n_pos = w.pos + 1;
+    }
+    if (host) {
+        if (!d.noise_init_dev) return fail(e, invalid("dpir_run_inpaint_loop: host noise needs noise_init_dev"));
+        if (with_n1 && !d.noise_n1_dev) return fail(e, invalid("dpir_run_inpaint_loop: eta != 0 with host noise needs noise_n1_dev"));
+        if (any_back && !noise_back) return fail(e, invalid("dpir_run_inpaint_loop: iter_num_U > 1 with host noise needs noise_back_dev"));
+        if (d.generate_mode == 1 && !d.noise_rp_dev) return fail(e, invalid("dpir_run_inpaint_loop: repaint with host noise needs noise_rp_dev"));
+    } else if (d.noise_init_dev || d.noise_n1_dev || d.noise_rp_dev || noise_back) {
+        return fail(e, invalid("dpir_run_inpaint_loop: host noise needs noise_n2_dev (all null selects device noise)"));
+    }
+    range_clear(e);
+    LoopBufs b{};
+    InpaintRowDev *rows_dev = nullptr, *cur = nullptr;
+    InpaintLoopDev* lp = nullptr;
+    API_TRY(e, e->ws.getT("loop#x", total, &b.x));
+    API_TRY(e, e->ws.getT("loop#out6", (size_t)B * e->net.desc.out_channels * H * W, &b.out6));
+    API_TRY(e, e->ws.getT("loop#n2", total, &b.n2));        // the init draw and the first repaint mix (device noise); the sub-steps draw in place
+    API_TRY(e, e->ws.getT("loop#t", (size_t)B, &b.t_dev));
+    API_TRY(e, e->ws.getT("inpaint#rows", (size_t)n_rows, &rows_dev));
+    API_TRY(e, e->ws.getT("inpaint#cur", (size_t)1, &cur));
+    API_TRY(e, e->ws.getT("inpaint#lp", (size_t)1, &lp));
+    API_TRY(e, upload_ints(e, "loop#y", d.labels_host, B, &b.y_dev));
+    const bool hoist_film = e->net.desc.num_classes == 0;
+    if (hoist_film) API_TRY(e, e->ws.getT("loop#film", (size_t)n_pos * e->net.film_rows, &b.film));
+    {
+        std::vector<InpaintRowDev> hr(n_rows);
+        for (int r = 0; r < n_rows; ++r) hr[r] = row_dev_of(rows[r], r);
+        InpaintLoopDev hl{d.y_dev, d.mask_dev, d.noise_n1_dev, d.noise_n2_dev, noise_back, d.noise_rp_dev, (unsigned long long)d.seed, (long long)d.image_offset};
+        API_HIP(e, hipMemcpyAsync(rows_dev, hr.data(), sizeof(InpaintRowDev) * n_rows, hipMemcpyHostToDevice, e->stream));
+        API_HIP(e, hipMemcpyAsync(lp, &hl, sizeof(hl), hipMemcpyHostToDevice, e->stream));
+        API_HIP(e, hipStreamSynchronize(e->stream));
+    }
+    if (b.film) {   // one FiLM row per visited timestep: the U sub-steps of a timestep share it (row.pos)
+        std::vector<int64_t> ts(n_pos);
+        for (int r = 0; r < n_rows; ++r) ts[rows[r].pos] = rows[r].t;
+        int* ts_dev = nullptr;
+        API_TRY(e, upload_ints(e, "loop#ts", ts.data(), n_pos, &ts_dev));
+        API_TRY(e, unet_film_table(e, ts_dev, n_pos, b.film));
+    }
+    ProxState none{};
+    API_TRY(e, loop_init(e, d, b, &none));                  // x from y's own noise level: sa_start / s1m_start (main_ddpir_inpainting.py:190-193)
+    hipStream_t s = e->stream;
+    if (d.generate_mode == 1) {                             // the first sub-step's mix (:244-246); every later one is applied by the sub-step before it
+        ProfScope ps(&e->prof, PC_ELEM);
+        const float* nr = d.noise_rp_dev;
+        if (!nr) { API_TRY(e, launch_randn(s, b.n2, d.seed, 3, d.image_offset, B, (size_t)3 * H * W)); nr = b.n2; }
+        API_TRY(e, launch_repaint_mix(s, b.x, d.y_dev, d.mask_dev, nr, rows[0].sa_t, rows[0].s1m_t, total));
+    }
+    // one 16-byte access per lane needs every tensor behind lp aligned; the decision is baked into a captured graph, so it is part of its key
+    auto al = [](const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) == 0; };
+    const bool aligned = al(d.y_dev, 15) && al(d.mask_dev, 3) && al(d.noise_n1_dev, 15) && al(d.noise_n2_dev, 15) && al(noise_back, 15) && al(d.noise_rp_dev, 15);
+    InpaintStepArgs a{};
+    a.x = b.x; a.eps = b.out6; a.eps_ch = e->net.desc.out_channels; a.mode = d.generate_mode; a.guidance = d.guidance;
+    a.device_noise = host ? 0 : 1; a.row = cur; a.lp = lp; a.B = B; a.HW = H * W; a.cus = e->cus; a.scalar_only = aligned ? 0 : 1;
+    const StepDev* cur_st = &cur->st;
+    auto data_pass = [&]() -> Status {
+        ProfScope ps(&e->prof, PC_ELEM);
+        return launch_inpaint_step(s, a);
+    };
+    auto sub_step = [&]() -> Status {
+        if (!b.film) hipLaunchKernelGGL(fill_t_kernel, dim3((B + 255) / 256), dim3(256), 0, s, b.t_dev, cur_st, B);
+        DPIR_TRY(unet_forward(e, b.x, b.t_dev, b.y_dev, b.out6, B, H, W, b.film, b.film ? cur_st : nullptr));
+        return data_pass();
+    };
+    hipGraphExec_t g = nullptr;
+    for (int r = 0; r < n_rows; ++r) {
+        const bool last = rows[r].last != 0;
+        const bool dead = last && d.skip_dead_final_eval;
+        if (dead && !(d.generate_mode == 1 && rows[r].mix_next)) continue;
+        API_HIP(e, hipMemcpyAsync(cur, rows_dev + r, sizeof(InpaintRowDev), hipMemcpyDeviceToDevice, s));
+        if (dead) { API_TRY(e, data_pass()); continue; }        // the dead evaluation is skipped, the next row's mix is not: it reaches x_0
+        if (!d.use_graph) { API_TRY(e, sub_step()); continue; }
+        if (!g) {
+            dpir_engine::GraphKey k{};
+            k.task = d.task; k.B = B; k.H = H; k.W = W; k.sf = 1; k.generate_mode = d.generate_mode;
+            k.kind = aligned ? 1 : 0;
+            k.host_n1 = d.noise_n1_dev != nullptr; k.host_n2 = host; k.host_rp = d.noise_rp_dev != nullptr;
+            k.has_labels = d.labels_host != nullptr;
+            k.guidance = d.guidance; k.loop = 1;
+            bool ran = false;
+            if (int rc = cached_step_graph(e, k, sub_step, nullptr, nullptr, &g, &ran)) return rc;
+            if (ran) continue;   // this sub-step was executed eagerly
+        }
+        ProfScope ps(&e->prof, PC_LOOP);
+        API_HIP(e, hipGraphLaunch(g, s));
+    }
+    {
+        ProfScope ps(&e->prof, PC_ELEM);
+        API_TRY(e, launch_finalize(s, b.x, out_f32, out_u8, B, H * W));
+    }
+    return DPIR_OK;
+}
+
+int dpir_run_inpaint_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_inpaint_row* rows, int n_rows, const float* noise_back,
+                          float* out_f32, uint8_t* out_u8) {
+    return run_with_hop_guard(e, [&] { return run_inpaint_loop_once(e, dd, rows, n_rows, noise_back, out_f32, out_u8); });
 }
 
 // ------------------------------------------------------------------------------------------ gradient-mode plugs + DPS loop (8f-4)

@@ -358,7 +358,9 @@ def restore_sharded(engine, cfg, y, k=None, mask=None, labels=None, *, rank: int
                   labels=None if labels is None else np.asarray(labels)[sl], seed=seed, image_offset=image_offset + lo,
                   use_graph=use_graph, out_u8=out_u8, _cache=cache, skip_dead_final_eval=skip_dead_final_eval)
         if noise_source == "host":
-            drawn = [None if a is None else (np.ascontiguousarray(a[sl]) if a.ndim == 4 else np.ascontiguousarray(a[:, sl])) for a in host_noise]
+            cut = lambda a: None if a is None else (np.ascontiguousarray(a[sl]) if a.ndim == 4 else np.ascontiguousarray(a[:, sl]))     # noqa: E731
+            # driver main_ddpir_inpainting: the dict of restore.draw_inpaint_host_noise for the global batch
+            drawn = {k_: cut(a) for k_, a in host_noise.items()} if isinstance(host_noise, dict) else [cut(a) for a in host_noise]
             out_f32 = restore.restore_batch(engine, cfg, np.ascontiguousarray(y[sl]), noise_source="host", predrawn=drawn, **kw)
         else:
             out_f32 = restore.restore_batch(engine, cfg, np.ascontiguousarray(y[sl]), noise_source="device", **kw)

@@ -285,6 +285,13 @@ def main(argv=None):
                     _, steps, _ = restore._steps(cfg)
                     for shp in restore.dps_host_noise_shapes(cfg, steps, 0, H, W):
                         dps_nf(shp)
+            elif noise == "host" and cfg.driver == "main_ddpir_inpainting":
+                # driver: main_ddpir_inpainting -- the standalone program's per-image draw order (restore.inpaint_host_noise_shapes); every rank
+                # draws the global batch and keeps its images
+                _, rows, _ = restore._inpaint_rows(cfg)
+                nf = lambda shape: torch.randn(tuple(shape), generator=host_gen).numpy()
+                full = restore.draw_inpaint_host_noise(nf, cfg, rows, n_b, H, W)
+                drawn = {k_: None if a is None else np.ascontiguousarray(a[lo:hi] if a.ndim == 4 else a[:, lo:hi]) for k_, a in full.items()}
             elif noise == "host":
                 # EVERY rank draws the global batch's noise, also a rank whose shard is empty (ragged last batch with fewer images
                 # than ranks): the shared generator must advance identically everywhere or later batches depend on the world size

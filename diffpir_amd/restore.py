@@ -55,7 +55,8 @@ class LoopConfig:
     skip_noise_model_t: bool = False    # main_ddpir.py:192-195, 391
     # which reference program's semantics the loop follows: "main_ddpir" (every task; refuses the gradient modes for deblurring, as that
     # program does) or "main_ddpir_deblur" (the standalone deblurring program: the reflect-padded blur operator in DPS_y0 / DPS_yt / the
-    # first-order data step, its t_y initialisation of x in every mode, one image's own residual norm)
+    # first-order data step, its t_y initialisation of x in every mode, one image's own residual norm) or "main_ddpir_inpainting" (the
+    # standalone inpainting program: the same t_y initialisation and the resampling of iter_num_U sub-steps per timestep)
     driver: str = "main_ddpir"
 
     @property
@@ -81,6 +82,24 @@ class LoopConfig:
                 raise NotImplementedError("driver='main_ddpir_deblur' runs generate_mode DiffPIR (sub_1_analytic true or false), DPS_y0 and DPS_yt with "
                                           "model_output_type=pred_xstart, iter_num_U=1")
             return
+        if self.driver == "main_ddpir_inpainting":
+            if self.task != "inpaint":
+                raise ValueError("driver='main_ddpir_inpainting' is the standalone inpainting program: task must be 'inpaint'")
+            if not self.sub_1_analytic:
+                raise NotImplementedError("sub_1_analytic=false is a `pass` under a TODO in main_ddpir_inpainting.py:280-283")
+            if self.generate_mode not in ("DiffPIR", "repaint", "vanilla") or self.model_output_type != "pred_xstart":
+                raise NotImplementedError("driver='main_ddpir_inpainting' runs generate_mode DiffPIR / repaint / vanilla with "
+                                          "model_output_type=pred_xstart (pred_x_prev is not on the accelerated path), any iter_num_U >= 1")
+            if int(self.iter_num_U) < 1:
+                raise ValueError("iter_num_U must be >= 1")
+            # skip_noise_model_t has nothing to select here: the program pins noise_model_t = 0 (main_ddpir_inpainting.py:89), so the test at :266 holds on
+            # every step and the key is ignored, true or false
+            from .schedule import make_seq
+            n = len(make_seq(self.num_train_timesteps, self.iter_num, self.skip_type))
+            if n < 10:
+                raise ValueError(f"main_ddpir_inpainting.py:227 `progress_seq = seq[::(len(seq)//10)]` raises for a schedule of {n} entries "
+                                 "(fewer than 10): there is no behaviour to mirror")
+            return
         # ddim_sample is accepted: with model_output_type=pred_xstart it selects the same x0 prediction and the same number
         # of RNG draws as p_sample (utils_model.py:219-240; tests/golden/model_fn.npz).  iter_num_U > 1 cannot be mirrored:
         # the reference raises IndexError on `seq[i+1]` at its last step (main_ddpir.py:448-451 with u < iter_num_U-1).
@@ -102,7 +121,7 @@ class LoopConfig:
             raise NotImplementedError("generate_mode repaint / vanilla are inpainting modes in the reference")
 
 
-DRIVERS = ("main_ddpir", "main_ddpir_deblur")
+DRIVERS = ("main_ddpir", "main_ddpir_deblur", "main_ddpir_inpainting")
 GENERATE_MODES = {"DiffPIR": 0, "repaint": 1, "vanilla": 2, "DPS_y0": 3, "DPS_yt": 4}
 
 
@@ -115,10 +134,10 @@ def t_start_of(cfg: LoopConfig, reduced) -> int:
 
 def start_coefficients(cfg: LoopConfig, dt):
     """(sa, s1m) of the initial x = sa (2y - 1) + s1m randn_like(y), float32.  main_ddpir.py:315 places y at t_start as if it were clean;
-    main_ddpir_deblur.py:228-231 noises it from its own level t_y up to t_start, on the driver's float32 tables."""
+    main_ddpir_deblur.py:228-231 and main_ddpir_inpainting.py:190-193 noise it from its own level t_y up to t_start, on the driver's float32 tables."""
     t_start = t_start_of(cfg, dt.reduced)
     sa, s1m = np.float32(dt.sqrt_ac[t_start]), np.float32(dt.sqrt_1m_ac[t_start])
-    if cfg.driver != "main_ddpir_deblur":
+    if cfg.driver not in ("main_ddpir_deblur", "main_ddpir_inpainting"):
         return sa, s1m
     t_y = find_nearest(dt.reduced, 2 * cfg.noise_level_img)
     eff = np.float32(sa / np.float32(dt.sqrt_ac[t_y]))
@@ -175,6 +194,9 @@ def restore_batch(engine: Engine, cfg: LoopConfig, y, k=None, mask=None, labels=
     Returns a DeviceArray [B,3,H,W] = x_0 in [0,1] (un-clamped, main_ddpir.py:470), and the u8 NHWC
     array as well when return_u8."""
     cfg.check_supported()
+    if cfg.driver == "main_ddpir_inpainting":
+        return _restore_inpaint_resample(engine, cfg, y, mask, labels, noise_source, noise_fn, seed, image_offset, use_graph, skip_dead_final_eval,
+                                         out_f32, out_u8, return_u8, _cache, predrawn)
     if cfg.driver == "main_ddpir_deblur" and (cfg.generate_mode != "DiffPIR" or not cfg.sub_1_analytic):
         if predrawn is not None or mask is not None or use_graph:
             raise NotImplementedError("the deblurring program's gradient modes take host noise through noise_fn, no mask and no step graph")
@@ -259,6 +281,105 @@ def dps_host_noise_shapes(cfg: LoopConfig, steps, B: int, H: int, W: int):
         if cfg.driver == "main_ddpir_deblur" and cfg.generate_mode == "DiffPIR" and not st["last"]:
             shapes += [(B, 3, H, W)] * 2          # the re-noise's two draws (main_ddpir_deblur.py:346-347), analytic and first-order alike
     return shapes
+
+
+def _inpaint_rows(cfg: LoopConfig):
+    from .schedule import DriverTables, build_inpaint_rows
+    t_start = None
+    if cfg.noise_init_img != "max":
+        t_start = t_start_of(cfg, DriverTables.make(cfg.beta_start, cfg.beta_end, cfg.num_train_timesteps).reduced)
+    return build_inpaint_rows(iter_num=cfg.iter_num, iter_num_U=int(cfg.iter_num_U), sigma=cfg.sigma, lambda_=cfg.lambda_, zeta=cfg.zeta, eta=cfg.eta,
+                              skip_type=cfg.skip_type, T=cfg.num_train_timesteps, beta_start=cfg.beta_start, beta_end=cfg.beta_end, t_start=t_start)
+
+
+def inpaint_host_noise_shapes(cfg: LoopConfig, rows, B: int, H: int, W: int):
+    """Shapes of the standalone inpainting program's randn_like draws, in call order.  The program restores one image at a time, so every draw
+    is (1,3,H,W) and the whole sequence repeats per image: init (main_ddpir_inpainting.py:193), then per sub-step [the repaint mix, :245],
+    p_sample's unused draw (gaussian_diffusion.py:430) and, on non-final steps, the eta and zeta draws (:293, both always drawn) and the
+    set-back draw where u < iter_num_U - 1 (:300)."""
+    one = (1, 3, H, W)
+    per = [one]
+    for r in rows:
+        per += [one] * ((cfg.generate_mode == "repaint") + 1 + (0 if r["last"] else 2 + r["back"]))
+    return per * B
+
+
+def draw_inpaint_host_noise(noise_fn: Callable, cfg: LoopConfig, rows, B: int, H: int, W: int):
+    """Consume noise_fn in the order of inpaint_host_noise_shapes and keep what the loop uses, batch-shaped:
+    dict(init [B,3,H,W]; n1 (eta != 0) / n2 / back (iter_num_U > 1) / rp (repaint) [n_rows,B,3,H,W], or None)."""
+    rp, n = cfg.generate_mode == "repaint", len(rows)
+    full = (n, B, 3, H, W)
+    out = dict(init=np.empty((B, 3, H, W), np.float32), n1=np.zeros(full, np.float32) if cfg.eta != 0 else None, n2=np.zeros(full, np.float32),
+               back=np.zeros(full, np.float32) if any(r["back"] for r in rows) else None, rp=np.zeros(full, np.float32) if rp else None)
+    one = (1, 3, H, W)
+    for b in range(B):
+        out["init"][b] = np.asarray(noise_fn(one), np.float32)[0]
+        for s, r in enumerate(rows):
+            if rp:
+                out["rp"][s, b] = np.asarray(noise_fn(one), np.float32)[0]
+            noise_fn(one)                                   # p_sample's randn_like, unused
+            if r["last"]:
+                continue
+            a = np.asarray(noise_fn(one), np.float32)[0]
+            if out["n1"] is not None:
+                out["n1"][s, b] = a
+            out["n2"][s, b] = np.asarray(noise_fn(one), np.float32)[0]
+            if r["back"]:
+                out["back"][s, b] = np.asarray(noise_fn(one), np.float32)[0]
+    return out
+
+
+def _restore_inpaint_resample(engine, cfg, y, mask, labels, noise_source, noise_fn, seed, image_offset, use_graph, skip_dead_final_eval,
+                              out_f32, out_u8, return_u8, _cache, predrawn, _start=None):
+    """driver 'main_ddpir_inpainting' (main_ddpir_inpainting.py:190-303): dpir_run_inpaint_loop, one fused data pass per sub-step.
+    predrawn: the dict of draw_inpaint_host_noise (sharded runs).  _start: (sa, s1m) instead of the t_y initialisation (tests)."""
+    if mask is None:
+        raise EngineError("inpainting needs a mask")
+    dt, rows, arr = _inpaint_rows(cfg)
+    keep = []
+
+    def dev(a, dtype=np.float32):
+        if a is None:
+            return None
+        if isinstance(a, np.ndarray):
+            a = engine.to_device(a, dtype)
+        keep.append(a)
+        return a
+    y, mask = dev(y), dev(mask, np.uint8)
+    B, _, H, W = y.shape
+    d = _lib.LoopDesc()
+    d.task, d.B, d.H, d.W, d.sf = TASKS["inpaint"], B, H, W, 1
+    d.guidance = cfg.guidance_scale
+    d.sa_start, d.s1m_start = [float(v) for v in (start_coefficients(cfg, dt) if _start is None else _start)]
+    d.y_dev, d.mask_dev = _ptr(y), _ptr(mask)
+    lab = None
+    if labels is not None:
+        lab = np.ascontiguousarray(labels, dtype=np.int64)
+        d.labels_host = lab.ctypes.data
+    nback = None
+    if noise_source == "host":
+        if predrawn is None:
+            if noise_fn is None:
+                raise EngineError("noise_source='host' needs noise_fn")
+            predrawn = draw_inpaint_host_noise(noise_fn, cfg, rows, B, H, W)
+        dn = {k_: dev(v) for k_, v in predrawn.items()}
+        d.noise_init_dev, d.noise_n1_dev, d.noise_n2_dev, d.noise_rp_dev = _ptr(dn["init"]), _ptr(dn["n1"]), _ptr(dn["n2"]), _ptr(dn["rp"])
+        nback = dn["back"]
+    elif noise_source != "device":
+        raise ValueError("noise_source must be 'host' or 'device'")
+    d.seed, d.image_offset = seed, image_offset
+    d.use_graph, d.skip_dead_final_eval = int(use_graph), int(skip_dead_final_eval)
+    d.generate_mode = GENERATE_MODES[cfg.generate_mode]
+    if out_f32 is None:
+        out_f32 = engine.empty((B, 3, H, W))
+    if out_u8 is None and return_u8:
+        out_u8 = engine.empty((B, H, W, 3), np.uint8)
+    engine._check(engine.lib.dpir_run_inpaint_loop(engine.h, C.byref(d), arr, len(rows), _ptr(nback), _ptr(out_f32), _ptr(out_u8)))
+    if _cache is not None:
+        _cache["keep"] = keep
+    else:
+        engine.sync()
+    return (out_f32, out_u8) if return_u8 else out_f32
 
 
 def _restore_deblur_grad(engine, cfg, y, k, labels, noise_source, noise_fn, seed, image_offset, skip_dead_final_eval, out_f32, out_u8, return_u8):
@@ -397,6 +518,8 @@ def restore_batch_stepwise(model, diffusion, cfg: LoopConfig, y, k=None, mask=No
     from .utils_resizer import Resizer
     eng: Engine = model.engine
     cfg.check_supported()
+    if cfg.driver == "main_ddpir_inpainting":
+        return _stepwise_inpaint_resample(model, diffusion, cfg, y, mask, noise_fn, labels)
     dt, steps, arr = _steps(cfg)
     B, _, h, w = y.shape
     H, W = h * cfg.sf, w * cfg.sf
@@ -487,6 +610,49 @@ def restore_batch_stepwise(model, diffusion, cfg: LoopConfig, y, k=None, mask=No
             eng._check(lib.dpir_renoise(hnd, x.ptr, x0.ptr, C.byref(arr[i]), n1.ptr, n2.ptr, B, H, W))
     finally:
         utils_model.set_randn_like(None)
+    out = eng.empty(shape)
+    eng._check(lib.dpir_finalize(hnd, x.ptr, out.ptr, None, B, H, W))
+    eng.sync()
+    return out
+
+
+def _stepwise_inpaint_resample(model, diffusion, cfg: LoopConfig, y, mask, noise_fn, labels):
+    """main_ddpir_inpainting.py:190-303 over the drop-in plugs, one launch per expression: the unfused statement of dpir_run_inpaint_loop.
+    Host noise is taken through draw_inpaint_host_noise (the program's per-image draw order)."""
+    from . import utils_model
+    eng: Engine = model.engine
+    dt, rows, arr = _inpaint_rows(cfg)
+    B, _, H, W = y.shape
+    shape, numel = (B, 3, H, W), B * 3 * H * W
+    lib, hnd = eng.lib, eng.h
+    nz = draw_inpaint_host_noise(noise_fn, cfg, rows, B, H, W)
+    sa0, s1m0 = start_coefficients(cfg, dt)                     # :190-193
+    x = eng.empty(shape)
+    xs = y.numpy() * mask.numpy().astype(np.float32)            # y arrives masked: the identity (what init_x_kernel does)
+    x.copy_from(sa0 * (np.float32(2) * xs - np.float32(1)) + s1m0 * nz["init"])
+    kwargs = {} if labels is None else {"y": labels}
+    steps = (_lib.Step * len(rows))()
+    for s, r in enumerate(rows):
+        for f, _ in _lib.Step._fields_:
+            setattr(steps[s], f, r[f])
+    for s, r in enumerate(rows):
+        if cfg.generate_mode == "repaint":                  # :244-246
+            nr = eng.to_device(nz["rp"][s])
+            eng._check(lib.dpir_repaint_mix(hnd, x.ptr, _ptr(y), _ptr(mask), C.byref(steps[s]), nr.ptr, B, H, W))
+        x0 = utils_model.model_fn(x, noise_level=dt.reduced[r["t"]] * 255, model_out_type="pred_xstart", model_diffusion=model,
+                                  diffusion=diffusion, ddim_sample=cfg.ddim_sample, alphas_cumprod=dt.alphas_cumprod, **kwargs)
+        if r["last"]:
+            continue
+        if cfg.generate_mode == "DiffPIR":                  # :267-268
+            eng._check(lib.dpir_prox_mask(hnd, x0.ptr, _ptr(y), _ptr(mask), float(np.float32(r["tau"])), cfg.guidance_scale, B, H, W))
+        n1 = None if nz["n1"] is None else eng.to_device(nz["n1"][s])
+        n2 = eng.to_device(nz["n2"][s])
+        eng._check(lib.dpir_renoise(hnd, x.ptr, x0.ptr, C.byref(steps[s]), _ptr(n1), n2.ptr, B, H, W))       # :288-293
+        if r["back"]:                                       # :296-300
+            nb = eng.to_device(nz["back"][s])
+            eng._check(lib.dpir_ewise(hnd, 2, x.ptr, None, 0, float(np.float32(r["sae"])), x.ptr, numel))
+            eng._check(lib.dpir_ewise(hnd, 2, nb.ptr, None, 0, float(np.float32(r["sb"])), nb.ptr, numel))
+            eng._check(lib.dpir_ewise(hnd, 0, x.ptr, nb.ptr, numel, 0.0, x.ptr, numel))
     out = eng.empty(shape)
     eng._check(lib.dpir_finalize(hnd, x.ptr, out.ptr, None, B, H, W))
     eng.sync()

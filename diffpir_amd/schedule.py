@@ -151,3 +151,56 @@ def build_steps(*, iter_num: int, sigma: float, lambda_: float, zeta: float, eta
         for f, _ in _lib.Step._fields_:
             setattr(arr[i], f, st[f])
     return dt, steps, arr
+
+
+def build_inpaint_rows(*, iter_num: int, iter_num_U: int, sigma: float, lambda_: float, zeta: float, eta: float = 0.0,
+                       skip_type: str = "quad", T: int = 1000, beta_start=0.0001, beta_end=0.02, t_start: int = None):
+    """One row per sub-step (i, u) of the standalone inpainting program (main_ddpir_inpainting.py:200-300), model_out_type pred_xstart:
+    returns (DriverTables, list of python dicts, ctypes InpaintRow array).  Every coefficient is formed with 0-dim float32 torch tensors in
+    that program's operation order; rhos come from sigma_ks = s1m / sa in every generate_mode (:205-209 branch on model_out_type only).
+    A row carries the set-back pair (sae, sb) of :298-300 with its `back` flag (u < U - 1) and the next row's (sa, s1m) for the repaint
+    mix the fused pass applies ahead of the next denoiser call."""
+    import torch
+    if iter_num_U < 1:
+        raise ValueError("iter_num_U must be >= 1")
+    dt = DriverTables.make(beta_start, beta_end, T)
+    dtab = DiffusionTables.make(T)
+    if t_start is None:
+        t_start = T - 1
+    seq = make_seq(T, iter_num, skip_type)
+    if len(seq) < 10:
+        raise ValueError("main_ddpir_inpainting.py:227 `progress_seq = seq[::(len(seq)//10)]` raises for a schedule of fewer than 10 entries "
+                         f"(got {len(seq)}): there is no behaviour to mirror")
+    t_s1m, t_sa, t_betas = torch.from_numpy(dt.sqrt_1m_ac), torch.from_numpy(dt.sqrt_ac), torch.from_numpy(dt.betas)
+    rhos = (lambda_ * (sigma ** 2) / ((t_s1m / t_sa) ** 2)).float().numpy()          # :206, :209
+    t_list = [find_nearest(dt.reduced, dt.reduced[T - 1 - s]) for s in seq]          # :232-234
+    rows, pos = [], -1
+    for i, t_i in enumerate(t_list):
+        if t_i > t_start:
+            continue                                                                  # :236-237
+        pos += 1
+        last = seq[i] == seq[-1]
+        c1, c2 = dtab.c1c2(t_i)
+        base = dict(t=t_i, last=int(last), pos=pos, back=0, c1=float(c1), c2=float(c2), tau=float(rhos[t_i]), sa_t=float(dt.sqrt_ac[t_i]),
+                    s1m_t=float(dt.sqrt_1m_ac[t_i]), sa_p=0.0, k1=0.0, q=0.0, es=0.0, k2=0.0, sae=0.0, sb=0.0, sa_n=0.0, s1m_n=0.0,
+                    mix_next=0, reserved=0, t_im1=None, u=0)
+        if not last:
+            t_p = t_list[i + 1]
+            s1m_p, s1m_t = t_s1m[t_p], t_s1m[t_i]
+            es = eta * s1m_p / s1m_t * torch.sqrt(t_betas[t_i])                       # :291
+            q = torch.sqrt(s1m_p ** 2 - es ** 2)                                      # :292
+            k2 = np.sqrt(zeta) * s1m_p                                                # :293
+            sae = t_sa[t_i] / t_sa[t_p]                                               # :298
+            arg = s1m_t ** 2 - sae ** 2 * s1m_p ** 2                                  # :299-300
+            assert float(arg) >= 0.0, (t_i, t_p, float(arg))
+            base.update(sa_p=float(dt.sqrt_ac[t_p]), k1=float(np.float32(np.sqrt(1 - zeta))), q=float(q), es=float(es), k2=float(k2),
+                        sae=float(sae), sb=float(torch.sqrt(arg)), sb_arg=float(arg), t_im1=t_p)
+        for u in range(iter_num_U):
+            rows.append(dict(base, u=u, back=int(not last and u < iter_num_U - 1)))
+    for r, nxt in zip(rows[:-1], rows[1:]):
+        r.update(mix_next=1, sa_n=nxt["sa_t"], s1m_n=nxt["s1m_t"])
+    arr = (_lib.InpaintRow * len(rows))()
+    for i, r in enumerate(rows):
+        for f, _ in _lib.InpaintRow._fields_:
+            setattr(arr[i], f, r[f])
+    return dt, rows, arr

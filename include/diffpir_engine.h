@@ -266,6 +266,44 @@ typedef struct dpir_loop_desc {
 int dpir_run_loop(dpir_engine* e, const dpir_loop_desc* d, const dpir_step* steps_host, int n_steps,
                   float* out_f32_dev, uint8_t* out_u8_dev);
 
+/* ---- inpainting with resampling (main_ddpir_inpainting.py:147-317, iter_num_U >= 1) ------- */
+/* One row per sub-step (i, u) of the standalone inpainting program, all computed on the host as that program does
+ * (diffpir_amd/schedule.py build_inpaint_rows).  The first ten scalars are dpir_step's. */
+typedef struct dpir_inpaint_row {
+    int32_t t;            /* t_i: UNet timestep */
+    int32_t last;         /* 1 where seq[i] == seq[-1]: a dead denoiser call, nothing else (:261, :285, :296) */
+    int32_t pos;          /* position of t_i among the visited timesteps: the U sub-steps of one i share it (hoisted FiLM row) */
+    int32_t back;         /* 1: set back to t_i after the re-noise (u < iter_num_U - 1, :296-300) */
+    float c1, c2, tau, sa_t, s1m_t, sa_p, k1, q, es, k2;      /* the scalars of dpir_step, main_ddpir_inpainting.py:267, :288-293 */
+    float sae;            /* sqrt_alphas_cumprod[t_i] / sqrt_alphas_cumprod[t_im1] (:298) */
+    float sb;             /* sqrt(s1m[t_i]^2 - sae^2 * s1m[t_im1]^2) (:299-300); exactly 0 when t_im1 == t_i */
+    float sa_n, s1m_n;    /* sqrt_alphas_cumprod / sqrt_1m_alphas_cumprod at the NEXT row's t_i (repaint mix of the next sub-step, :244-246) */
+    int32_t mix_next;     /* 1: a next row exists (generate_mode repaint applies its mix at the end of this sub-step) */
+    int32_t reserved;
+} dpir_inpaint_row;
+
+/* The data side of one sub-step in one pass, in place on x_dev [B,3,H,W] (main_ddpir_inpainting.py:249-300 behind the network call):
+ *   x0 = clamp(c1 x - c2 eps)  [-> x0_out_dev when given]; generate_mode 0: x0 += guidance ((mask (2y-1) + tau x0)/(mask + tau) - x0);
+ *   x = sa_p x0 + k1 (q (x - sa_t x0)/s1m_t + es n1) + k2 n2; back: x = sae x + sb n_back; generate_mode 1 and mix_next:
+ *   x = (sa_n (2y-1) + s1m_n n_repaint_next) mask + (1 - mask) x.  A row with last = 1 only takes the mix.
+ * eps_dev [B,eps_channels,H,W] (eps_channels 3 or 6: the UNet's output, channels 0..2 used), y_dev in [0,1], mask_dev uint8 {0,1}.
+ * Noise: n2_dev non-NULL -> host-fed tensors [B,3,H,W] (n1 needed when es != 0, n_back when back, n_repaint_next when the mix applies);
+ * n2_dev NULL -> Philox in place, streams 1 + 4s / 2 + 4s / 2^32 + s / 3 + 4(s+1) for sub-step ordinal s = `substep`, keyed by (seed, image_offset + b)
+ * exactly as dpir_randn would produce them.  Bit-identical to dpir_prox_mask -> dpir_renoise -> dpir_ewise -> dpir_repaint_mix.
+ * Asynchronous on the engine stream like its siblings: the row travels by value in the kernel arguments (no copy, no synchronisation). */
+int dpir_inpaint_step(dpir_engine* e, float* x_dev, const float* eps_dev, int eps_channels, const float* y_dev, const uint8_t* mask_dev,
+                      const dpir_inpaint_row* row, int generate_mode, float guidance, const float* n1_dev, const float* n2_dev,
+                      const float* n_back_dev, const float* n_repaint_next_dev, uint64_t seed, int64_t image_offset, int substep,
+                      float* x0_out_dev, int B, int H, int W);
+
+/* Runs init -> n_rows x (UNet -> dpir_inpaint_step) -> finalize: the standalone inpainting program's loop for one batch, one captured graph
+ * for every sub-step (use_graph).  d as in dpir_run_loop with task DPIR_TASK_INPAINT and sa_start / s1m_start from the t_y initialisation
+ * (:190-193); d->generate_mode 0 / 1 / 2.  Host-fed noise (parity mode; all four NULL -> device Philox): d->noise_init_dev [B,3,H,W], and
+ * [n_rows,B,3,H,W] in sub-step order for d->noise_n1_dev (eta != 0), d->noise_n2_dev, noise_back_dev (some row has back) and
+ * d->noise_rp_dev (repaint).  Synchronisation and the fused-hop guard: as dpir_run_loop. */
+int dpir_run_inpaint_loop(dpir_engine* e, const dpir_loop_desc* d, const dpir_inpaint_row* rows_host, int n_rows, const float* noise_back_dev,
+                          float* out_f32_dev, uint8_t* out_u8_dev);
+
 /* ---- gradient-based sampling (generate_mode 'DPS_y0') ---------------------- */
 /* Replaces what torch.autograd does for the reference's DPS branch (main_ddpir.py:370-373, 434-438 with
  * utils_model.grad_and_value, utils/utils_model.py:390-394).  Gradient mode must be switched on BEFORE dpir_load_unet: it builds
