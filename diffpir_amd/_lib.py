@@ -67,6 +67,15 @@ class DegradeDesc(C.Structure):
                 ("kh", C.c_int32), ("kw", C.c_int32), ("noise_level_img", C.c_float), ("seed", C.c_uint64), ("image_offset", C.c_int64)]
 
 
+class Conv3Desc(C.Structure):
+    """dpir_debug_conv3_desc (include/diffpir_debug.h): one 3x3 layer for dpir_debug_conv3_layer."""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "ca", "cb", "Cout", "H", "W", "mode", "res_mode", "scaled", "prologue", "route", "split",
+                                          "defer", "Cout2")] +
+                [(n, C.c_void_p) for n in ("xa", "xb", "w", "bias", "res", "prm", "gamma", "beta", "film", "gamma2", "beta2", "w2", "bias2",
+                                           "out", "stat_out", "out2")] +
+                [(n, C.c_int32) for n in ("stat_kind_out", "path_out", "ksplit_out", "reserved")])
+
+
 PROF_CLASSES = 8
 PROF_NAMES = ["conv3x3", "conv1x1", "groupnorm_stats", "attention", "fft_prox", "elementwise", "unet_forward", "loop_graph"]
 
@@ -173,6 +182,8 @@ def load_debug():
                                                                         C.POINTER(C.c_float), C.POINTER(C.c_int)]
     d.dpir_debug_conv5_layer.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 7 + [C.POINTER(C.c_int)]
     d.dpir_debug_conv5_layer.restype = C.c_int
+    d.dpir_debug_conv3_layer.argtypes = [C.c_void_p, C.POINTER(Conv3Desc)]
+    d.dpir_debug_conv3_layer.restype = C.c_int
     for n in ("dpir_debug_conv_bench", "dpir_debug_victim", "dpir_debug_victim_alu", "dpir_debug_victim_fft_pk", "dpir_debug_victim_fft_nopk",
               "dpir_debug_conv7_check"):
         getattr(d, n).restype = C.c_int

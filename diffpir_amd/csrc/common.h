@@ -168,7 +168,8 @@ struct Conv6Args {
     float2* stat = nullptr;        // optional [B][Cout][conv6_stat_slots(H, W)] epilogue partial sums (no split-K)
     double2* stat_plane = nullptr; // optional [B][Cout] fp64 {sum, sum of squares}, written by the split-K combine
     bool x1 = false;               // single-product mode (f16x1): hi planes / hi weight halves only
-    const float* out_scale_dev = nullptr;      // optional device scalar folded into the output scale (dgrad, unet_bwd.hip)
+    // optional device scalar folded into the output scale (dgrad, unet_bwd.hip): it multiplies the convolution sum; bias and res are added unscaled
+    const float* out_scale_dev = nullptr;
     int force_kernel = 0;          // tests only: 6 = conv6 even where conv7 applies, 7 = conv7 or an error; 0 = launch_conv6 decides
     const struct Conv6Emit* emit = nullptr;    // conv6_params.h: fused emission of the NEXT convolution's operand planes instead of `out`
 };
@@ -177,8 +178,9 @@ bool conv7_emit_supported(int B, int Cout, int H, int W);
 bool conv6_supported(int H, int W);
 int conv6_stat_slots(int H, int W);
 // pend_out != null: a split-K launch leaves its slabs uncombined and describes them in *pend_out (stat kind 3); the caller must
-// have them finished (gn_act_small or launch_conv6_resolve) before the slab buffer is reused
-Status launch_conv6(hipStream_t s, const Conv6Args& a, int* stat_kind_out = nullptr, PendingConv* pend_out = nullptr);
+// have them finished (gn_act_small or launch_conv6_resolve) before the slab buffer is reused.  kernel_out (tests): 6 / 7 = the kernel
+// that ran
+Status launch_conv6(hipStream_t s, const Conv6Args& a, int* stat_kind_out = nullptr, PendingConv* pend_out = nullptr, int* kernel_out = nullptr);
 Status launch_conv6_resolve(hipStream_t s, const PendingConv& p);
 float pack_weights_conv6(const float* w_oihw, int cout, int cin, std::vector<uint16_t>& out);
 // conv5.hip: 1x1 convolution, f16x3 with the operand split done in-kernel from the fp32 NCHW (virtual concat) input
@@ -192,7 +194,7 @@ struct Conv5Args {
     // optional second product: the split operand planes of the following 3x3 convolution, silu(GroupNorm(src)) per emit_prm,
     // blocked [B][2*ceil(C/16)][HW][8] f16 (act.hip's layout); requires prm == null (the 1x1 itself multiplies the raw input)
     const float4* emit_prm = nullptr; void* emit_hi = nullptr; void* emit_lo = nullptr;
-    const float* out_scale_dev = nullptr;      // optional device scalar folded into the output scale (dgrad)
+    const float* out_scale_dev = nullptr;      // optional device scalar folded into the output scale (dgrad); bias and res are added unscaled
     int force_tile = 0;                        // tests only: 1 = the 128 x 256 tile, 2 = the 64 x 128 tile, whatever the workgroup count; 0 = launch_conv5 decides
 };
 constexpr int kConv5EmitMaxC = 384;            // channels of the GroupNorm table the plane-emitting variant stages in LDS

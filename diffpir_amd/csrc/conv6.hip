@@ -566,7 +566,7 @@ Status launch_conv6_resolve(hipStream_t s, const PendingConv& p) {
     return Status{};
 }
 
-Status launch_conv6(hipStream_t s, const Conv6Args& a, int* stat_kind_out, PendingConv* pend_out) {
+Status launch_conv6(hipStream_t s, const Conv6Args& a, int* stat_kind_out, PendingConv* pend_out, int* kernel_out) {
     if (stat_kind_out) *stat_kind_out = 0;
     if (pend_out) *pend_out = PendingConv{};
     const int geo = conv6_geo(a.H, a.W);
@@ -627,6 +627,7 @@ Status launch_conv6(hipStream_t s, const Conv6Args& a, int* stat_kind_out, Pendi
     // NARROW variant spreads over all four waves.  force_kernel (tests): 6 = conv6 (geometry 0 only), 7 = conv7.
     const bool idle_half = (a.Cout & 127) != 0 && (a.Cout & 127) <= 64 && a.Cout > 32;
     const bool use6 = a.force_kernel == 6 || (a.force_kernel != 7 && geo == 0 && (S > 1 || idle_half));
+    if (kernel_out) *kernel_out = use6 ? 6 : 7;
     if (use6 && geo != 0) return invalid("conv6 is built for the 8 x 32 geometry only (conv7 has the 16 x 16 and 8 x 8 ones)");
     if (!use6) DPIR_TRY(launch_conv7(s, k, blocks * S, a.x1));
     else if (a.x1) DPIR_TRY((launch6<0, 4, true>(s, k, blocks * S)));

@@ -3,6 +3,7 @@
 #include "engine.h"
 #include "conv6_params.h"
 #include "../../include/diffpir_debug.h"
+#include <string.h>
 #include <vector>
 using namespace dpir;
 static int fail(dpir_engine* e, const Status& s) {
@@ -283,6 +284,230 @@ int dpir_debug_conv5_layer(dpir_engine* e, int B, int ca, int cb, int Cout, int 
     API_TRY(e, st);
     API_HIP(e, hipStreamSynchronize(e->stream));
     API_HIP(e, hipMemcpy(out, dout, no * 4, hipMemcpyDeviceToHost));
+    return DPIR_OK;
+}
+
+// One 3x3 layer on caller-supplied host operands (include/diffpir_debug.h dpir_debug_conv3_desc): the prologue the forward would run
+// (none / act_split or the fp32 kernel's own table prologue / gn_act_small), then launch_conv6, launch_conv8 or launch_conv as Fwd::conv
+// and Fwd::gn_conv (unet.hip) call them.  Which kernel ran, the split-K factor and the statistics kind are read back from the launchers.
+int dpir_debug_conv3_layer(dpir_engine* e, dpir_debug_conv3_desc* d) {
+    if (!e || !d) return DPIR_ERR_INVALID;
+    d->path_out = -1; d->ksplit_out = 0; d->stat_kind_out = 0;
+    const int B = d->B, ca = d->ca, cb = d->cb, Cout = d->Cout, H = d->H, W = d->W, mode = d->mode, C = ca + cb;
+    if (!d->xa || !d->w || !d->bias || !d->out || B <= 0 || ca <= 0 || cb < 0 || (cb > 0 && !d->xb) || Cout <= 0 || H <= 0 || W <= 0 || mode < 0 || mode > 2 ||
+        d->res_mode < -1 || d->res_mode > 2 || (d->res_mode >= 0 && !d->res) || d->prologue < 0 || d->prologue > 2 ||
+        (d->route != 0 && d->route != 6 && d->route != 7 && d->route != 8))
+        return fail(e, invalid("conv3 layer: bad descriptor"));
+    if (d->prologue == 1 && !d->prm) return fail(e, invalid("conv3 layer: prologue 1 needs the table"));
+    if (d->prologue == 2 && (!d->gamma || !d->beta)) return fail(e, invalid("conv3 layer: prologue 2 needs gamma and beta"));
+    if (mode == 1 && ((H | W) & 1)) return fail(e, invalid("conv3 layer: a nearest-up source needs an even output size"));
+    if (d->res_mode == 1 && ((H | W) & 1)) return fail(e, invalid("conv3 layer: a half-resolution residual needs an even output size"));
+    if (d->defer && (!d->split || (d->route != 0 && d->route != 7) || !d->gamma2 || !d->beta2 || !d->w2 || !d->bias2 || !d->out2 || d->Cout2 <= 0))
+        return fail(e, invalid("conv3 layer: defer needs split, route 0 or 7 and the second stage's operands"));
+    (void)hipSetDevice(e->device);
+    const int Hs = mode == 1 ? H / 2 : (mode == 2 ? H * 2 : H), Ws = mode == 1 ? W / 2 : (mode == 2 ? W * 2 : W);
+    const size_t HWs = (size_t)Hs * Ws, HW = (size_t)H * W;
+    const size_t na = (size_t)B * ca * HWs, nb = (size_t)B * cb * HWs, no = (size_t)B * Cout * HW;
+    const size_t nres = d->res_mode == 1 ? no / 4 : (d->res_mode == 2 ? no * 4 : no);
+    const int coutp = round_up(Cout, 64);
+    float *dxa = nullptr, *dxb = nullptr, *dbias = nullptr, *dout = nullptr, *dres = nullptr, *scale = nullptr; float4* dprm = nullptr;
+    API_TRY(e, e->ws.getT("c3#xa", na, &dxa));
+    API_TRY(e, e->ws.getT("c3#xb", nb + 1, &dxb));
+    API_TRY(e, e->ws.getT("c3#b", (size_t)coutp, &dbias));
+    API_TRY(e, e->ws.getT("c3#o", no, &dout));
+    API_TRY(e, e->ws.getT("c3#res", nres, &dres));
+    API_TRY(e, e->ws.getT("c3#prm", (size_t)B * C, &dprm));
+    API_TRY(e, e->ws.getT("c3#scale", (size_t)4, &scale));
+    API_HIP(e, hipMemcpy(dxa, d->xa, na * 4, hipMemcpyHostToDevice));
+    if (cb) API_HIP(e, hipMemcpy(dxb, d->xb, nb * 4, hipMemcpyHostToDevice));
+    API_HIP(e, hipMemset(dbias, 0, (size_t)coutp * 4));
+    API_HIP(e, hipMemcpy(dbias, d->bias, (size_t)Cout * 4, hipMemcpyHostToDevice));
+    if (d->prologue == 1) API_HIP(e, hipMemcpy(dprm, d->prm, (size_t)B * C * 16, hipMemcpyHostToDevice));
+    if (d->res_mode >= 0) API_HIP(e, hipMemcpy(dres, d->res, nres * 4, hipMemcpyHostToDevice));
+    const float quarter = 0.25f;
+    API_HIP(e, hipMemcpy(scale, &quarter, 4, hipMemcpyHostToDevice));
+    API_HIP(e, hipMemset(dout, 0xFF, no * 4));
+    const float* res = d->res_mode >= 0 ? dres : nullptr;
+    const int res_mode = d->res_mode >= 0 ? d->res_mode : 0;
+    const CatSrc src{dxa, ca, cb ? dxb : nullptr, cb};
+    const bool x1 = e->precision == 2;
+    const bool f16path = e->precision != 0 && conv6_supported(H, W);
+    const size_t pcap = (size_t)16 * no;                       // room for 16 slabs
+    float* partial = nullptr;
+    if (d->split) {
+        API_TRY(e, e->ws.getT("c3#partial", pcap, &partial));
+        API_HIP(e, hipMemset(partial, 0xFF, pcap * 4));
+    }
+
+    if (d->route == 8) {        // Fwd::conv's output-layer route
+        if (e->precision == 0) return fail(e, invalid("conv3 layer: conv8 needs an f16 engine"));
+        if (d->prologue != 1 || cb || mode != 0 || res || d->scaled || d->split) return fail(e, invalid("conv3 layer: conv8 takes a table prologue, one source, no resampling, no residual"));
+        if (!conv8_supported(B, C, Cout, H, W)) return fail(e, invalid("conv8: shape not supported"));
+        std::vector<uint16_t> w8;
+        const float w8_scale = pack_weights_conv8(d->w, Cout, C, w8);
+        void* wp = nullptr;
+        API_TRY(e, e->ws.get("c3#w8", w8.size() * 2, &wp));
+        API_HIP(e, hipMemcpy(wp, w8.data(), w8.size() * 2, hipMemcpyHostToDevice));
+        Conv8Args a8;
+        a8.x = dxa; a8.prm = dprm; a8.w = wp; a8.w_scale = w8_scale; a8.bias = dbias; a8.out = dout;
+        a8.B = B; a8.C = C; a8.Cout = Cout; a8.H = H; a8.W = W; a8.range_ctr = e->range_ctr; a8.x1 = x1;
+        a8.silu = d->prm[3] != 0.f;
+        API_TRY(e, launch_conv8(e->stream, a8));
+        API_HIP(e, hipStreamSynchronize(e->stream));
+        API_HIP(e, hipMemcpy(d->out, dout, no * 4, hipMemcpyDeviceToHost));
+        d->path_out = 8;
+        return DPIR_OK;
+    }
+
+    if (!f16path) {             // the fp32 kernel: everything the f16 path refuses, and the whole f32 engine
+        if (d->route != 0) return fail(e, invalid("conv3 layer: conv6 / conv7 cannot be forced here (f32 engine or a shape the f16 path refuses)"));
+        if (d->prologue == 2) return fail(e, Status{DPIR_ERR_UNSUPPORTED, "conv3 layer: gn_act_small only feeds the f16 path"});
+        if (d->scaled || d->defer) return fail(e, invalid("conv3 layer: the fp32 kernel has no device output scale and no deferred combine"));
+        // load_conv's packing of the fp32 operand: [CinP][taps][CoutP]
+        const int cinp = round_up(C, 16);
+        std::vector<float> packed((size_t)cinp * 9 * coutp, 0.f);
+        for (int co = 0; co < Cout; ++co)
+            for (int ci = 0; ci < C; ++ci)
+                for (int t = 0; t < 9; ++t) packed[((size_t)ci * 9 + t) * coutp + co] = d->w[((size_t)co * C + ci) * 9 + t];
+        float* dw = nullptr;
+        API_TRY(e, e->ws.getT("c3#w", packed.size(), &dw));
+        API_HIP(e, hipMemcpy(dw, packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
+        ConvArgs a;
+        a.src.a = dxa; a.src.ca = ca; a.src.b = cb ? dxb : nullptr; a.src.cb = cb; a.src.Hs = Hs; a.src.Ws = Ws; a.src.mode = mode;
+        a.src.prm = d->prologue == 1 ? dprm : nullptr;
+        a.w = dw; a.bias = dbias; a.out = dout; a.res = res; a.res_mode = res_mode;
+        a.B = B; a.Cin = C; a.Cout = Cout; a.CoutP = coutp; a.H = H; a.W = W; a.ks = 3;
+        a.partial = partial; a.partial_capacity = partial ? pcap : 0;
+        API_TRY(e, launch_conv(e->stream, a));
+        API_HIP(e, hipStreamSynchronize(e->stream));
+        API_HIP(e, hipMemcpy(d->out, dout, no * 4, hipMemcpyDeviceToHost));
+        d->path_out = 0;
+        return DPIR_OK;
+    }
+
+    // ---- the f16 path: operand planes, then launch_conv6
+    const int C8 = 2 * ((C + 15) / 16);
+    const size_t plane = (size_t)B * C8 * HW * 16;
+    char* s16 = nullptr;
+    API_TRY(e, e->ws.getT("c3#s16", 2 * plane, &s16));
+    API_HIP(e, hipMemset(s16, 0xFF, 2 * plane));
+    if (d->prologue == 2) {     // Fwd::gn_conv's fused low-resolution prologue
+        if (C % 16 || !gn_act_small_supported(C, Hs, Ws, mode)) return fail(e, Status{DPIR_ERR_UNSUPPORTED, "conv3 layer: gn_act_small refuses this shape"});
+        float *dg = nullptr, *db = nullptr, *df = nullptr;
+        API_TRY(e, e->ws.getT("c3#gamma", (size_t)C, &dg));
+        API_TRY(e, e->ws.getT("c3#beta", (size_t)C, &db));
+        API_TRY(e, e->ws.getT("c3#film", (size_t)B * 2 * C, &df));
+        API_HIP(e, hipMemcpy(dg, d->gamma, (size_t)C * 4, hipMemcpyHostToDevice));
+        API_HIP(e, hipMemcpy(db, d->beta, (size_t)C * 4, hipMemcpyHostToDevice));
+        if (d->film) API_HIP(e, hipMemcpy(df, d->film, (size_t)B * 2 * C * 4, hipMemcpyHostToDevice));
+        GnActArgs ga;
+        ga.src = src; ga.gamma = dg; ga.beta = db;
+        ga.film = d->film ? df : nullptr; ga.film_stride = 2 * C; ga.film_off = 0; ga.fstep = nullptr; ga.frows = 2 * C;
+        ga.silu = true; ga.mode = mode; ga.B = B; ga.Hs = Hs; ga.Ws = Ws;
+        ga.hi = s16; ga.lo = x1 ? nullptr : s16 + plane; ga.range_ctr = e->range_ctr;
+        API_TRY(e, launch_gn_act_small(e->stream, ga));
+    } else {
+        API_TRY(e, launch_act_split(e->stream, src, d->prologue == 1 ? dprm : nullptr, mode, B, H, W, s16, x1 ? nullptr : s16 + plane, e->range_ctr));
+    }
+    std::vector<uint16_t> w16v;
+    const float w16_scale = pack_weights_conv6(d->w, Cout, C, w16v);
+    void* wp = nullptr;
+    API_TRY(e, e->ws.get("c3#w16", w16v.size() * 2, &wp));
+    API_HIP(e, hipMemcpy(wp, w16v.data(), w16v.size() * 2, hipMemcpyHostToDevice));
+    // Fwd::conv6_on_planes
+    Conv6Args a6;
+    a6.x1 = x1;
+    a6.xhi = s16; a6.xlo = s16 + plane; a6.w16 = wp; a6.w16_scale = w16_scale;
+    a6.bias = dbias; a6.out = dout; a6.res = res; a6.res_mode = res_mode;
+    a6.B = B; a6.Cin = C; a6.Cout = Cout; a6.H = H; a6.W = W;
+    a6.partial = partial; a6.partial_capacity = partial ? pcap : 0;
+    a6.force_kernel = d->route;
+    if (d->scaled) a6.out_scale_dev = scale;
+    const int slots = conv6_stat_slots(H, W);
+    float2* st = nullptr; double2* sp = nullptr;
+    const size_t nst = (size_t)B * Cout * slots;
+    if (slots > 0 && Cout % 32 == 0) {
+        API_TRY(e, e->ws.getT("c3#st", nst, &st));
+        API_TRY(e, e->ws.getT("c3#sp", (size_t)B * Cout, &sp));
+        API_HIP(e, hipMemset(st, 0xFF, nst * 8));
+        API_HIP(e, hipMemset(sp, 0xFF, (size_t)B * Cout * 16));
+    }
+    a6.stat = st; a6.stat_plane = sp;
+    int kind = 0, kernel = 0;
+    PendingConv pc;
+    API_TRY(e, launch_conv6(e->stream, a6, &kind, d->defer ? &pc : nullptr, &kernel));
+    d->path_out = kernel; d->stat_kind_out = kind;
+    d->ksplit_out = kind == 3 ? pc.ksplit : 1;
+    if (d->split && !d->defer) {     // the resolved launch keeps its factor to itself: the same launch again with the combine left pending
+        PendingConv probe;
+        Conv6Args b6 = a6;
+        float* o2 = nullptr;
+        API_TRY(e, e->ws.getT("c3#o_again", no, &o2));
+        b6.out = o2;
+        int k2 = 0;
+        API_HIP(e, hipStreamSynchronize(e->stream));
+        std::vector<float> first(no);
+        API_HIP(e, hipMemcpy(first.data(), dout, no * 4, hipMemcpyDeviceToHost));
+        API_TRY(e, launch_conv6(e->stream, b6, &k2, &probe));
+        d->ksplit_out = k2 == 3 ? probe.ksplit : 1;
+        if (k2 == 3) API_TRY(e, launch_conv6_resolve(e->stream, probe));
+        API_HIP(e, hipStreamSynchronize(e->stream));
+        // both launches ran the same slabs in the same order: the output of the first one is what is returned, the second must equal it
+        std::vector<float> again(no);
+        API_HIP(e, hipMemcpy(again.data(), o2, no * 4, hipMemcpyDeviceToHost));
+        if (memcmp(first.data(), again.data(), no * 4) != 0) return fail(e, Status{DPIR_ERR_STATE, "conv3 layer: two identical split-K launches disagree"});
+    }
+    if (d->defer) {
+        if (kind != 3) return fail(e, invalid("conv3 layer: defer was asked for but launch_conv6 did not split this launch"));
+        // Fwd::gn_conv after a split-K conv1: the fused prologue of the next layer combines the slabs (and stores the finished tensor)
+        const int Cn = Cout, Co2 = d->Cout2;
+        if (Cn % 16 || !gn_act_small_supported(Cn, H, W, 0)) return fail(e, Status{DPIR_ERR_UNSUPPORTED, "conv3 layer: gn_act_small refuses the second stage"});
+        const int C8b = 2 * ((Cn + 15) / 16);
+        const size_t plane2 = (size_t)B * C8b * HW * 16, no2 = (size_t)B * Co2 * HW;
+        char* s16b = nullptr; float *dg = nullptr, *db = nullptr, *dbias2 = nullptr, *dout2 = nullptr;
+        API_TRY(e, e->ws.getT("c3#s16b", 2 * plane2, &s16b));
+        API_TRY(e, e->ws.getT("c3#gamma2", (size_t)Cn, &dg));
+        API_TRY(e, e->ws.getT("c3#beta2", (size_t)Cn, &db));
+        API_TRY(e, e->ws.getT("c3#b2", (size_t)round_up(Co2, 64), &dbias2));
+        API_TRY(e, e->ws.getT("c3#o2", no2, &dout2));
+        API_HIP(e, hipMemset(s16b, 0xFF, 2 * plane2));
+        API_HIP(e, hipMemcpy(dg, d->gamma2, (size_t)Cn * 4, hipMemcpyHostToDevice));
+        API_HIP(e, hipMemcpy(db, d->beta2, (size_t)Cn * 4, hipMemcpyHostToDevice));
+        API_HIP(e, hipMemset(dbias2, 0, (size_t)round_up(Co2, 64) * 4));
+        API_HIP(e, hipMemcpy(dbias2, d->bias2, (size_t)Co2 * 4, hipMemcpyHostToDevice));
+        API_HIP(e, hipMemset(dout2, 0xFF, no2 * 4));
+        GnActArgs ga;
+        ga.src = CatSrc{dout, Cn, nullptr, 0}; ga.pend = pc; ga.gamma = dg; ga.beta = db;
+        ga.silu = true; ga.mode = 0; ga.B = B; ga.Hs = H; ga.Ws = W;
+        ga.hi = s16b; ga.lo = x1 ? nullptr : s16b + plane2; ga.range_ctr = e->range_ctr;
+        API_TRY(e, launch_gn_act_small(e->stream, ga));
+        std::vector<uint16_t> w16b;
+        const float w16b_scale = pack_weights_conv6(d->w2, Co2, Cn, w16b);
+        void* wp2 = nullptr;
+        API_TRY(e, e->ws.get("c3#w16b", w16b.size() * 2, &wp2));
+        API_HIP(e, hipMemcpy(wp2, w16b.data(), w16b.size() * 2, hipMemcpyHostToDevice));
+        Conv6Args c6;
+        c6.x1 = x1; c6.xhi = s16b; c6.xlo = s16b + plane2; c6.w16 = wp2; c6.w16_scale = w16b_scale;
+        c6.bias = dbias2; c6.out = dout2; c6.B = B; c6.Cin = Cn; c6.Cout = Co2; c6.H = H; c6.W = W;
+        API_TRY(e, launch_conv6(e->stream, c6));
+        API_HIP(e, hipStreamSynchronize(e->stream));
+        API_HIP(e, hipMemcpy(d->out2, dout2, no2 * 4, hipMemcpyDeviceToHost));
+    }
+    API_HIP(e, hipStreamSynchronize(e->stream));
+    API_HIP(e, hipMemcpy(d->out, dout, no * 4, hipMemcpyDeviceToHost));
+    if (d->stat_out && (kind == 1 || kind == 2)) {
+        if (kind == 1) {        // epilogue slots: fp32 partial sums of at most 256 values, folded in fp64 (gn_prm's contract)
+            std::vector<float2> hs(nst);
+            API_HIP(e, hipMemcpy(hs.data(), st, nst * 8, hipMemcpyDeviceToHost));
+            for (size_t pl = 0; pl < (size_t)B * Cout; ++pl) {
+                double s1 = 0.0, s2 = 0.0;
+                for (int k = 0; k < slots; ++k) { s1 += (double)hs[pl * slots + k].x; s2 += (double)hs[pl * slots + k].y; }
+                d->stat_out[2 * pl] = s1; d->stat_out[2 * pl + 1] = s2;
+            }
+        } else {
+            API_HIP(e, hipMemcpy(d->stat_out, sp, (size_t)B * Cout * 16, hipMemcpyDeviceToHost));
+        }
+    }
     return DPIR_OK;
 }
 

@@ -38,6 +38,26 @@ int dpir_debug_conv7_emit_supported(dpir_engine* e, int B, int Cout, int H, int 
  * precision (f16x3 / f16x1) selects the products. */
 int dpir_debug_conv5_layer(dpir_engine* e, int B, int ca, int cb, int Cout, int H, int W, int tile, const float* xa, const float* xb,
                            const float* w, const float* bias, const float* prm, const float* res, float* out, int* path_out);
+/* One 3x3 convolution layer on host operands through the routes of the forward (Fwd::conv / Fwd::gn_conv): prologue, then launch_conv6
+ * (conv6 / conv7, all three tile geometries, whole K or split-K), launch_conv8 or the general fp32 kernel.  Sources are at the resolution
+ * `mode` implies (0 plain, 1 nearest-up: H/2 x W/2, 2 average pool: 2H x 2W); H x W is the output resolution.
+ *   prologue 0 none; 1 the table prm[B][ca+cb][4] {mean, scale, shift, SiLU flag} (act_split, or the fp32 kernel's own prologue); 2 GroupNorm32
+ *     (gamma, beta, optional per-image FiLM rows film[B][2C] = {scale, shift}) + SiLU through gn_act_small, which computes the statistics.
+ *   res_mode -1 none, 0 same shape, 1 half resolution (nearest-up), 2 double resolution (2x2 mean); scaled: a device output scale of 0.25.
+ *   route 0: the engine precision's own dispatch (f16x3 / f16x1: planes + launch_conv6; f32, or a shape conv6 refuses: launch_conv);
+ *     6 / 7: force_kernel; 8: launch_conv8 (prologue 1 with the SiLU flag, one source, mode 0).
+ *   split 0: no slab buffer; 1: a slab buffer, launch_conv6's own rule decides.
+ *   defer (split, route 0 / 7): the split-K combine is left to a second stage, gn_act_small(gamma2, beta2, SiLU) with the pending convolution
+ *     followed by a second 3x3 layer (w2 [Cout2][Cout][3][3], bias2): out = the first layer as gn_act_small stored it, out2 = the second layer.
+ * Outputs: out; stat_out[B][Cout][2] fp64 {sum, sum of squares} where the launch produced statistics (stat_kind_out 1: epilogue slots,
+ * folded here; 2: the split-K combine's per-plane records; 0 none; 3 left pending); path_out 0 fp32 kernel / 6 / 7 / 8; ksplit_out. */
+typedef struct dpir_debug_conv3_desc {
+    int32_t B, ca, cb, Cout, H, W, mode, res_mode, scaled, prologue, route, split, defer, Cout2;
+    const float *xa, *xb, *w, *bias, *res, *prm, *gamma, *beta, *film, *gamma2, *beta2, *w2, *bias2;
+    float* out; double* stat_out; float* out2;
+    int32_t stat_kind_out, path_out, ksplit_out, reserved;
+} dpir_debug_conv3_desc;
+int dpir_debug_conv3_layer(dpir_engine* e, dpir_debug_conv3_desc* d);
 #ifdef __cplusplus
 }
 #endif
