@@ -2,6 +2,7 @@
 // against the product library and uses its internal launchers; nothing here is on the product path.
 #include "engine.h"
 #include "conv6_params.h"
+#include "conv9.h"
 #include "../../include/diffpir_debug.h"
 #include <string.h>
 #include <vector>
@@ -508,6 +509,114 @@ int dpir_debug_conv3_layer(dpir_engine* e, dpir_debug_conv3_desc* d) {
             API_HIP(e, hipMemcpy(d->stat_out, sp, (size_t)B * Cout * 16, hipMemcpyDeviceToHost));
         }
     }
+    return DPIR_OK;
+}
+
+// One 8 x 8 layer on caller-supplied host operands through conv9 (csrc/conv9.hip), as Fwd::conv6_on_planes / Fwd::resblock (unet.hip) launch it
+// -- without their workgroup threshold, so that one image can be run alone.  Planes of the first layer: act_split (optionally with a table).
+// hop: conv1's epilogue writes the second layer's planes (GroupNorm32(gamma2, beta2) + FiLM rows + SiLU), the second layer runs on conv9 too.
+int dpir_debug_conv9_layer(dpir_engine* e, dpir_debug_conv9_desc* d) {
+    if (!e || !d) return DPIR_ERR_INVALID;
+    d->ran_out = 0;
+    const int B = d->B, Cin = d->Cin, Cout = d->Cout, H = d->H, W = d->W;
+    if (!d->x || !d->w || !d->bias || B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || d->res_mode < -1 || d->res_mode > 2 ||
+        (d->res_mode >= 0 && !d->res) || (!d->hop && !d->out) || (d->hop && (!d->gamma2 || !d->beta2 || !d->w2 || !d->bias2 || !d->out2 || d->Cout2 <= 0)))
+        return fail(e, invalid("conv9 layer: bad descriptor"));
+    if (e->grad_enabled) return fail(e, Status{DPIR_ERR_UNSUPPORTED, "conv9 layer: a gradient-mode engine keeps launch_conv6's route"});
+    if (e->precision == 0) return fail(e, Status{DPIR_ERR_UNSUPPORTED, "conv9 layer: the f32 precision keeps the fp32 kernel"});
+    if (d->hop && d->res_mode >= 0) return fail(e, invalid("conv9 layer: the hop's first layer takes no residual"));
+    if ((d->res_mode == 1 && ((H | W) & 1))) return fail(e, invalid("conv9 layer: a half-resolution residual needs an even output size"));
+    (void)hipSetDevice(e->device);
+    const bool x1 = e->precision == 2;
+    const size_t HW = (size_t)H * W, nx = (size_t)B * Cin * HW, no = (size_t)B * Cout * HW;
+    const size_t nres = d->res_mode == 1 ? no / 4 : (d->res_mode == 2 ? no * 4 : no);
+    const int chunks = (Cin + 15) / 16, C8 = 2 * chunks;
+    const size_t plane = (size_t)B * C8 * HW * 16;
+    float *dx = nullptr, *dbias = nullptr, *dout = nullptr, *dres = nullptr; float4* dprm = nullptr; double2* sp = nullptr; char* s16 = nullptr;
+    API_TRY(e, e->ws.getT("c9#x", nx, &dx));
+    API_TRY(e, e->ws.getT("c9#b", (size_t)round_up(Cout, 64), &dbias));
+    API_TRY(e, e->ws.getT("c9#o", no, &dout));
+    API_TRY(e, e->ws.getT("c9#res", nres, &dres));
+    API_TRY(e, e->ws.getT("c9#prm", (size_t)B * Cin, &dprm));
+    API_TRY(e, e->ws.getT("c9#sp", (size_t)B * Cout, &sp));
+    API_TRY(e, e->ws.getT("c9#s16", 2 * plane, &s16));
+    API_HIP(e, hipMemcpy(dx, d->x, nx * 4, hipMemcpyHostToDevice));
+    API_HIP(e, hipMemset(dbias, 0, (size_t)round_up(Cout, 64) * 4));
+    API_HIP(e, hipMemcpy(dbias, d->bias, (size_t)Cout * 4, hipMemcpyHostToDevice));
+    if (d->prm) API_HIP(e, hipMemcpy(dprm, d->prm, (size_t)B * Cin * 16, hipMemcpyHostToDevice));
+    if (d->res_mode >= 0) API_HIP(e, hipMemcpy(dres, d->res, nres * 4, hipMemcpyHostToDevice));
+    // poison on the engine's stream (non-blocking: a null-stream memset is not ordered with the launches below)
+    API_HIP(e, hipMemsetAsync(dout, 0xFF, no * 4, e->stream));
+    API_HIP(e, hipMemsetAsync(sp, 0xFF, (size_t)B * Cout * 16, e->stream));
+    API_HIP(e, hipMemsetAsync(s16, 0xFF, 2 * plane, e->stream));
+    API_TRY(e, launch_act_split(e->stream, CatSrc{dx, Cin, nullptr, 0}, d->prm ? dprm : nullptr, 0, B, H, W, s16, x1 ? nullptr : s16 + plane, e->range_ctr));
+    std::vector<uint16_t> w16v;
+    const float w16_scale = pack_weights_conv6(d->w, Cout, Cin, w16v);
+    void* wp = nullptr;
+    API_TRY(e, e->ws.get("c9#w16", w16v.size() * 2, &wp));
+    API_HIP(e, hipMemcpy(wp, w16v.data(), w16v.size() * 2, hipMemcpyHostToDevice));
+    Conv9Args a9;
+    a9.xhi = s16; a9.xlo = s16 + plane; a9.w16 = wp; a9.w16_scale = w16_scale; a9.bias = dbias; a9.out = dout;
+    if (d->res_mode >= 0) { a9.res = dres; a9.res_mode = d->res_mode; }
+    a9.B = B; a9.Cin = Cin; a9.Cout = Cout; a9.H = H; a9.W = W; a9.stat_plane = sp; a9.x1 = x1;
+    d->ms_out = 0.0;
+    auto timed = [&](auto&& launch) -> int {       // iters > 0: the launch again, back to back, averaged
+        if (d->iters <= 0) return DPIR_OK;
+        hipEvent_t e0, e1;
+        API_HIP(e, hipEventCreate(&e0)); API_HIP(e, hipEventCreate(&e1));
+        API_HIP(e, hipEventRecord(e0, e->stream));
+        for (int i = 0; i < d->iters; ++i) API_TRY(e, launch());
+        API_HIP(e, hipEventRecord(e1, e->stream));
+        API_HIP(e, hipEventSynchronize(e1));
+        float ms = 0; API_HIP(e, hipEventElapsedTime(&ms, e0, e1));
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        d->ms_out = ms / d->iters;
+        return DPIR_OK;
+    };
+    if (!d->hop) {
+        API_TRY(e, launch_conv9(e->stream, a9));
+        if (int rc = timed([&]() { return launch_conv9(e->stream, a9); })) return rc;
+        API_HIP(e, hipStreamSynchronize(e->stream));
+        d->ran_out = 1;
+        API_HIP(e, hipMemcpy(d->out, dout, no * 4, hipMemcpyDeviceToHost));
+        if (d->stat_out) API_HIP(e, hipMemcpy(d->stat_out, sp, (size_t)B * Cout * 16, hipMemcpyDeviceToHost));
+        return DPIR_OK;
+    }
+    const int Co2 = d->Cout2, C8b = 2 * ((Cout + 15) / 16);
+    const size_t plane2 = (size_t)B * C8b * HW * 16, no2 = (size_t)B * Co2 * HW;
+    char* s16b = nullptr; float *dg = nullptr, *db = nullptr, *df = nullptr, *dbias2 = nullptr, *dout2 = nullptr;
+    API_TRY(e, e->ws.getT("c9#s16b", 2 * plane2, &s16b));
+    API_TRY(e, e->ws.getT("c9#gamma2", (size_t)Cout, &dg));
+    API_TRY(e, e->ws.getT("c9#beta2", (size_t)Cout, &db));
+    API_TRY(e, e->ws.getT("c9#film2", (size_t)B * 2 * Cout, &df));
+    API_TRY(e, e->ws.getT("c9#b2", (size_t)round_up(Co2, 64), &dbias2));
+    API_TRY(e, e->ws.getT("c9#o2", no2, &dout2));
+    API_HIP(e, hipMemsetAsync(s16b, 0xFF, 2 * plane2, e->stream));
+    API_HIP(e, hipMemcpy(dg, d->gamma2, (size_t)Cout * 4, hipMemcpyHostToDevice));
+    API_HIP(e, hipMemcpy(db, d->beta2, (size_t)Cout * 4, hipMemcpyHostToDevice));
+    if (d->film2) API_HIP(e, hipMemcpy(df, d->film2, (size_t)B * 2 * Cout * 4, hipMemcpyHostToDevice));
+    API_HIP(e, hipMemset(dbias2, 0, (size_t)round_up(Co2, 64) * 4));
+    API_HIP(e, hipMemcpy(dbias2, d->bias2, (size_t)Co2 * 4, hipMemcpyHostToDevice));
+    API_HIP(e, hipMemsetAsync(dout2, 0xFF, no2 * 4, e->stream));
+    std::vector<uint16_t> w16b;
+    const float w16b_scale = pack_weights_conv6(d->w2, Co2, Cout, w16b);
+    void* wp2 = nullptr;
+    API_TRY(e, e->ws.get("c9#w16b", w16b.size() * 2, &wp2));
+    API_HIP(e, hipMemcpy(wp2, w16b.data(), w16b.size() * 2, hipMemcpyHostToDevice));
+    Conv6Emit em;
+    em.hi = s16b; em.lo = x1 ? nullptr : s16b + plane2; em.C8 = C8b; em.gamma = dg; em.beta = db;
+    em.film = d->film2 ? df : nullptr; em.film_stride = 2 * Cout; em.film_off = 0; em.frows = 2 * Cout; em.fstep = nullptr;
+    em.range_ctr = e->range_ctr;
+    a9.out = nullptr; a9.stat_plane = nullptr; a9.emit = &em;
+    API_TRY(e, launch_conv9(e->stream, a9));
+    Conv9Args b9;
+    b9.xhi = s16b; b9.xlo = s16b + plane2; b9.w16 = wp2; b9.w16_scale = w16b_scale; b9.bias = dbias2; b9.out = dout2;
+    b9.B = B; b9.Cin = Cout; b9.Cout = Co2; b9.H = H; b9.W = W; b9.x1 = x1;
+    API_TRY(e, launch_conv9(e->stream, b9));
+    if (int rc = timed([&]() -> Status { DPIR_TRY(launch_conv9(e->stream, a9)); return launch_conv9(e->stream, b9); })) return rc;
+    API_HIP(e, hipStreamSynchronize(e->stream));
+    d->ran_out = 1;
+    API_HIP(e, hipMemcpy(d->out2, dout2, no2 * 4, hipMemcpyDeviceToHost));
     return DPIR_OK;
 }
 

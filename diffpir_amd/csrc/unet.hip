@@ -8,6 +8,7 @@
 // exist as separate passes (see conv.hip).
 #include "engine.h"
 #include "conv6_params.h"
+#include "conv9.h"
 #include <unordered_map>
 #include <cstdint>
 #include <math.h>
@@ -382,6 +383,17 @@ struct Fwd {
         return conv(cw, in, mode, prm, res, res_mode, out, Ho, Wo, emit);
     }
 
+    // conv9 (csrc/conv9.hip) takes a 3x3 layer when the shape fits its whole-image tile, the forward is not recording a tape, the
+    // precision is one of the f16 modes and the launch has enough workgroups (B x Cout / 32) to fill the device: below the threshold the
+    // split-K route of launch_conv6, tuned for small batches, stays.  DPIR_CONV9=0 restores launch_conv6's dispatch everywhere,
+    // DPIR_CONV9_MIN_WG overrides the threshold (profiles/conv9/README.md has the per-layer table it comes from).
+    bool conv9_route(const ConvW& cw, int Ho, int Wo, bool hop) const {
+        static const bool on = !(getenv("DPIR_CONV9") && atoi(getenv("DPIR_CONV9")) == 0);
+        static const int min_wg = getenv("DPIR_CONV9_MIN_WG") ? atoi(getenv("DPIR_CONV9_MIN_WG")) : kConv9MinWg;
+        return on && !grad && e->precision != 0 && cw.w16 && cw.ks == 3 && conv9_supported(B, cw.cin, cw.cout, Ho, Wo, hop) &&
+               (long long)B * (cw.cout / 32) >= min_wg;
+    }
+
     Status conv6_on_planes(const ConvW& cw, char* s16, size_t plane, const float* res, int res_mode, float* out, int Ho, int Wo,
                            const Conv6Emit* emit = nullptr) {
         const bool x1 = e->precision == 2;
@@ -404,6 +416,18 @@ struct Fwd {
         int kind = 0;
         PendingConv pc;
         ProfScope ps(&e->prof, PC_CONV3);
+        // 8 x 8: one workgroup per (image, 32 output channels), whole K -- no slabs, nothing pending.  A hop (emit) reaches this shape only
+        // from resblock's conv9 branch: conv7's own emission needs the 8 x 32 geometry.
+        if (conv9_route(cw, Ho, Wo, emit != nullptr)) {
+            Conv9Args a9;
+            a9.xhi = s16; a9.xlo = s16 + plane; a9.w16 = cw.w16; a9.w16_scale = cw.w16_scale; a9.bias = cw.bias; a9.out = out;
+            a9.res = res; a9.res_mode = res_mode; a9.B = B; a9.Cin = cw.cin; a9.Cout = cw.cout; a9.H = Ho; a9.W = Wo;
+            a9.stat_plane = emit ? nullptr : sp; a9.x1 = x1; a9.emit = emit;
+            DPIR_TRY(launch_conv9(s, a9));
+            if (sp && !emit) fused[out] = FusedStat{nullptr, 0, sp};
+            else fused.erase(out);
+            return Status{};
+        }
         DPIR_TRY(launch_conv6(s, a6, &kind, fuse_small ? &pc : nullptr));
         if (kind == 1) fused[out] = FusedStat{st, slots, nullptr};
         else if (kind == 2) fused[out] = FusedStat{nullptr, 0, sp};
@@ -596,9 +620,20 @@ struct Fwd {
         // profiles/r04/dead_end_side_stream_skip_*.log.)
         float* sk = nullptr;
         if (r.has_skip) DPIR_TRY(ws.getT(r.name + "#skip", on, &sk));
-        const bool fuse = h1_fusable(r, Ho, Wo);
+        // 8 x 8 with both convolutions on conv9: a GroupNorm group of h1 is whole inside one workgroup of conv1, which writes conv2's planes
+        // itself -- nothing of Conv6Emit's arena is used.  Obeys fuse_h1 like conv7's hop (DPIR_FUSE_H1=0, time-out replay: plain conv9 + gn_act_small).
+        const bool hop9 = fuse_h1 && !grad && r.gn2.c == r.cout && conv9_route(r.conv1, Ho, Wo, true) && conv9_route(r.conv2, Ho, Wo, false);
+        const bool fuse = hop9 || h1_fusable(r, Ho, Wo);
         Conv6Emit em; char* s16b = nullptr; size_t plane2 = 0;
-        if (fuse) DPIR_TRY(make_emit(r, Ho, Wo, &em, &s16b, &plane2));
+        if (hop9) {
+            const int C8 = r.cout / 8;
+            plane2 = (size_t)B * C8 * Ho * Wo * 16;
+            DPIR_TRY(ws.getT("act#s16b", 2 * plane2, &s16b));
+            em.hi = s16b; em.lo = e->precision == 2 ? nullptr : s16b + plane2; em.C8 = C8;
+            em.gamma = r.gn2.gamma; em.beta = r.gn2.beta;
+            em.film = r.film_off >= 0 ? film : nullptr; em.film_stride = film_stride; em.film_off = r.film_off < 0 ? 0 : r.film_off;
+            em.frows = film_rows; em.fstep = fstep; em.range_ctr = e->range_ctr;
+        } else if (fuse) DPIR_TRY(make_emit(r, Ho, Wo, &em, &s16b, &plane2));
         DPIR_TRY(gn_conv(r.gn1, r.name + "#gn1", -1, r.conv1, in, r.mode, nullptr, 0, fuse ? nullptr : h1, Ho, Wo, &tr.prm1, &tr.st1, fuse ? &em : nullptr));
         if (!fuse) tap(r.name + "#h1", h1, on);
         if (r.has_skip) {

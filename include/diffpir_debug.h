@@ -58,6 +58,22 @@ typedef struct dpir_debug_conv3_desc {
     int32_t stat_kind_out, path_out, ksplit_out, reserved;
 } dpir_debug_conv3_desc;
 int dpir_debug_conv3_layer(dpir_engine* e, dpir_debug_conv3_desc* d);
+/* One 8 x 8 3x3 layer on host operands through conv9 (csrc/conv9.hip: one workgroup per image and 32 output channels, whole K), as the
+ * forward launches it above its workgroup threshold (the probe has no threshold: one image can be run alone).  x[B][Cin][H][W] is at the output
+ * resolution; prm: optional table [B][Cin][4] {mean, scale, shift, SiLU flag} applied by act_split; res / res_mode as dpir_debug_conv3_desc.
+ *   hop 0: out[B][Cout][H][W] and stat_out[B][Cout][2] fp64 {sum, sum of squares} of the stored planes.
+ *   hop 1: the first layer's epilogue writes the second layer's operand planes -- GroupNorm32(gamma2, beta2), optional per-image FiLM rows
+ *     film2[B][2 Cout] = {scale, shift}, SiLU -- and the second layer (w2 [Cout2][Cout][3][3], bias2) runs on conv9 as well: out2[B][Cout2][H][W].
+ * A refusal (shape, gradient-mode engine, f32 precision) is a non-zero return code with dpir_last_error's text; ran_out = 1 when conv9 ran.
+ * iters > 0: the launch (hop: both launches) is repeated back to back that many times and ms_out is the average time of one repeat. */
+typedef struct dpir_debug_conv9_desc {
+    int32_t B, Cin, Cout, H, W, res_mode, hop, Cout2;
+    const float *x, *w, *bias, *res, *prm, *gamma2, *beta2, *film2, *w2, *bias2;
+    float* out; double* stat_out; float* out2;
+    int32_t ran_out, iters;
+    double ms_out;
+} dpir_debug_conv9_desc;
+int dpir_debug_conv9_layer(dpir_engine* e, dpir_debug_conv9_desc* d);
 #ifdef __cplusplus
 }
 #endif
