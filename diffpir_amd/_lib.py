@@ -83,6 +83,13 @@ class Conv9Desc(C.Structure):
                 [(n, C.c_int32) for n in ("ran_out", "iters")] + [("ms_out", C.c_double)])
 
 
+class ConvUpDesc(C.Structure):
+    """dpir_debug_conv_up_desc (include/diffpir_debug.h): conv1 of an up-sampling ResBlock, or the two-layer hop, for dpir_debug_conv_up_layer."""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "Cin", "Cout", "Hs", "Ws", "hop", "force_hop", "Cout2", "route", "reserved")] +
+                [(n, C.c_void_p) for n in ("x", "w", "bias", "res", "prm", "gamma2", "beta2", "film2", "w2", "bias2", "out", "stat_out", "out2")] +
+                [(n, C.c_int32) for n in ("ran_out", "iters")] + [("ms_out", C.c_double)])
+
+
 PROF_CLASSES = 8
 PROF_NAMES = ["conv3x3", "conv1x1", "groupnorm_stats", "attention", "fft_prox", "elementwise", "unet_forward", "loop_graph"]
 
@@ -193,6 +200,10 @@ def load_debug():
     d.dpir_debug_conv3_layer.restype = C.c_int
     d.dpir_debug_conv9_layer.argtypes = [C.c_void_p, C.POINTER(Conv9Desc)]
     d.dpir_debug_conv9_layer.restype = C.c_int
+    d.dpir_debug_conv_up_layer.argtypes = [C.c_void_p, C.POINTER(ConvUpDesc)]
+    d.dpir_debug_conv_up_layer.restype = C.c_int
+    d.dpir_debug_conv_up_counts.argtypes = [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    d.dpir_debug_conv_up_counts.restype = None
     for n in ("dpir_debug_conv_bench", "dpir_debug_victim", "dpir_debug_victim_alu", "dpir_debug_victim_fft_pk", "dpir_debug_victim_fft_nopk",
               "dpir_debug_conv7_check"):
         getattr(d, n).restype = C.c_int

@@ -3,6 +3,7 @@
 #include "engine.h"
 #include "conv6_params.h"
 #include "conv9.h"
+#include "conv_up.h"
 #include "../../include/diffpir_debug.h"
 #include <string.h>
 #include <vector>
@@ -619,6 +620,146 @@ int dpir_debug_conv9_layer(dpir_engine* e, dpir_debug_conv9_desc* d) {
     API_HIP(e, hipMemcpy(d->out2, dout2, no2 * 4, hipMemcpyDeviceToHost));
     return DPIR_OK;
 }
+
+// conv1 of an up-sampling ResBlock on caller-supplied host operands (include/diffpir_debug.h dpir_debug_conv_up_desc), as Fwd::resblock_up
+// (unet.hip) launches it -- route 0: act_split at the SOURCE resolution + conv_up (csrc/conv_up.hip) -- or as the forward ran it before --
+// route 1: act_split with the nearest-up source + launch_conv6.  hop: the first layer's epilogue writes the second layer's planes and the second
+// layer runs through launch_conv6 in both routes.
+int dpir_debug_conv_up_layer(dpir_engine* e, dpir_debug_conv_up_desc* d) {
+    if (!e || !d) return DPIR_ERR_INVALID;
+    d->ran_out = 0; d->ms_out = 0.0;
+    const int B = d->B, Cin = d->Cin, Cout = d->Cout, Hs = d->Hs, Ws = d->Ws;
+    if (!d->x || !d->w || !d->bias || B <= 0 || Cin <= 0 || Cout <= 0 || Hs <= 0 || Ws <= 0 || (!d->hop && !d->out) || d->route < 0 || d->route > 1 ||
+        (d->hop && (!d->gamma2 || !d->beta2 || !d->w2 || !d->bias2 || !d->out2 || d->Cout2 <= 0)))
+        return fail(e, invalid("conv_up layer: bad descriptor"));
+    if (e->grad_enabled) return fail(e, Status{DPIR_ERR_UNSUPPORTED, "conv_up layer: a gradient-mode engine keeps launch_conv6's route"});
+    if (e->precision == 0) return fail(e, Status{DPIR_ERR_UNSUPPORTED, "conv_up layer: the f32 precision keeps the fp32 kernel"});
+    if (d->res) return fail(e, invalid("conv_up: conv1 of an up-sampling ResBlock takes no residual"));
+    const int min_wg = d->force_hop ? 0 : 384;
+    if (d->route == 0) {
+        if (const char* why = conv_up_supported(B, Cin, Cout, Hs, Ws, d->hop != 0, min_wg)) return fail(e, Status{DPIR_ERR_UNSUPPORTED, why});
+    } else if (Cin % 16 || !conv6_supported(2 * Hs, 2 * Ws) || (d->hop && !conv7_emit_supported(B, Cout, 2 * Hs, 2 * Ws))) {
+        return fail(e, Status{DPIR_ERR_UNSUPPORTED, "conv_up layer: launch_conv6's route refuses this shape"});
+    }
+    (void)hipSetDevice(e->device);
+    const bool x1 = e->precision == 2;
+    const int H = 2 * Hs, W = 2 * Ws;
+    const size_t HWs = (size_t)Hs * Ws, HW = 4 * HWs, nx = (size_t)B * Cin * HWs, no = (size_t)B * Cout * HW;
+    const int C8 = 2 * ((Cin + 15) / 16);
+    const size_t plane_s = (size_t)B * C8 * HWs * 16, plane = 4 * plane_s;
+    const int slots = conv_up_stat_slots(Hs, Ws);
+    const size_t nst = (size_t)B * Cout * slots;
+    float *dx = nullptr, *dbias = nullptr, *dout = nullptr; float4* dprm = nullptr; float2* st = nullptr; char* s16 = nullptr;
+    API_TRY(e, e->ws.getT("cu#x", nx, &dx));
+    API_TRY(e, e->ws.getT("cu#b", (size_t)round_up(Cout, 64), &dbias));
+    API_TRY(e, e->ws.getT("cu#o", no, &dout));
+    API_TRY(e, e->ws.getT("cu#prm", (size_t)B * Cin, &dprm));
+    API_TRY(e, e->ws.getT("cu#st", nst, &st));
+    API_TRY(e, e->ws.getT("cu#s16", 2 * plane, &s16));
+    API_HIP(e, hipMemcpy(dx, d->x, nx * 4, hipMemcpyHostToDevice));
+    API_HIP(e, hipMemset(dbias, 0, (size_t)round_up(Cout, 64) * 4));
+    API_HIP(e, hipMemcpy(dbias, d->bias, (size_t)Cout * 4, hipMemcpyHostToDevice));
+    if (d->prm) API_HIP(e, hipMemcpy(dprm, d->prm, (size_t)B * Cin * 16, hipMemcpyHostToDevice));
+    API_HIP(e, hipMemsetAsync(dout, 0xFF, no * 4, e->stream));
+    API_HIP(e, hipMemsetAsync(st, 0xFF, nst * 8, e->stream));
+    API_HIP(e, hipMemsetAsync(s16, 0xFF, 2 * plane, e->stream));
+    std::vector<uint16_t> wv;
+    const float w_scale = d->route == 0 ? pack_weights_conv_up(d->w, Cout, Cin, wv) : pack_weights_conv6(d->w, Cout, Cin, wv);
+    void* wp = nullptr;
+    API_TRY(e, e->ws.get("cu#w", wv.size() * 2, &wp));
+    API_HIP(e, hipMemcpy(wp, wv.data(), wv.size() * 2, hipMemcpyHostToDevice));
+    const CatSrc src{dx, Cin, nullptr, 0};
+    const float4* prm = d->prm ? dprm : nullptr;
+    // second layer and the hop's arena
+    const int Co2 = d->hop ? d->Cout2 : 0, C8b = 2 * ((Cout + 15) / 16);
+    const size_t plane2 = (size_t)B * C8b * HW * 16, no2 = (size_t)B * Co2 * HW;
+    char* s16b = nullptr; float *dg = nullptr, *db = nullptr, *df = nullptr, *dbias2 = nullptr, *dout2 = nullptr; long long* arena = nullptr; void* wp2 = nullptr;
+    const size_t arena_words = (size_t)B * 64 + ((size_t)B * ((Cout + 63) / 64) + 1) / 2;
+    Conv6Emit em;
+    float w2_scale = 1.f;
+    if (d->hop) {
+        API_TRY(e, e->ws.getT("cu#s16b", 2 * plane2, &s16b));
+        API_TRY(e, e->ws.getT("cu#gamma2", (size_t)Cout, &dg));
+        API_TRY(e, e->ws.getT("cu#beta2", (size_t)Cout, &db));
+        API_TRY(e, e->ws.getT("cu#film2", (size_t)B * 2 * Cout, &df));
+        API_TRY(e, e->ws.getT("cu#b2", (size_t)round_up(Co2, 64), &dbias2));
+        API_TRY(e, e->ws.getT("cu#o2", no2, &dout2));
+        API_TRY(e, e->ws.getT("cu#arena", arena_words, &arena));
+        API_HIP(e, hipMemsetAsync(s16b, 0xFF, 2 * plane2, e->stream));
+        API_HIP(e, hipMemcpy(dg, d->gamma2, (size_t)Cout * 4, hipMemcpyHostToDevice));
+        API_HIP(e, hipMemcpy(db, d->beta2, (size_t)Cout * 4, hipMemcpyHostToDevice));
+        if (d->film2) API_HIP(e, hipMemcpy(df, d->film2, (size_t)B * 2 * Cout * 4, hipMemcpyHostToDevice));
+        API_HIP(e, hipMemset(dbias2, 0, (size_t)round_up(Co2, 64) * 4));
+        API_HIP(e, hipMemcpy(dbias2, d->bias2, (size_t)Co2 * 4, hipMemcpyHostToDevice));
+        API_HIP(e, hipMemsetAsync(dout2, 0xFF, no2 * 4, e->stream));
+        std::vector<uint16_t> w16b;
+        w2_scale = pack_weights_conv6(d->w2, Co2, Cout, w16b);
+        API_TRY(e, e->ws.get("cu#w16b", w16b.size() * 2, &wp2));
+        API_HIP(e, hipMemcpy(wp2, w16b.data(), w16b.size() * 2, hipMemcpyHostToDevice));
+        em.hi = s16b; em.lo = x1 ? nullptr : s16b + plane2; em.C8 = C8b; em.gamma = dg; em.beta = db;
+        em.film = d->film2 ? df : nullptr; em.film_stride = 2 * Cout; em.film_off = 0; em.frows = 2 * Cout; em.fstep = nullptr;
+        em.acc = arena; em.cnt = reinterpret_cast<unsigned*>(arena + (size_t)B * 64); em.range_ctr = e->range_ctr;
+    }
+    int kernel1 = 0;
+    auto once = [&]() -> Status {
+        if (d->hop) DPIR_HIP(hipMemsetAsync(arena, 0, arena_words * 8, e->stream));
+        if (d->route == 0) {
+            DPIR_TRY(launch_act_split(e->stream, src, prm, 0, B, Hs, Ws, s16, x1 ? nullptr : s16 + plane_s, e->range_ctr));
+            ConvUpArgs a;
+            a.xhi = s16; a.xlo = s16 + plane_s; a.wup = wp; a.wup_scale = w_scale; a.bias = dbias; a.out = d->hop ? nullptr : dout;
+            a.B = B; a.Cin = Cin; a.Cout = Cout; a.Hs = Hs; a.Ws = Ws; a.stat = d->hop ? nullptr : st; a.x1 = x1;
+            a.emit = d->hop ? &em : nullptr; a.min_wg_hop = min_wg;
+            DPIR_TRY(launch_conv_up(e->stream, a));
+        } else {
+            DPIR_TRY(launch_act_split(e->stream, src, prm, 1, B, H, W, s16, x1 ? nullptr : s16 + plane, e->range_ctr));
+            Conv6Args a6;
+            a6.x1 = x1; a6.xhi = s16; a6.xlo = s16 + plane; a6.w16 = wp; a6.w16_scale = w_scale; a6.bias = dbias; a6.out = d->hop ? nullptr : dout;
+            a6.B = B; a6.Cin = Cin; a6.Cout = Cout; a6.H = H; a6.W = W; a6.stat = d->hop ? nullptr : st;
+            a6.emit = d->hop ? &em : nullptr;
+            int kind = 0;
+            DPIR_TRY(launch_conv6(e->stream, a6, &kind, nullptr, &kernel1));
+            if (!d->hop && kind != 1) return invalid("conv_up layer: launch_conv6 produced no epilogue statistics here");
+        }
+        if (d->hop) {
+            Conv6Args c6;
+            c6.x1 = x1; c6.xhi = s16b; c6.xlo = s16b + plane2; c6.w16 = wp2; c6.w16_scale = w2_scale;
+            c6.bias = dbias2; c6.out = dout2; c6.B = B; c6.Cin = Cout; c6.Cout = Co2; c6.H = H; c6.W = W;
+            DPIR_TRY(launch_conv6(e->stream, c6));
+        }
+        return Status{};
+    };
+    API_TRY(e, once());
+    if (d->iters > 0) {       // the whole route again, back to back, averaged
+        hipEvent_t e0, e1;
+        API_HIP(e, hipEventCreate(&e0)); API_HIP(e, hipEventCreate(&e1));
+        API_HIP(e, hipEventRecord(e0, e->stream));
+        for (int i = 0; i < d->iters; ++i) API_TRY(e, once());
+        API_HIP(e, hipEventRecord(e1, e->stream));
+        API_HIP(e, hipEventSynchronize(e1));
+        float ms = 0; API_HIP(e, hipEventElapsedTime(&ms, e0, e1));
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        d->ms_out = ms / d->iters;
+    }
+    API_HIP(e, hipStreamSynchronize(e->stream));
+    d->ran_out = d->route == 0 ? (d->hop ? 2 : 1) : 7;
+    if (d->hop) {
+        API_HIP(e, hipMemcpy(d->out2, dout2, no2 * 4, hipMemcpyDeviceToHost));
+        return DPIR_OK;
+    }
+    API_HIP(e, hipMemcpy(d->out, dout, no * 4, hipMemcpyDeviceToHost));
+    if (d->stat_out) {          // epilogue slots: fp32 partial sums of 64 values, folded in fp64 (gn_prm's contract)
+        std::vector<float2> hs(nst);
+        API_HIP(e, hipMemcpy(hs.data(), st, nst * 8, hipMemcpyDeviceToHost));
+        for (size_t pl = 0; pl < (size_t)B * Cout; ++pl) {
+            double s1 = 0.0, s2 = 0.0;
+            for (int k = 0; k < slots; ++k) { s1 += (double)hs[pl * slots + k].x; s2 += (double)hs[pl * slots + k].y; }
+            d->stat_out[2 * pl] = s1; d->stat_out[2 * pl + 1] = s2;
+        }
+    }
+    return DPIR_OK;
+}
+
+void dpir_debug_conv_up_counts(long long* plain, long long* hop) { conv_up_launch_counts(plain, hop); }
 
 int dpir_debug_conv7_emit_supported(dpir_engine* e, int B, int Cout, int H, int W, int* capacity_out) {
     if (!e) return 0;

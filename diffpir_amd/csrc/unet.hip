@@ -9,6 +9,7 @@
 #include "engine.h"
 #include "conv6_params.h"
 #include "conv9.h"
+#include "conv_up.h"
 #include <unordered_map>
 #include <cstdint>
 #include <math.h>
@@ -67,7 +68,7 @@ Status upload(dpir_engine* e, const float* host, size_t n, float** dev) {
 
 // OIHW (or OI1 for conv1d) -> [CinP][taps][CoutP], zero padded: CinP % 16 == 0, CoutP % 64 == 0 (conv2.hip's LDS-DMA
 // copies whole K chunks and 64-channel column blocks without bounds checks)
-Status load_conv(dpir_engine* e, const WeightMap& wm, const std::string& p, int cin, int cout, int ks, bool one_d, ConvW* out) {
+Status load_conv(dpir_engine* e, const WeightMap& wm, const std::string& p, int cin, int cout, int ks, bool one_d, ConvW* out, bool up_pack = false) {
     const float *w = nullptr, *b = nullptr;
     std::vector<int64_t> shape = one_d ? std::vector<int64_t>{cout, cin, 1} : std::vector<int64_t>{cout, cin, ks, ks};
     DPIR_TRY(wm.find(p + ".weight", shape, &w));
@@ -127,6 +128,16 @@ Status load_conv(dpir_engine* e, const WeightMap& wm, const std::string& p, int 
             DPIR_HIP(hipMemcpy(p8, w8.data(), w8.size() * 2, hipMemcpyHostToDevice));
             out->w8 = p8;
         }
+        if (up_pack && ks == 3 && !one_d && cin % 16 == 0 && cout % 32 == 0) {
+            // conv1 behind a nearest-x2 up-sampling: the four 2x2 phase filters (conv_up.hip), besides the 3x3 pack (gradient mode, small shapes)
+            std::vector<uint16_t> wu;
+            out->wup_scale = pack_weights_conv_up(w, cout, cin, wu);
+            void* pu = nullptr;
+            if (hipMalloc(&pu, wu.size() * 2) != hipSuccess) return Status{DPIR_ERR_NOMEM, "hipMalloc for the phase weights failed"};
+            e->net.allocs.push_back(pu);
+            DPIR_HIP(hipMemcpy(pu, wu.data(), wu.size() * 2, hipMemcpyHostToDevice));
+            out->wup = pu;
+        }
     }
     return Status{};
 }
@@ -172,7 +183,7 @@ Status unet_load(dpir_engine* e, const dpir_unet_desc* d, const dpir_tensor* wei
     auto add_res = [&](const std::string& p, int cin, int cout, int mode, Block& blk) -> Status {
         ResW r; r.name = p; r.cin = cin; r.cout = cout; r.mode = mode;
         DPIR_TRY(load_gn(e, wm, p + ".in_layers.0", cin, &r.gn1));
-        DPIR_TRY(load_conv(e, wm, p + ".in_layers.2", cin, cout, 3, false, &r.conv1));
+        DPIR_TRY(load_conv(e, wm, p + ".in_layers.2", cin, cout, 3, false, &r.conv1, mode == 1));
         DPIR_TRY(load_gn(e, wm, p + ".out_layers.0", cout, &r.gn2));
         DPIR_TRY(load_conv(e, wm, p + ".out_layers.3", cout, cout, 3, false, &r.conv2));
         r.has_skip = cin != cout;
@@ -532,7 +543,8 @@ struct Fwd {
                conv7_emit_supported(B, r.cout, Ho, Wo) && fuse_arena && fuse_off + (size_t)B * 64 + (size_t)B * (r.cout / 128) <= fuse_cap &&
                (size_t)B * (2 * ((r.cout + 15) / 16)) * Ho * Wo * 16 < ((size_t)1 << 32);
     }
-    Status make_emit(const ResW& r, int Ho, int Wo, Conv6Emit* em, char** s16b, size_t* plane2) {
+    Status make_emit(const ResW& r, int Ho, int Wo, Conv6Emit* em, char** s16b, size_t* plane2, int cnt_per_img = 0) {
+        if (cnt_per_img <= 0) cnt_per_img = r.cout / 128;
         const bool x1 = e->precision == 2;
         const int C8 = 2 * ((r.cout + 15) / 16);
         *plane2 = (size_t)B * C8 * Ho * Wo * 16;
@@ -544,7 +556,7 @@ struct Fwd {
         em->acc = fuse_arena + fuse_off;
         fuse_off += (size_t)B * 64;                     // [B][32 groups][2]
         em->cnt = reinterpret_cast<unsigned*>(fuse_arena + fuse_off);
-        fuse_off += ((size_t)B * (r.cout / 128) + 1) / 2;
+        fuse_off += ((size_t)B * cnt_per_img + 1) / 2;
         em->range_ctr = e->range_ctr;
         // test hooks for the time-out path (tests/test_gpu_benched_batches.py): a short spin limit and an arrival count that cannot be reached
         static const int spin_env = getenv("DPIR_FUSE_SPIN_LIMIT") ? atoi(getenv("DPIR_FUSE_SPIN_LIMIT")) : 0;
@@ -556,6 +568,78 @@ struct Fwd {
         return Status{};
     }
 
+    // conv1 of an up-sampling ResBlock as four 2x2 phase convolutions of the source image (csrc/conv_up.hip): an f16 precision, no tape, the
+    // phase pack loaded, the shape supported, and enough workgroups that launch_conv6 would not have split K (its rule: 256).  Everything else
+    // -- source widths below 32, gradient mode, f32 -- keeps the route through the up-sampled planes.  DPIR_CONV_UP=0 restores that route everywhere.
+    bool conv_up_route(const ResW& r, const Act& in) const {
+        static const bool on = !(getenv("DPIR_CONV_UP") && atoi(getenv("DPIR_CONV_UP")) == 0);
+        return on && r.mode == 1 && !grad && e->precision != 0 && r.conv1.wup && !in.b && in.C() == r.gn1.c &&
+               !conv_up_supported(B, in.C(), r.cout, in.H, in.W, false) && conv_up_workgroups(B, r.cout, in.H, in.W) >= 256;
+    }
+    Status resblock_up(const ResW& r, const Act& in, Act* out, int Ho, int Wo, float* h1, size_t on) {
+        const bool x1 = e->precision == 2;
+        const int C = in.C(), C8 = 2 * (C / 16);
+        const size_t plane = (size_t)B * C8 * in.H * in.W * 16;
+        char* s16 = nullptr;
+        DPIR_TRY(ws.getT("act#s16", 2 * plane, &s16));
+        // GroupNorm + SiLU + split at the SOURCE resolution (mode 0), as the reference does before it up-samples
+        if (fuse_small && gn_act_small_supported(C, in.H, in.W, 0)) {
+            if (pending.partial && !is_pending(in.a)) DPIR_TRY(resolve());
+            GnActArgs ga;
+            ga.src = CatSrc{in.a, in.ca, nullptr, 0};
+            ga.pend = pending;
+            ga.gamma = r.gn1.gamma; ga.beta = r.gn1.beta;
+            ga.film = nullptr; ga.film_stride = film_stride; ga.film_off = 0; ga.fstep = fstep; ga.frows = film_rows;
+            ga.silu = true; ga.mode = 0; ga.B = B; ga.Hs = in.H; ga.Ws = in.W;
+            ga.hi = s16; ga.lo = x1 ? nullptr : s16 + plane; ga.range_ctr = e->range_ctr;
+            {
+                ProfScope ps(&e->prof, PC_ELEM);
+                DPIR_TRY(launch_gn_act_small(s, ga));
+            }
+            if (pending.partial) { fused.erase(pending.out); pending = PendingConv{}; }   // finished (and stored) by the fused prologue
+        } else {
+            DPIR_TRY(resolve());
+            float4* prm = nullptr;
+            DPIR_TRY(gn(r.gn1, in, r.name + "#gn1", -1, true, &prm));
+            ProfScope ps(&e->prof, PC_ELEM);
+            DPIR_TRY(launch_act_split(s, CatSrc{in.a, in.ca, nullptr, 0}, prm, 0, B, in.H, in.W, s16, x1 ? nullptr : s16 + plane, e->range_ctr));
+        }
+        ConvUpArgs a;
+        a.xhi = s16; a.xlo = s16 + plane; a.wup = r.conv1.wup; a.wup_scale = r.conv1.wup_scale; a.bias = r.conv1.bias;
+        a.B = B; a.Cin = C; a.Cout = r.cout; a.Hs = in.H; a.Ws = in.W; a.x1 = x1;
+        float* o = nullptr;
+        DPIR_TRY(ws.getT(r.name + "#out", on, &o));
+        // the hop obeys fuse_h1 (DPIR_FUSE_H1=0, time-out replay) and launch_conv6's whole-K rule of 384 workgroups, as conv7's
+        const bool hop = fuse_h1 && r.gn2.c == r.cout && r.conv2.w16 && r.conv2.ks == 3 && conv6_supported(Ho, Wo) && fuse_arena &&
+                         !conv_up_supported(B, C, r.cout, in.H, in.W, true, 384) && fuse_off + (size_t)B * 64 + (size_t)B * (r.cout / 64) <= fuse_cap;
+        if (hop) {
+            Conv6Emit em; char* s16b = nullptr; size_t plane2 = 0;
+            DPIR_TRY(make_emit(r, Ho, Wo, &em, &s16b, &plane2, r.cout / 64));
+            a.emit = &em; a.min_wg_hop = 384;
+            {
+                ProfScope ps(&e->prof, PC_CONV3);
+                DPIR_TRY(launch_conv_up(s, a));
+            }
+            DPIR_TRY(conv6_on_planes(r.conv2, s16b, plane2, in.a, 1, o, Ho, Wo));
+        } else {
+            const int slots = conv_up_stat_slots(in.H, in.W);
+            float2* st = nullptr;
+            DPIR_TRY(ws.getT("st#" + std::to_string(reinterpret_cast<uintptr_t>(h1)), (size_t)B * r.cout * slots, &st));
+            a.out = h1; a.stat = st;
+            {
+                ProfScope ps(&e->prof, PC_CONV3);
+                DPIR_TRY(launch_conv_up(s, a));
+            }
+            fused[h1] = FusedStat{st, slots, nullptr};
+            tap(r.name + "#h1", h1, on);
+            Act h1a; h1a.a = h1; h1a.ca = r.cout; h1a.H = Ho; h1a.W = Wo;
+            DPIR_TRY(gn_conv(r.gn2, r.name + "#gn2", r.film_off, r.conv2, h1a, 0, in.a, 1, o, Ho, Wo));
+        }
+        tap(r.name, o, on);
+        out->a = o; out->ca = r.cout; out->b = nullptr; out->cb = 0; out->H = Ho; out->W = Wo;
+        return Status{};
+    }
+
     Status resblock(const ResW& r, const Act& in, Act* out) {
         if (in.C() != r.cin) return invalid("resblock " + r.name + ": input channels mismatch");
         int Ho = r.mode == 1 ? in.H * 2 : (r.mode == 2 ? in.H / 2 : in.H);
@@ -564,6 +648,7 @@ struct Fwd {
         size_t on = (size_t)B * r.cout * Ho * Wo;
         float* h1 = nullptr;
         DPIR_TRY(ws.getT(r.name + "#h1", on, &h1));
+        if (conv_up_route(r, in)) return resblock_up(r, in, out, Ho, Wo, h1, on);
         Act h1a; h1a.a = h1; h1a.ca = r.cout; h1a.H = Ho; h1a.W = Wo;
         const float* res = nullptr; int res_mode = 0;
         // ResBlock with a 1x1 skip projection at a resolution the fused low-resolution prologue does not take: ONE pass over the

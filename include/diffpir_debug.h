@@ -74,6 +74,25 @@ typedef struct dpir_debug_conv9_desc {
     double ms_out;
 } dpir_debug_conv9_desc;
 int dpir_debug_conv9_layer(dpir_engine* e, dpir_debug_conv9_desc* d);
+/* conv1 of an up-sampling ResBlock (3x3 on the nearest-x2 up-sampled x) on host operands.  x[B][Cin][Hs][Ws] is at the SOURCE resolution, out
+ * [B][Cout][2 Hs][2 Ws]; prm: optional table [B][Cin][4] {mean, scale, shift, SiLU flag} applied by act_split at the source resolution.
+ *   route 0: conv_up (csrc/conv_up.hip: four 2x2 phase convolutions of the source image); route 1: the up-sampled planes + launch_conv6.
+ *   hop 0: out and stat_out[B][Cout][2] fp64 {sum, sum of squares} (the epilogue's slots, folded here).
+ *   hop 1: the first layer's epilogue writes the second layer's planes -- GroupNorm32(gamma2, beta2), optional FiLM rows film2[B][2 Cout], SiLU --
+ *     and the second layer (w2 [Cout2][Cout][3][3], bias2) runs through launch_conv6: out2[B][Cout2][2 Hs][2 Ws].
+ *   force_hop: the hop without the forward's lower bound of 384 workgroups (small test shapes).
+ * A refusal (shape, residual, gradient-mode engine, f32 precision) is a non-zero return code with dpir_last_error's text; ran_out = 1 conv_up,
+ * 2 conv_up's hop, 7 launch_conv6's route.  iters > 0: the whole route (act_split and every launch) is repeated that many times, ms_out = average. */
+typedef struct dpir_debug_conv_up_desc {
+    int32_t B, Cin, Cout, Hs, Ws, hop, force_hop, Cout2, route, reserved;
+    const float *x, *w, *bias, *res, *prm, *gamma2, *beta2, *film2, *w2, *bias2;
+    float* out; double* stat_out; float* out2;
+    int32_t ran_out, iters;
+    double ms_out;
+} dpir_debug_conv_up_desc;
+int dpir_debug_conv_up_layer(dpir_engine* e, dpir_debug_conv_up_desc* d);
+/* conv_up launches of this process so far: plain epilogue, fused hop (which route a forward took) */
+void dpir_debug_conv_up_counts(long long* plain, long long* hop);
 #ifdef __cplusplus
 }
 #endif
