@@ -90,6 +90,20 @@ class ConvUpDesc(C.Structure):
                 [(n, C.c_int32) for n in ("ran_out", "iters")] + [("ms_out", C.c_double)])
 
 
+class AttentionDesc(C.Structure):
+    """dpir_debug_attention_desc (include/diffpir_debug.h): the attention core, forward and backward, for dpir_debug_attention."""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "C", "T", "head_ch")] + [(n, C.c_void_p) for n in ("qkv", "dAtt", "out", "dqkv")] +
+                [("guard_bad_out", C.c_uint64)])
+
+
+class GroupNormDesc(C.Structure):
+    """dpir_debug_groupnorm_desc (include/diffpir_debug.h): one GroupNorm + FiLM + SiLU site, forward table and backward, for dpir_debug_groupnorm."""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "ca", "cb", "Hs", "Ws", "mode", "silu", "acc_a", "acc_b", "reserved")] +
+                [(n, C.c_void_p) for n in ("xa", "xb", "gamma", "beta", "film", "dA", "ga_init", "gb_init", "extra",
+                                           "prm_out", "stats_out", "ga_out", "gb_out")] +
+                [(n, C.c_int32) for n in ("ns_out", "reserved2")] + [("guard_bad_out", C.c_uint64)])
+
+
 PROF_CLASSES = 8
 PROF_NAMES = ["conv3x3", "conv1x1", "groupnorm_stats", "attention", "fft_prox", "elementwise", "unet_forward", "loop_graph"]
 
@@ -204,6 +218,10 @@ def load_debug():
     d.dpir_debug_conv_up_layer.restype = C.c_int
     d.dpir_debug_conv_up_counts.argtypes = [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     d.dpir_debug_conv_up_counts.restype = None
+    d.dpir_debug_attention.argtypes = [C.c_void_p, C.POINTER(AttentionDesc)]
+    d.dpir_debug_attention.restype = C.c_int
+    d.dpir_debug_groupnorm.argtypes = [C.c_void_p, C.POINTER(GroupNormDesc)]
+    d.dpir_debug_groupnorm.restype = C.c_int
     for n in ("dpir_debug_conv_bench", "dpir_debug_victim", "dpir_debug_victim_alu", "dpir_debug_victim_fft_pk", "dpir_debug_victim_fft_nopk",
               "dpir_debug_conv7_check"):
         getattr(d, n).restype = C.c_int

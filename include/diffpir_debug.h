@@ -93,6 +93,37 @@ typedef struct dpir_debug_conv_up_desc {
 int dpir_debug_conv_up_layer(dpir_engine* e, dpir_debug_conv_up_desc* d);
 /* conv_up launches of this process so far: plain epilogue, fused hop (which route a forward took) */
 void dpir_debug_conv_up_counts(long long* plain, long long* hop);
+/* The attention core (csrc/attn.hip) and its backward (csrc/grad.hip: launch_attention_bwd) on host operands, through the product's launchers.
+ *   qkv[B][3C][T] in the legacy order: heads first, then q | k | v inside each head (QKVAttentionLegacy); head_ch as the model's num_head_channels.
+ *   out[B][C][T] = launch_attention.  dAtt[B][C][T] (optional): dqkv[B][3C][T] = launch_attention_bwd, its T x T scratch allocated here.
+ * Every buffer a kernel writes has 256 floats of a fixed bit pattern in front of and behind it and starts out filled with that pattern (a NaN);
+ * guard_bad_out = guard words that changed, over all of them.  Operands are allocated at their exact size.  A launcher's refusal (head_ch != 64,
+ * C no multiple of 64, backward with T > 1024 -- for which no T x T scratch is allocated) is a non-zero return code with dpir_last_error's text. */
+typedef struct dpir_debug_attention_desc {
+    int32_t B, C, T, head_ch;
+    const float *qkv, *dAtt;
+    float *out, *dqkv;
+    uint64_t guard_bad_out;
+} dpir_debug_attention_desc;
+int dpir_debug_attention(dpir_engine* e, dpir_debug_attention_desc* d);
+/* One GroupNorm32 (+ FiLM, + SiLU) site on host operands, forward table and backward, through the product's launchers.
+ *   The source is the virtual concat of xa[B][ca][Hs][Ws] and xb[B][cb][Hs][Ws] (cb may be 0); gamma, beta [ca+cb]; film (optional) [B][2(ca+cb)]
+ *   = {scale, shift} rows; silu: the SiLU flag of the table.
+ *   Forward: launch_gn_stats per source, then launch_gn_prm, as Fwd::gn (csrc/unet.hip) chains them.  prm_out[B][C][4] = {mean, a, b, SiLU flag}
+ *   with GN+FiLM(x) = (x - mean) * a + b; stats_out[B][32][2] = {mean, rstd} per (image, group).
+ *   Backward (dA given): launch_gn_bwd on that same device table and statistics.  dA[B][C][Ho][Wo] is the gradient w.r.t. the activated and resampled
+ *   tensor: mode 0 Ho x Wo = Hs x Ws, 1 (nearest-up) 2Hs x 2Ws, 2 (2x2 mean) Hs/2 x Ws/2.  acc_a / acc_b: accumulate into the prior contents
+ *   ga_init / gb_init instead of overwriting; extra (optional, mode 0, cb = 0): a tensor shaped like xa added into ga before dx.
+ *   ga_out[B][ca][Hs][Ws], gb_out[B][cb][Hs][Ws]; ns_out = gn_bwd_parts(C, Hs, Ws), the partial workgroups per group.
+ * Guard words as for dpir_debug_attention.  A launcher's refusal (C no multiple of 32, mode 2 with an odd source) is a non-zero return code. */
+typedef struct dpir_debug_groupnorm_desc {
+    int32_t B, ca, cb, Hs, Ws, mode, silu, acc_a, acc_b, reserved;
+    const float *xa, *xb, *gamma, *beta, *film, *dA, *ga_init, *gb_init, *extra;
+    float *prm_out, *stats_out, *ga_out, *gb_out;
+    int32_t ns_out, reserved2;
+    uint64_t guard_bad_out;
+} dpir_debug_groupnorm_desc;
+int dpir_debug_groupnorm(dpir_engine* e, dpir_debug_groupnorm_desc* d);
 #ifdef __cplusplus
 }
 #endif
