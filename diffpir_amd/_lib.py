@@ -53,6 +53,13 @@ class InpaintRow(C.Structure):
                 ("mix_next", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ProgressDesc(C.Structure):
+    """dpir_progress_desc: the progressive strip armed for the next whole-loop call (dpir_set_progress)."""
+    _fields_ = [("panel_of_step_host", C.POINTER(C.c_int32)), ("n_entries", C.c_int32), ("n_panels", C.c_int32),
+                ("strip_f32", C.c_void_p), ("strip_u8", C.c_void_p), ("masked_f32", C.c_void_p), ("masked_u8", C.c_void_p),
+                ("minmax_dev", C.c_void_p)]
+
+
 class DpsCoef(C.Structure):
     _fields_ = [("pc1", C.c_float), ("pc2", C.c_float), ("min_log", C.c_float), ("max_log", C.c_float), ("sa_prev", C.c_float), ("s1m_prev", C.c_float)]
 
@@ -155,6 +162,9 @@ SIGNATURES = {
     "dpir_renoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Step), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "dpir_repaint_mix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "dpir_finalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "dpir_progress_snapshot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "dpir_set_progress": (C.c_int, [C.c_void_p, C.POINTER(ProgressDesc)]),
     "dpir_randn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
     "dpir_ewise": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_size_t]),
     "dpir_comm_unique_id": (C.c_int, [C.c_void_p]),

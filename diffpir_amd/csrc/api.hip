@@ -5,6 +5,7 @@
 #include "grad.h"
 #include "blur.h"
 #include "inpaint.h"
+#include "progress.h"
 #include <math.h>
 #include <string.h>
 #include <stdlib.h>
@@ -138,6 +139,34 @@ static Status check_shape(const char* entry, int B, int H, int W, int sf = 1) {
     return Status{};
 }
 
+// ---- progressive strip (dpir_set_progress): shared by the four whole-loop entries
+// The arming lasts for ONE public loop call: cleared when that call returns, whatever it returns (a re-run by run_with_hop_guard happens inside it).
+struct ProgressOneShot {
+    dpir_engine* e;
+    ~ProgressOneShot() { if (e) e->progress = dpir_engine::Progress{}; }
+};
+// before anything is launched: the armed table must describe this call
+static Status progress_check(dpir_engine* e, const char* entry, int n_entries, const dpir_loop_desc& d) {
+    const dpir_engine::Progress& pg = e->progress;
+    if (!pg.armed) return Status{};
+    if ((int)pg.panel_of.size() != n_entries)
+        return invalid(std::string(entry) + ": dpir_set_progress armed " + std::to_string(pg.panel_of.size()) + " entries for a loop of " + std::to_string(n_entries));
+    if ((pg.masked_f32 || pg.masked_u8) && (!d.mask_dev || !d.y_dev || d.sf != 1))
+        return invalid(std::string(entry) + ": a masked progress strip needs the mask and a full-size y (inpainting)");
+    if ((long long)pg.n_panels * d.W > 0x7fffffffLL) return invalid(std::string(entry) + ": n_panels * W is out of range");
+    return Status{};
+}
+// the panel of step / row idx, if it has one, from x as it stands on the stream now
+static Status progress_emit(dpir_engine* e, int idx, const float* x, const dpir_loop_desc& d) {
+    const dpir_engine::Progress& pg = e->progress;
+    if (!pg.armed || idx < 0 || pg.panel_of[idx] < 0) return Status{};
+    ProfScope ps(&e->prof, PC_ELEM);
+    const bool masked = pg.masked_f32 || pg.masked_u8;
+    ProgressArgs a{x, masked ? d.y_dev : nullptr, masked ? d.mask_dev : nullptr, pg.strip_f32, pg.strip_u8, pg.masked_f32, pg.masked_u8, pg.minmax,
+                   d.B, d.H, d.W, pg.panel_of[idx], pg.n_panels, e->cus};
+    return launch_progress_snapshot(e->stream, a);
+}
+
 extern "C" {
 
 int dpir_version(void) { return DPIR_ABI_VERSION; }
@@ -195,6 +224,7 @@ void dpir_destroy(dpir_engine* e) {
     prox_release(&e->loop_prox);
     (void)dpir_comm_destroy(e);
     if (e->range_ctr) (void)hipFree(e->range_ctr);
+    if (e->progress_premix) (void)hipFree(e->progress_premix);
     (void)hipStreamDestroy(e->stream);
     delete e;
 }
@@ -541,6 +571,38 @@ int dpir_finalize(dpir_engine* e, const float* x, float* of, uint8_t* ou, int B,
     API_TRY(e, launch_finalize(e->stream, x, of, ou, B, H * W));
     return DPIR_OK;
 }
+int dpir_progress_snapshot(dpir_engine* e, const float* x, const float* y, const uint8_t* mask, int panel, int n_panels, float* strip_f32,
+                           uint8_t* strip_u8, float* masked_f32, uint8_t* masked_u8, float* minmax, int B, int H, int W) {
+    if (!e || !x) return fail(e, invalid("dpir_progress_snapshot: null argument"));
+    API_TRY(e, check_shape("dpir_progress_snapshot", B, H, W));
+    if (n_panels < 1 || panel < 0 || panel >= n_panels)
+        return fail(e, invalid("dpir_progress_snapshot: panel must be in [0, n_panels) (got panel " + std::to_string(panel) + " of " + std::to_string(n_panels) + ")"));
+    if ((long long)n_panels * W > 0x7fffffffLL) return fail(e, invalid("dpir_progress_snapshot: n_panels * W is out of range"));
+    const bool masked = masked_f32 || masked_u8;
+    if (masked && (!y || !mask)) return fail(e, invalid("dpir_progress_snapshot: a masked output needs y and mask"));
+    if (reinterpret_cast<uintptr_t>(minmax) & 3u) return fail(e, invalid("dpir_progress_snapshot: minmax must be 4-byte aligned"));
+    (void)hipSetDevice(e->device);
+    ProfScope ps(&e->prof, PC_ELEM);
+    ProgressArgs a{x, masked ? y : nullptr, masked ? mask : nullptr, strip_f32, strip_u8, masked_f32, masked_u8, minmax, B, H, W, panel, n_panels, e->cus};
+    API_TRY(e, launch_progress_snapshot(e->stream, a));
+    return DPIR_OK;
+}
+int dpir_set_progress(dpir_engine* e, const dpir_progress_desc* desc) {
+    if (!e) return DPIR_ERR_INVALID;
+    e->progress = dpir_engine::Progress{};
+    if (!desc) return DPIR_OK;
+    if (!desc->panel_of_step_host || desc->n_entries < 1 || desc->n_panels < 1) return fail(e, invalid("dpir_set_progress: the panel table, n_entries and n_panels are required"));
+    if (reinterpret_cast<uintptr_t>(desc->minmax_dev) & 3u) return fail(e, invalid("dpir_set_progress: minmax_dev must be 4-byte aligned"));
+    for (int i = 0; i < desc->n_entries; ++i)
+        if (desc->panel_of_step_host[i] < -1 || desc->panel_of_step_host[i] >= desc->n_panels)
+            return fail(e, invalid("dpir_set_progress: entry " + std::to_string(i) + " is outside [-1, n_panels)"));
+    dpir_engine::Progress& pg = e->progress;
+    pg.panel_of.assign(desc->panel_of_step_host, desc->panel_of_step_host + desc->n_entries);
+    pg.n_panels = desc->n_panels;
+    pg.strip_f32 = desc->strip_f32; pg.strip_u8 = desc->strip_u8; pg.masked_f32 = desc->masked_f32; pg.masked_u8 = desc->masked_u8; pg.minmax = desc->minmax_dev;
+    pg.armed = true;
+    return DPIR_OK;
+}
 int dpir_randn(dpir_engine* e, float* out, uint64_t seed, uint64_t stream_id, int64_t image_offset, int B, int C, int H, int W) {
     if (!e || !out) return fail(e, invalid("dpir_randn: null argument"));
     API_TRY(e, check_shape("dpir_randn", B, H, W));
@@ -722,6 +784,7 @@ static int run_with_hop_guard(dpir_engine* e, const std::function<int()>& once) 
 }
 
 int dpir_run_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, int n_steps, float* out_f32, uint8_t* out_u8) {
+    ProgressOneShot one_shot{e};
     return run_with_hop_guard(e, [&] { return run_loop_once(e, dd, steps, n_steps, out_f32, out_u8); });
 }
 
@@ -769,6 +832,7 @@ static int run_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_st
     if (d.first_order && (d.generate_mode != 0 || (d.task != DPIR_TASK_SR_BLUR && d.task != DPIR_TASK_SR_CUBIC)))
         return fail(e, Status{DPIR_ERR_UNSUPPORTED, "the first-order data step (sub_1_analytic: false) is implemented for the DiffPIR mode of the "
                                                     "super-resolution tasks (the reference's deblurring operator raises at main_ddpir.py:302)"});
+    API_TRY(e, progress_check(e, "dpir_run_loop", n_steps, d));
     const int B = d.B, H = d.H, W = d.W;
     const size_t total = (size_t)B * 3 * H * W;
     range_clear(e);
@@ -826,7 +890,10 @@ static int run_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_st
     }
     API_TRY(e, loop_init(e, d, b, &prox));
     hipGraphExec_t g_step = nullptr, g_last = nullptr;
+    // a progress panel shows x after its step (the repaint mix of this loop opens the NEXT step): taken when the next iteration begins, or before finalize,
+    // so that a step skipped by skip_dead_final_eval yields its panel too
     for (int i = 0; i < n_steps; ++i) {
+        API_TRY(e, progress_emit(e, i - 1, b.x, d));
         const bool last = steps[i].last != 0;
         if (last && d.skip_dead_final_eval) continue;
         API_HIP(e, hipMemcpyAsync(b.cur, b.steps_dev + i, sizeof(StepDev), hipMemcpyDeviceToDevice, e->stream));
@@ -849,6 +916,7 @@ static int run_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_st
         ProfScope ps(&e->prof, PC_LOOP);
         API_HIP(e, hipGraphLaunch(g, e->stream));
     }
+    API_TRY(e, progress_emit(e, n_steps - 1, b.x, d));
     {
         ProfScope ps(&e->prof, PC_ELEM);
         API_TRY(e, launch_finalize(e->stream, b.x, out_f32, out_u8, B, H * W));
@@ -860,7 +928,7 @@ static int run_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_st
 static InpaintRowDev row_dev_of(const dpir_inpaint_row& r, int s) {
     InpaintRowDev o{};
     o.st = StepDev{r.t, r.last, r.pos, 0, r.c1, r.c2, r.tau, r.sa_t, r.s1m_t, r.sa_p, r.k1, r.q, r.es, r.k2};
-    o.s = s; o.back = r.back; o.mix_next = r.mix_next; o.pad = 0;
+    o.s = s; o.back = r.back; o.mix_next = r.mix_next; o.emit = 0;
     o.sae = r.sae; o.sb = r.sb; o.sa_n = r.sa_n; o.s1m_n = r.s1m_n;
     return o;
 }
@@ -925,6 +993,19 @@ static int run_inpaint_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const
     } else if (d.noise_init_dev || d.noise_n1_dev || d.noise_rp_dev || noise_back) {
         return fail(e, invalid("dpir_run_inpaint_loop: host noise needs noise_n2_dev (all null selects device noise)"));
     }
+    API_TRY(e, progress_check(e, "dpir_run_inpaint_loop", n_rows, d));
+    // generate_mode repaint: the fused pass mixes the next sub-step's known region into x before x ever reaches memory, so the rows that own a
+    // panel also write the pre-mix x to a scratch image, which the snapshot then reads.  (The alternative, forming the panel inside the fused pass,
+    // would put the strip layout, the uint8 / masked outputs and the min/max reduction into that kernel a second time.)
+    const dpir_engine::Progress& pg = e->progress;
+    const bool premix = pg.armed && d.generate_mode == 1;
+    if (premix && e->progress_premix_bytes < total * sizeof(float)) {
+        API_HIP(e, hipStreamSynchronize(e->stream));
+        if (e->progress_premix) (void)hipFree(e->progress_premix);
+        e->progress_premix = nullptr; e->progress_premix_bytes = 0;
+        API_HIP(e, hipMalloc((void**)&e->progress_premix, total * sizeof(float)));
+        e->progress_premix_bytes = total * sizeof(float);
+    }
     range_clear(e);
     LoopBufs b{};
     InpaintRowDev *rows_dev = nullptr, *cur = nullptr;
@@ -941,8 +1022,9 @@ static int run_inpaint_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const
     if (hoist_film) API_TRY(e, e->ws.getT("loop#film", (size_t)n_pos * e->net.film_rows, &b.film));
     {
         std::vector<InpaintRowDev> hr(n_rows);
-        for (int r = 0; r < n_rows; ++r) hr[r] = row_dev_of(rows[r], r);
-        InpaintLoopDev hl{d.y_dev, d.mask_dev, d.noise_n1_dev, d.noise_n2_dev, noise_back, d.noise_rp_dev, (unsigned long long)d.seed, (long long)d.image_offset};
+        for (int r = 0; r < n_rows; ++r) { hr[r] = row_dev_of(rows[r], r); hr[r].emit = premix && pg.panel_of[r] >= 0; }
+        InpaintLoopDev hl{d.y_dev, d.mask_dev, d.noise_n1_dev, d.noise_n2_dev, noise_back, d.noise_rp_dev, (unsigned long long)d.seed, (long long)d.image_offset,
+                          premix ? e->progress_premix : nullptr};
         API_HIP(e, hipMemcpyAsync(rows_dev, hr.data(), sizeof(InpaintRowDev) * n_rows, hipMemcpyHostToDevice, e->stream));
         API_HIP(e, hipMemcpyAsync(lp, &hl, sizeof(hl), hipMemcpyHostToDevice, e->stream));
         API_HIP(e, hipStreamSynchronize(e->stream));
@@ -980,7 +1062,13 @@ static int run_inpaint_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const
         return data_pass();
     };
     hipGraphExec_t g = nullptr;
+    // the panel of row r - 1 when row r begins (or before finalize): a row skipped as dead yields its panel too.  Repaint: a row that mixed the
+    // next one in left its own x in the scratch image
+    auto emit = [&](int r) -> Status {
+        return progress_emit(e, r, r >= 0 && premix && rows[r].mix_next ? e->progress_premix : b.x, d);
+    };
     for (int r = 0; r < n_rows; ++r) {
+        API_TRY(e, emit(r - 1));
         const bool last = rows[r].last != 0;
         const bool dead = last && d.skip_dead_final_eval;
         if (dead && !(d.generate_mode == 1 && rows[r].mix_next)) continue;
@@ -1001,6 +1089,7 @@ static int run_inpaint_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const
         ProfScope ps(&e->prof, PC_LOOP);
         API_HIP(e, hipGraphLaunch(g, s));
     }
+    API_TRY(e, emit(n_rows - 1));
     {
         ProfScope ps(&e->prof, PC_ELEM);
         API_TRY(e, launch_finalize(s, b.x, out_f32, out_u8, B, H * W));
@@ -1010,6 +1099,7 @@ static int run_inpaint_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const
 
 int dpir_run_inpaint_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_inpaint_row* rows, int n_rows, const float* noise_back,
                           float* out_f32, uint8_t* out_u8) {
+    ProgressOneShot one_shot{e};
     return run_with_hop_guard(e, [&] { return run_inpaint_loop_once(e, dd, rows, n_rows, noise_back, out_f32, out_u8); });
 }
 
@@ -1147,6 +1237,7 @@ int dpir_grad_and_value(dpir_engine* e, int through_network, const float* x_hat_
 int dpir_run_dps_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, const dpir_dps_coef* coefs, int n_steps,
                       int variant, float lambda_, const float* noise_ps_dev, const float* noise_yt_dev, float step_scale, float* out_f32,
                       uint8_t* out_u8) {
+    ProgressOneShot one_shot{e};
     if (!e || !dd || !steps || !coefs || n_steps <= 0) return fail(e, invalid("dpir_run_dps_loop: null argument"));
     if (variant != 0 && variant != 1) return fail(e, invalid("dpir_run_dps_loop: variant must be 0 (DPS_y0) or 1 (DPS_yt)"));
     (void)hipSetDevice(e->device);
@@ -1158,6 +1249,7 @@ int dpir_run_dps_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step*
                                                     "main_ddpir.py:302 and its inpainting branch never defines xt)"});
     if (d.B <= 0 || d.H <= 0 || d.W <= 0 || d.sf < 1 || d.H % d.sf || d.W % d.sf || !d.y_dev) return fail(e, invalid("dpir_run_dps_loop: bad shape"));
     if ((e->net.desc.num_classes > 0) != (d.labels_host != nullptr)) return fail(e, invalid("labels iff class-conditional model"));
+    API_TRY(e, progress_check(e, "dpir_run_dps_loop", n_steps, d));
     const int B = d.B, H = d.H, W = d.W, sf = d.sf, h = H / sf, w = W / sf, oc = e->net.desc.out_channels;
     const size_t total = (size_t)B * 3 * H * W, small = (size_t)B * 3 * h * w;
     hipStream_t s = e->stream;
@@ -1182,6 +1274,7 @@ int dpir_run_dps_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step*
         API_TRY(e, launch_init_x(s, b.init_src, nullptr, n0, d.sa_start, d.s1m_start, b.x, total));
     }
     for (int i = 0; i < n_steps; ++i) {
+        API_TRY(e, progress_emit(e, i - 1, b.x, d));     // the panel of step i - 1: x after its update
         const dpir_step& st = steps[i];
         if (st.last && d.skip_dead_final_eval) continue;
         std::vector<int64_t> tv(B, st.t);
@@ -1217,6 +1310,7 @@ int dpir_run_dps_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step*
         API_TRY(e, dps_grad_through_network(e, gup, normv, &direct, &dxn));
         API_TRY(e, launch_dps_update(s, xprev, direct, dxn, step_scale, b.x, nullptr, total));
     }
+    API_TRY(e, progress_emit(e, n_steps - 1, b.x, d));
     {
         ProfScope ps(&e->prof, PC_ELEM);
         API_TRY(e, launch_finalize(s, b.x, out_f32, out_u8, B, H * W));
@@ -1297,6 +1391,7 @@ int dpir_grad_and_value_blur(dpir_engine* e, int through_network, const float* x
 
 int dpir_run_deblur_grad_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, const dpir_dps_coef* coefs, int n_steps, int variant,
                               float lambda_, const float* noise_ps_dev, const float* noise_yt_dev, float* out_f32, uint8_t* out_u8) {
+    ProgressOneShot one_shot{e};
     if (!e || !dd || !steps || n_steps <= 0) return fail(e, invalid("dpir_run_deblur_grad_loop: null argument"));
     if (variant < 0 || variant > 2) return fail(e, invalid("dpir_run_deblur_grad_loop: variant must be 0 (DPS_y0), 1 (DPS_yt) or 2 (first-order data step)"));
     if (variant != 2 && !coefs) return fail(e, invalid("dpir_run_deblur_grad_loop: the DPS variants need the p_sample coefficients"));
@@ -1308,6 +1403,7 @@ int dpir_run_deblur_grad_loop(dpir_engine* e, const dpir_loop_desc* dd, const dp
     if (!d.y_dev || !d.k_dev) return fail(e, invalid("dpir_run_deblur_grad_loop: y and the PSF are required"));
     API_TRY(e, blur_check("dpir_run_deblur_grad_loop", d.kh, d.kw, d.B, d.H, d.W));
     if ((e->net.desc.num_classes > 0) != (d.labels_host != nullptr)) return fail(e, invalid("labels iff class-conditional model"));
+    API_TRY(e, progress_check(e, "dpir_run_deblur_grad_loop", n_steps, d));
     const int B = d.B, H = d.H, W = d.W, K = d.kh, oc = e->net.desc.out_channels;
     const size_t total = (size_t)B * 3 * H * W;
     bool with_n1 = false;
@@ -1335,6 +1431,7 @@ int dpir_run_deblur_grad_loop(dpir_engine* e, const dpir_loop_desc* dd, const dp
         API_TRY(e, launch_init_x(s, d.y_dev, nullptr, n0, d.sa_start, d.s1m_start, b.x, total));
     }
     for (int i = 0; i < n_steps; ++i) {
+        API_TRY(e, progress_emit(e, i - 1, b.x, d));     // the panel of step i - 1: x after its update
         const dpir_step& st = steps[i];
         if (st.last && d.skip_dead_final_eval) continue;
         std::vector<int64_t> tv(B, st.t);
@@ -1384,6 +1481,7 @@ int dpir_run_deblur_grad_loop(dpir_engine* e, const dpir_loop_desc* dd, const dp
         API_TRY(e, dps_grad_through_network(e, gup, normv, &direct, &dxn, true));
         API_TRY(e, launch_dps_update(s, xprev, direct, dxn, 1.f, b.x, nullptr, total));
     }
+    API_TRY(e, progress_emit(e, n_steps - 1, b.x, d));
     {
         ProfScope ps(&e->prof, PC_ELEM);
         API_TRY(e, launch_finalize(s, b.x, out_f32, out_u8, B, H * W));

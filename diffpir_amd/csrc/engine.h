@@ -138,6 +138,15 @@ struct dpir_engine {
     unsigned long long enqueue_serial() const { return prof.serial + copy_serial; }
     unsigned long long copy_serial = 0;
     void arm_replay(std::function<int()> fn) { ++fwd_since_sync; replay_last = std::move(fn); replay_serial = enqueue_serial(); }
+    // dpir_set_progress: the progressive strip armed for the NEXT loop call only (cleared when that call returns).  panel_of holds one panel
+    // index or -1 per step / row.  premix: the engine's own scratch [B,3,H,W] for the fused inpainting step's pre-mix emit -- a plain
+    // allocation, NOT a workspace buffer: growing the workspace would bump its generation and orphan the captured step graphs.
+    struct Progress {
+        bool armed = false;
+        std::vector<int> panel_of; int n_panels = 0;
+        float* strip_f32 = nullptr; uint8_t* strip_u8 = nullptr; float* masked_f32 = nullptr; uint8_t* masked_u8 = nullptr; float* minmax = nullptr;
+    } progress;
+    float* progress_premix = nullptr; size_t progress_premix_bytes = 0;
     void* comm = nullptr; int comm_world = 1, comm_rank = 0;     // RCCL communicator (comm.cpp), or null
 
     dpir::Status resizer(int in_len, int sf, dpir::ResizerTab* out);

@@ -14,7 +14,7 @@ struct InpaintRowDev {
     int s;                  // sub-step ordinal: host-noise slice and the Philox stream offset (draw + 4 s; set-back 2^32 + s)
     int back;               // 1: set back to t_i after the re-noise (u < U - 1, main_ddpir_inpainting.py:296-300)
     int mix_next;           // 1: apply the NEXT sub-step's repaint mix (:244-246) at the end of this pass
-    int pad;
+    int emit;               // 1 (armed progress panel, loop only): write x as it stands BEFORE the next sub-step's mix to InpaintLoopDev::premix
     float sae, sb;          // set-back pair: sa[t_i] / sa[t_im1], sqrt(s1m[t_i]^2 - sae^2 s1m[t_im1]^2)
     float sa_n, s1m_n;      // sa / s1m at the next sub-step's timestep (repaint mix)
 };
@@ -25,6 +25,7 @@ struct InpaintLoopDev {
     const float* y; const uint8_t* mask;
     const float* n1; const float* n2; const float* nback; const float* nrp;
     unsigned long long seed; long long image_offset;
+    float* premix;          // [B,3,H,W] scratch for rows with `emit`, or null (no progress strip armed)
 };
 
 struct InpaintStepArgs {
@@ -37,6 +38,8 @@ struct InpaintStepArgs {
     const float *n1, *n2, *nback, *nrp_next;    // host noise of THIS call (plug entry), or null with lp (loop: lp's tensors + row->s slices)
     unsigned long long seed; long long image_offset;
     float* x0_out;              // optional: the clamped x0 prediction, before the prox
+    float* premix_out;          // optional: x of this sub-step before the next sub-step's repaint mix is applied to it (what a progress panel shows,
+                                // main_ddpir_inpainting.py:303 precedes :245 of the next iteration); with lp: lp->premix on rows with `emit`
     const InpaintRowDev* row;   // device (the loop: the fixed-address current row), or null -> row_val
     InpaintRowDev row_val;      // the row by value in the kernel arguments (plug entry: no copy, no synchronisation)
     const InpaintLoopDev* lp;   // device or null

@@ -15,7 +15,7 @@ namespace dpir {
 struct InpaintFlags { bool last, prox, with_n1, back, mix; };
 
 __device__ __forceinline__ float inpaint_elem(float x, float eps, float yv, float m, float n1, float n2, float nb, float nr, const InpaintRowDev& r,
-                                              float g, const InpaintFlags& f, float* x0_out) {
+                                              float g, const InpaintFlags& f, float* x0_out, float* premix) {
     if (!f.last) {
         const StepDev& c = r.st;
         float v = c.c1 * x - c.c2 * eps;                         // xstart_kernel
@@ -38,6 +38,7 @@ __device__ __forceinline__ float inpaint_elem(float x, float eps, float yv, floa
             x = p + s;
         }
     }
+    *premix = x;
     if (f.mix) {                                                 // repaint_mix_kernel with the next sub-step's coefficients
         float known = r.sa_n * (2.0f * yv - 1.0f) + r.s1m_n * nr;
         x = known * m + (1.0f - m) * x;
@@ -54,8 +55,10 @@ __global__ __launch_bounds__(256) void inpaint_step_kernel(InpaintStepArgs a, si
     const float* y = a.y; const uint8_t* mask = a.mask;
     const float *n1 = a.n1, *n2 = a.n2, *nb = a.nback, *nr = a.nrp_next;
     unsigned long long seed = a.seed; long long image_offset = a.image_offset;
+    float* pm = a.premix_out;
     if (a.lp) {
         const InpaintLoopDev l = *a.lp;
+        pm = r.emit ? l.premix : nullptr;
         y = l.y; mask = l.mask; seed = l.seed; image_offset = l.image_offset;
         if (!a.device_noise) {
             const size_t slice = (size_t)r.s * a.B * P;
@@ -70,6 +73,7 @@ __global__ __launch_bounds__(256) void inpaint_step_kernel(InpaintStepArgs a, si
     f.back = !f.last && r.back != 0;
     f.mix = a.mode == 1 && r.mix_next != 0;
     if (f.last && !f.mix) return;
+    if (!f.mix) pm = nullptr;       // nothing is mixed in: x itself is what the panel shows
     const bool dev = a.device_noise != 0;
     const uint64_t s4 = 4ull * (uint64_t)r.s;
     // images along blockIdx.y, an image's groups along x by grid stride: no integer division per group (q < 2^29 by check_shape)
@@ -124,15 +128,17 @@ __global__ __launch_bounds__(256) void inpaint_step_kernel(InpaintStepArgs a, si
             if (f.back) philox_normal4(seed, (1ull << 32) + (uint64_t)r.s, img, j, zb);
             if (f.mix) philox_normal4(seed, 3ull + s4 + 4ull, img, j, zr);
         }
-        float ov[4], x0v[4];
+        float ov[4], x0v[4], pv[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) ov[e] = inpaint_elem(xv[e], ev[e], yv[e], mv[e], z1[e], z2[e], zb[e], zr[e], r, a.guidance, f, &x0v[e]);
+        for (int e = 0; e < 4; ++e) ov[e] = inpaint_elem(xv[e], ev[e], yv[e], mv[e], z1[e], z2[e], zb[e], zr[e], r, a.guidance, f, &x0v[e], &pv[e]);
         if (VEC) {
             *reinterpret_cast<float4*>(a.x + base) = make_float4(ov[0], ov[1], ov[2], ov[3]);
+            if (pm) *reinterpret_cast<float4*>(pm + base) = make_float4(pv[0], pv[1], pv[2], pv[3]);
             if (a.x0_out && !f.last) *reinterpret_cast<float4*>(a.x0_out + base) = make_float4(x0v[0], x0v[1], x0v[2], x0v[3]);
         } else {
             for (int e = 0; e < cnt; ++e) {
                 a.x[base + e] = ov[e];
+                if (pm) pm[base + e] = pv[e];
                 if (a.x0_out && !f.last) a.x0_out[base + e] = x0v[e];
             }
         }
@@ -143,7 +149,7 @@ static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 Status launch_inpaint_step(hipStream_t s, const InpaintStepArgs& a) {
     const size_t P = (size_t)3 * a.HW, q = (P + 3) / 4;
-    bool vec = !a.scalar_only && a.HW % 4 == 0 && aligned16(a.x) && aligned16(a.eps) && aligned16(a.x0_out);
+    bool vec = !a.scalar_only && a.HW % 4 == 0 && aligned16(a.x) && aligned16(a.eps) && aligned16(a.x0_out) && aligned16(a.premix_out);
     if (!a.lp) vec = vec && aligned16(a.y) && (reinterpret_cast<uintptr_t>(a.mask) & 3u) == 0 && aligned16(a.n1) && aligned16(a.n2) && aligned16(a.nback) &&
                      aligned16(a.nrp_next);
     // memory-bound: no more workgroups than the device keeps resident (8 x 256 threads per CU), the rest by grid stride

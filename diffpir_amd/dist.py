@@ -337,7 +337,7 @@ def check_dps_sharding(engine, cfg, n_images: int, world: int):
 
 def restore_sharded(engine, cfg, y, k=None, mask=None, labels=None, *, rank: int, world: int, image_offset: int = 0, seed: int = 0,
                     use_graph: bool = True, noise_source: str = "device", host_noise=None, cache: dict = None,
-                    skip_dead_final_eval: bool = False):
+                    skip_dead_final_eval: bool = False, progress=None):
     """One GLOBAL batch restored by `world` ranks: rank r runs images [lo, hi) of the batch on its own GPU (its own engine,
     its own replayed graph, no collective inside the loop) and ONE all-gather of the uint8 results ends the batch
     (SURVEY.md 8e).  y / k / mask / labels are the global batch (numpy, host); every rank slices its block.
@@ -347,6 +347,9 @@ def restore_sharded(engine, cfg, y, k=None, mask=None, labels=None, *, rank: int
     by restore.draw_host_noise for the global shape; each rank uploads its image slice.
     Returns (uint8 [n_images, H, W, 3] on every rank as an engine-owned DeviceArray, local fp32 DeviceArray)."""
     from . import restore
+    if progress is not None:
+        raise NotImplementedError("restore_sharded: a progressive strip (progress=) is not gathered across ranks; run restore.restore_batch "
+                                  "on one GPU for save_progressive / log_process")
     n = y.shape[0]
     check_dps_sharding(engine, cfg, n, world)
     lo, hi = shard_range(n, rank, world)

@@ -269,6 +269,15 @@ class Engine:
     def unet_flops(self, H, W, cls: int = -1) -> float:
         return float(self.lib.dpir_unet_flops_class(self.h, H, W, cls))
 
+    def progress_snapshot(self, x, panel: int, n_panels: int, strip_f32=None, strip_u8=None, y=None, mask=None, masked_f32=None, masked_u8=None,
+                          minmax=None):
+        """One panel of the progressive strip from x [B,3,H,W] (dpir_progress_snapshot): x/2+.5 into columns [panel W, (panel+1) W) of
+        strip_f32 [B,3,H,n_panels W] / strip_u8 [B,H,n_panels W,3], the masked blend y mask + (1 - mask)(x/2+.5) likewise, and the
+        per-image (max, min) into minmax [n_panels,B,2].  Every output is optional."""
+        B, _, H, W = x.shape
+        self._check(self.lib.dpir_progress_snapshot(self.h, _ptr(x), _ptr(y), _ptr(mask), int(panel), int(n_panels), _ptr(strip_f32), _ptr(strip_u8),
+                                                    _ptr(masked_f32), _ptr(masked_u8), _ptr(minmax), B, H, W))
+
     def graph_cache_size(self) -> int:
         return int(self.lib.dpir_graph_cache_size(self.h))
 

@@ -195,6 +195,70 @@ def load_mask_image(config, H, W):
     return np.ascontiguousarray((m != 0).astype(np.uint8).transpose(2, 0, 1)[None])
 
 
+def progress_options(config):
+    """(save_progressive, save_progressive_mask, log_process): the reference's three switches (main_ddpir_deblur.py:46, 53;
+    main_ddpir_inpainting.py:48-49, 63), all off unless the YAML says otherwise.  log_process logs inside the `if save_progressive` block
+    (main_ddpir_deblur.py:361-368), so it needs save_progressive; save_progressive_mask is read by the standalone inpainting program only, for
+    generate_mode repaint and DiffPIR (main_ddpir_inpainting.py:352, 364, 370)."""
+    save = bool(config.get("save_progressive", False))
+    driver = config.get("driver", "main_ddpir")
+    mask = save and bool(config.get("save_progressive_mask", False)) and driver == "main_ddpir_inpainting" and config.task == "inpaint" \
+        and config.generate_mode in ("repaint", "DiffPIR")
+    return save, mask, save and bool(config.get("log_process", False))
+
+
+def result_dir(config):
+    """E_path of main_ddpir.py:146-158: <results>/<result_name>, under `cwd`."""
+    name = (f"{config.testset_name}_{config.task}_{config.generate_mode}_{config.model_name}_sigma{config.noise_level_img}_NFE{config.iter_num}"
+            f"_eta{config.eta}_zeta{config.zeta}_lambda{config.lambda_}")
+    if config.task == "sr":
+        name += f"_{config.sr_mode}{config.sf}"
+    elif config.task == "deblur":
+        name += f"_blurmode_{config.blur_mode}"
+    else:
+        name += f"_mask_type_{config.get('mask_type', 'loaded')}"
+    return os.path.join(config.get("cwd", "") or "", config.get("results", "results"), name)
+
+
+def progress_file_names(config, img_name, ext, lambda_, current_time, psnr):
+    """(process strip, masked process strip) file names: main_ddpir_inpainting.py:359, 371 under driver main_ddpir_inpainting,
+    main_ddpir_deblur.py:406 (= main_ddpir_sisr.py:432) under the other two."""
+    if config.get("driver", "main_ddpir") == "main_ddpir_inpainting":
+        return (img_name + "_process_lambda_{:.3f}_{}{}".format(lambda_, current_time, ext),
+                img_name + "_process_mask_lambda_{:.3f}_{}{}".format(lambda_, current_time, ext))
+    return (img_name + "_sigma_{:.3f}_process_lambda_{:.3f}_{}_psnr_{:.4f}{}".format(config.noise_level_img, lambda_, current_time, psnr, ext), None)
+
+
+def write_png(path, rgb_u8):
+    """uint8 [H,W,3] -> PNG through PIL (cv2, the reference's writer, is not a dependency)."""
+    from PIL import Image
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    Image.fromarray(np.ascontiguousarray(rgb_u8)).save(path)
+
+
+def emit_progress(config, pg, names, lambda_, psnrs, current_time=None, writer=write_png, logger=None):
+    """What the reference does with progress_img after one image (main_ddpir_deblur.py:367-368, 400-406; main_ddpir_inpainting.py:310-311,
+    349-371), for every image of a batch: the log_process lines, one "process" PNG and, when asked for, the masked one.  The strips are the
+    engine's uint8 conversion (clamp, x 255, round half to even) of the float panels.  Returns the paths written."""
+    save, mask, log_p = progress_options(config)
+    logger = logger or log
+    current_time = current_time or time.strftime("%Y_%m_%d_%H_%M_%S")
+    out_dir, paths = result_dir(config), []
+    for b, full in enumerate(names):
+        img_name, ext = os.path.splitext(full)
+        if log_p:
+            for line in pg.log_lines(b):
+                logger.info(line)
+        if save:
+            plain, masked = progress_file_names(config, img_name, ext, lambda_, current_time, float(psnrs[b]))
+            paths.append(os.path.join(out_dir, plain))
+            writer(paths[-1], pg.strip_u8[b])
+            if mask:
+                paths.append(os.path.join(out_dir, masked))
+                writer(paths[-1], pg.masked_u8[b])
+    return paths
+
+
 def main(argv=None):
     import sys
     ap = argparse.ArgumentParser()
@@ -299,6 +363,10 @@ def main(argv=None):
                 nf = lambda shape: torch.randn(tuple(shape), generator=host_gen).numpy()
                 full = restore.draw_host_noise(nf, steps, (n_b, 3, H, W), cfg.eta != 0, repaint=cfg.generate_mode == "repaint")
                 drawn = [None if a is None else (np.ascontiguousarray(a[lo:hi]) if a.ndim == 4 else np.ascontiguousarray(a[:, lo:hi])) for a in full]
+            save_p, mask_p, _ = progress_options(config)
+            if save_p and world > 1:
+                raise NotImplementedError("save_progressive / log_process on several GPUs: the strips are not gathered across ranks (num_gpus: 1)")
+            pg = restore.Progress(u8=True, masked=mask_p) if save_p else None
             if hi > lo:
                 sl = slice(lo, hi)
                 # degradation on the device (dpir_degrade): blur / down-sampling / masking + AWGN, device Philox noise keyed by the
@@ -308,8 +376,10 @@ def main(argv=None):
                                      image_offset=i0 + lo)
                 out_f32 = restore.restore_batch(eng, cfg, y, k=ops.get("k"), mask=None if dps_mode else ops.get("mask"), noise_source=noise,
                                                 predrawn=drawn, noise_fn=dps_nf, seed=config.seed, image_offset=i0 + lo, use_graph=use_graph and not deb_grad, out_u8=u8_local, _cache=cache,
-                                                skip_dead_final_eval=bool(config.get("engine_skip_dead_final_eval", False)))
+                                                skip_dead_final_eval=bool(config.get("engine_skip_dead_final_eval", False)), progress=pg)
                 psnr_i, psnr_y_i = dgr.metrics(eng, out_f32, ops["gt"])            # dpir_metrics: per-image PSNR / PSNR-Y
+                if pg is not None:
+                    emit_progress(config, pg, names[i0 + lo:i0 + hi], lambda_, psnr_i)
                 per_img = np.stack([psnr_i, psnr_y_i], 1).astype(np.float64)
             u8 = ddist.all_gather_results(u8_local, n_b, rank, world, engine=eng)           # the one collective of the path
             allm = ddist.all_gather_results(per_img.reshape(-1, 2), n_b, rank, world, engine=eng)      # per-image PSNR rows (host numpy)

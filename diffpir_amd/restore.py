@@ -5,7 +5,7 @@ Two entry points with identical results:
                               into dpir_run_loop (optionally a cached hipGraph) does init -> N x
                               (UNet -> prox -> re-noise) -> finalize without returning to Python.
   * restore_batch_stepwise -- the reference's loop body, line for line, calling the drop-in plugs
-                              (utils_model.model_fn, utils_sisr.pre_calculate/data_solution, ...).
+                              (utils_model.model_fn, utils_sisr.pre_calculate, dpir_prox_fft_apply, ...).
                               Exists to show (and test) that the reference loop runs unmodified
                               against the engine's operator surface.
 Noise: noise_source="host" draws N(0,1) on the host in the reference's order (SURVEY.md 8 a-R: init,
@@ -125,6 +125,117 @@ DRIVERS = ("main_ddpir", "main_ddpir_deblur", "main_ddpir_inpainting")
 GENERATE_MODES = {"DiffPIR": 0, "repaint": 1, "vanilla": 2, "DPS_y0": 3, "DPS_yt": 4}
 
 
+@dataclass
+class Progress:
+    """The progressive "process" strip of one restoration call (the reference's save_progressive / log_process / save_progressive_mask:
+    main_ddpir_deblur.py:359-371, 400-406, main_ddpir_inpainting.py:302-313, 349-371).  Request: u8 (also the uint8 strips), masked (also the
+    strips with the known pixels pasted back; needs a mask).  After the call: panels = [(seq value, t_i), ...] in strip order; strip_f32
+    [B,3,H,P W] = x/2+.5 of each panel side by side, strip_u8 [B,H,P W,3]; masked_f32 / masked_u8 in the same layouts; minmax [P,B,2] =
+    (np.max, np.min) of each image's panel -- numpy arrays on the host."""
+    u8: bool = True
+    masked: bool = False
+    panels: list = None
+    strip_f32: np.ndarray = None
+    strip_u8: np.ndarray = None
+    masked_f32: np.ndarray = None
+    masked_u8: np.ndarray = None
+    minmax: np.ndarray = None
+
+    def log_lines(self, b: int):
+        """log_process: one line per panel for image b, the reference's format (main_ddpir_deblur.py:368, main_ddpir_inpainting.py:311)."""
+        return ["{:>4d}, steps: {:>4d}, np.max(x_show): {:.4f}, np.min(x_show): {:.4f}".format(s, t, self.minmax[p, b, 0], self.minmax[p, b, 1])
+                for p, (s, t) in enumerate(self.panels)]
+
+
+def progress_table(cfg: LoopConfig, entries):
+    """(panel index or -1 for every step / row dict of build_steps / build_inpaint_rows, [(seq value, t_i) of each panel]).  An inpainting
+    row group (the iter_num_U sub-steps of one timestep) keeps its panel on its last row: the snapshot follows the whole `for u` loop."""
+    from .schedule import make_seq, progress_panels
+    seq = make_seq(cfg.num_train_timesteps, cfg.iter_num, cfg.skip_type)
+    visited = []
+    for st in entries:
+        if not visited or visited[-1] != st["seq_i"]:
+            visited.append(st["seq_i"])
+    of_i = dict(zip(visited, progress_panels(seq, visited, cfg.driver)))
+    table, panels = [], []
+    for j, st in enumerate(entries):
+        closes = j + 1 == len(entries) or entries[j + 1]["seq_i"] != st["seq_i"]
+        p = of_i[st["seq_i"]] if closes else -1
+        table.append(p)
+        if p >= 0:
+            panels.append((int(st["seq"]), int(st["t"])))
+    return table, panels
+
+
+class _ArmedProgress:
+    """Allocates the strips, arms the next whole-loop call (dpir_set_progress) and, after it, downloads them into the Progress object."""
+
+    def __init__(self, engine: Engine, progress: Progress, cfg: LoopConfig, entries, B: int, H: int, W: int, has_mask: bool):
+        if progress.masked and not has_mask:
+            raise ValueError("Progress(masked=True) needs a mask (the inpainting task)")
+        self.progress, self.engine = progress, engine
+        table, self.panels = progress_table(cfg, entries)
+        P = len(self.panels)
+        self.f32 = engine.empty((B, 3, H, P * W))
+        self.u8 = engine.empty((B, H, P * W, 3), np.uint8) if progress.u8 else None
+        self.mf32 = engine.empty((B, 3, H, P * W)) if progress.masked else None
+        self.mu8 = engine.empty((B, H, P * W, 3), np.uint8) if progress.masked and progress.u8 else None
+        self.mm = engine.empty((P, B, 2))
+        self.table = (C.c_int32 * len(table))(*table)
+        d = _lib.ProgressDesc()
+        d.panel_of_step_host, d.n_entries, d.n_panels = self.table, len(table), P
+        d.strip_f32, d.strip_u8, d.masked_f32, d.masked_u8, d.minmax_dev = self.f32.ptr, _ptr(self.u8), _ptr(self.mf32), _ptr(self.mu8), self.mm.ptr
+        engine._check(engine.lib.dpir_set_progress(engine.h, C.byref(d)))
+
+    def finish(self):
+        pg = self.progress
+        pg.panels = self.panels
+        pg.strip_f32, pg.minmax = self.f32.numpy(), self.mm.numpy()
+        pg.strip_u8 = None if self.u8 is None else self.u8.numpy()
+        pg.masked_f32 = None if self.mf32 is None else self.mf32.numpy()
+        pg.masked_u8 = None if self.mu8 is None else self.mu8.numpy()
+
+
+def _arm(engine, progress, cfg, entries, B, H, W, has_mask):
+    return None if progress is None else _ArmedProgress(engine, progress, cfg, entries, B, H, W, has_mask)
+
+
+class _HostProgress:
+    """restore_batch_stepwise's side of Progress: x is downloaded at the panel steps and x/2+.5, the uint8 conversion, the masked blend and
+    max / min are formed in numpy float32 -- deliberately NOT dpir_progress_snapshot, so that the stepwise path is the yardstick of the kernel."""
+
+    def __init__(self, progress: Progress, cfg: LoopConfig, entries, y, mask):
+        self.pg = progress
+        self.table, self.panels = progress_table(cfg, entries)
+        if progress.masked and mask is None:
+            raise ValueError("Progress(masked=True) needs a mask (the inpainting task)")
+        self.y = y.numpy() if progress.masked else None
+        self.m = mask.numpy().astype(np.float32) if progress.masked else None
+        self.f32, self.mf32 = [], []
+
+    def take(self, j: int, x):
+        """after step / row j (call with j = -1 freely)"""
+        if j < 0 or self.table[j] < 0:
+            return
+        v = x.numpy() / np.float32(2) + np.float32(0.5)
+        self.f32.append(v)
+        if self.pg.masked:
+            self.mf32.append(self.y * self.m + (np.float32(1) - self.m) * v)
+
+    @staticmethod
+    def _u8(strip):
+        return np.ascontiguousarray(np.rint(np.clip(strip, np.float32(0), np.float32(1)) * np.float32(255)).astype(np.uint8).transpose(0, 2, 3, 1))
+
+    def finish(self):
+        pg = self.pg
+        pg.panels = self.panels
+        pg.strip_f32 = np.concatenate(self.f32, axis=3)
+        pg.minmax = np.stack([np.stack([v.max(axis=(1, 2, 3)), v.min(axis=(1, 2, 3))], axis=1) for v in self.f32]).astype(np.float32)
+        pg.strip_u8 = self._u8(pg.strip_f32) if pg.u8 else None
+        pg.masked_f32 = np.concatenate(self.mf32, axis=3) if pg.masked else None
+        pg.masked_u8 = self._u8(pg.masked_f32) if pg.masked and pg.u8 else None
+
+
 def t_start_of(cfg: LoopConfig, reduced) -> int:
     """main_ddpir.py:197-200: the timestep the forward-noised initial image is placed at; steps above it are skipped (:346)."""
     if cfg.noise_init_img == "max":
@@ -189,22 +300,24 @@ def draw_host_noise(noise_fn: Callable, steps, shape, need_n1: bool, repaint: bo
 def restore_batch(engine: Engine, cfg: LoopConfig, y, k=None, mask=None, labels=None, noise_source="device",
                   noise_fn: Optional[Callable] = None, seed: int = 0, image_offset: int = 0, use_graph: bool = False,
                   skip_dead_final_eval: bool = False, out_f32=None, out_u8=None, return_u8: bool = False, _cache: dict = None,
-                  predrawn=None):
+                  predrawn=None, progress: Optional[Progress] = None):
     """y: [B,3,h,w] in [0,1]; k: [B,1,kh,kw]; mask: uint8 [B,3,H,W] -- device arrays (or numpy, uploaded).
     Returns a DeviceArray [B,3,H,W] = x_0 in [0,1] (un-clamped, main_ddpir.py:470), and the u8 NHWC
-    array as well when return_u8."""
+    array as well when return_u8.  progress: a Progress request, filled with the progressive strip of this call (every driver and mode)."""
     cfg.check_supported()
     if cfg.driver == "main_ddpir_inpainting":
         return _restore_inpaint_resample(engine, cfg, y, mask, labels, noise_source, noise_fn, seed, image_offset, use_graph, skip_dead_final_eval,
-                                         out_f32, out_u8, return_u8, _cache, predrawn)
+                                         out_f32, out_u8, return_u8, _cache, predrawn, progress=progress)
     if cfg.driver == "main_ddpir_deblur" and (cfg.generate_mode != "DiffPIR" or not cfg.sub_1_analytic):
         if predrawn is not None or mask is not None or use_graph:
             raise NotImplementedError("the deblurring program's gradient modes take host noise through noise_fn, no mask and no step graph")
-        return _restore_deblur_grad(engine, cfg, y, k, labels, noise_source, noise_fn, seed, image_offset, skip_dead_final_eval, out_f32, out_u8, return_u8)
+        return _restore_deblur_grad(engine, cfg, y, k, labels, noise_source, noise_fn, seed, image_offset, skip_dead_final_eval, out_f32, out_u8, return_u8,
+                                    progress=progress)
     if cfg.generate_mode in ("DPS_y0", "DPS_yt"):
         if predrawn is not None or mask is not None:
             raise NotImplementedError("DPS modes take host noise through noise_fn (their draw order differs from the DiffPIR loop's) and no mask")
-        return _restore_dps(engine, cfg, y, labels, noise_source, noise_fn, seed, image_offset, skip_dead_final_eval, out_f32, out_u8, return_u8)
+        return _restore_dps(engine, cfg, y, labels, noise_source, noise_fn, seed, image_offset, skip_dead_final_eval, out_f32, out_u8, return_u8,
+                            progress=progress)
     dt, steps, arr = _steps(cfg)
     keep = []
 
@@ -261,7 +374,10 @@ def restore_batch(engine: Engine, cfg: LoopConfig, y, k=None, mask=None, labels=
         out_f32 = engine.empty((B, 3, H, W))
     if out_u8 is None and return_u8:
         out_u8 = engine.empty((B, H, W, 3), np.uint8)
+    armed = _arm(engine, progress, cfg, steps, B, H, W, mask is not None)
     engine._check(engine.lib.dpir_run_loop(engine.h, C.byref(d), arr, len(steps), _ptr(out_f32), _ptr(out_u8)))
+    if armed:
+        armed.finish()
     if _cache is not None:
         _cache["keep"] = keep
     else:
@@ -330,7 +446,7 @@ def draw_inpaint_host_noise(noise_fn: Callable, cfg: LoopConfig, rows, B: int, H
 
 
 def _restore_inpaint_resample(engine, cfg, y, mask, labels, noise_source, noise_fn, seed, image_offset, use_graph, skip_dead_final_eval,
-                              out_f32, out_u8, return_u8, _cache, predrawn, _start=None):
+                              out_f32, out_u8, return_u8, _cache, predrawn, _start=None, progress=None):
     """driver 'main_ddpir_inpainting' (main_ddpir_inpainting.py:190-303): dpir_run_inpaint_loop, one fused data pass per sub-step.
     predrawn: the dict of draw_inpaint_host_noise (sharded runs).  _start: (sa, s1m) instead of the t_y initialisation (tests)."""
     if mask is None:
@@ -374,7 +490,10 @@ def _restore_inpaint_resample(engine, cfg, y, mask, labels, noise_source, noise_
         out_f32 = engine.empty((B, 3, H, W))
     if out_u8 is None and return_u8:
         out_u8 = engine.empty((B, H, W, 3), np.uint8)
+    armed = _arm(engine, progress, cfg, rows, B, H, W, True)
     engine._check(engine.lib.dpir_run_inpaint_loop(engine.h, C.byref(d), arr, len(rows), _ptr(nback), _ptr(out_f32), _ptr(out_u8)))
+    if armed:
+        armed.finish()
     if _cache is not None:
         _cache["keep"] = keep
     else:
@@ -382,7 +501,8 @@ def _restore_inpaint_resample(engine, cfg, y, mask, labels, noise_source, noise_
     return (out_f32, out_u8) if return_u8 else out_f32
 
 
-def _restore_deblur_grad(engine, cfg, y, k, labels, noise_source, noise_fn, seed, image_offset, skip_dead_final_eval, out_f32, out_u8, return_u8):
+def _restore_deblur_grad(engine, cfg, y, k, labels, noise_source, noise_fn, seed, image_offset, skip_dead_final_eval, out_f32, out_u8, return_u8,
+                         progress=None):
     """driver 'main_ddpir_deblur', generate_mode DPS_y0 / DPS_yt / DiffPIR with sub_1_analytic false: dpir_run_deblur_grad_loop.  Host noise is
     drawn batch-shaped in the loop's order (dps_host_noise_shapes); image n uses slice n."""
     from .schedule import DiffusionTables
@@ -445,13 +565,16 @@ def _restore_deblur_grad(engine, cfg, y, k, labels, noise_source, noise_fn, seed
         out_f32 = engine.empty(shape)
     if out_u8 is None and return_u8:
         out_u8 = engine.empty((B, H, W, 3), np.uint8)
+    armed = _arm(engine, progress, cfg, steps, B, H, W, False)
     engine._check(engine.lib.dpir_run_deblur_grad_loop(engine.h, C.byref(d), arr, coefs, len(steps), variant, float(cfg.lambda_),
                                                        _ptr(nps), _ptr(nyt), _ptr(out_f32), _ptr(out_u8)))
     engine.sync()
+    if armed:
+        armed.finish()
     return (out_f32, out_u8) if return_u8 else out_f32
 
 
-def _restore_dps(engine, cfg, y, labels, noise_source, noise_fn, seed, image_offset, skip_dead_final_eval, out_f32, out_u8, return_u8):
+def _restore_dps(engine, cfg, y, labels, noise_source, noise_fn, seed, image_offset, skip_dead_final_eval, out_f32, out_u8, return_u8, progress=None):
     """generate_mode 'DPS_y0' / 'DPS_yt' (main_ddpir.py:370-373, 433-445): dpir_run_dps_loop.  Host noise order: init, then per step the
     p_sample draw and (DPS_yt, non-final steps) the y_t draw; there is no re-noising in these modes (main_ddpir.py:448)."""
     from .schedule import DiffusionTables
@@ -504,13 +627,17 @@ def _restore_dps(engine, cfg, y, labels, noise_source, noise_fn, seed, image_off
         out_f32 = engine.empty((B, 3, H, W))
     if out_u8 is None and return_u8:
         out_u8 = engine.empty((B, H, W, 3), np.uint8)
+    armed = _arm(engine, progress, cfg, steps, B, H, W, False)
     engine._check(engine.lib.dpir_run_dps_loop(engine.h, C.byref(d), arr, coefs, len(steps), 1 if yt_mode else 0, float(cfg.lambda_),
                                                _ptr(nps), _ptr(nyt), 1.0, _ptr(out_f32), _ptr(out_u8)))
     engine.sync()
+    if armed:
+        armed.finish()
     return (out_f32, out_u8) if return_u8 else out_f32
 
 
-def restore_batch_stepwise(model, diffusion, cfg: LoopConfig, y, k=None, mask=None, noise_fn: Callable = None, labels=None):
+def restore_batch_stepwise(model, diffusion, cfg: LoopConfig, y, k=None, mask=None, noise_fn: Callable = None, labels=None,
+                           progress: Optional[Progress] = None):
     """The reference's loop body (main_ddpir.py:291-470) against the drop-in plugs, host-fed noise.  Every branch the monolithic
     loops implement: the DiffPIR analytic step, the first-order data step (sub_1_analytic: false), DPS_y0 and DPS_yt -- the latter
     three written with the reference's own expressions on device arrays (`xt - norm_grad * 1.`, ...)."""
@@ -519,8 +646,9 @@ def restore_batch_stepwise(model, diffusion, cfg: LoopConfig, y, k=None, mask=No
     eng: Engine = model.engine
     cfg.check_supported()
     if cfg.driver == "main_ddpir_inpainting":
-        return _stepwise_inpaint_resample(model, diffusion, cfg, y, mask, noise_fn, labels)
+        return _stepwise_inpaint_resample(model, diffusion, cfg, y, mask, noise_fn, labels, progress)
     dt, steps, arr = _steps(cfg)
+    hp = None if progress is None else _HostProgress(progress, cfg, steps, y, mask)
     B, _, h, w = y.shape
     H, W = h * cfg.sf, w * cfg.sf
     shape = (B, 3, H, W)
@@ -552,6 +680,8 @@ def restore_batch_stepwise(model, diffusion, cfg: LoopConfig, y, k=None, mask=No
     utils_model.set_randn_like(draw)
     try:
         for i, st in enumerate(steps):
+            if hp:
+                hp.take(i - 1, x)                               # the panel of the step before: x as that step left it
             curr_sigma = dt.reduced[st["t"]]
             t_i = st["t"]
             if cfg.generate_mode == "repaint":                  # main_ddpir.py:355-358
@@ -593,16 +723,12 @@ def restore_batch_stepwise(model, diffusion, cfg: LoopConfig, y, k=None, mask=No
                 x0 = x0.detach_()
             elif cfg.task == "inpaint":
                 eng._check(lib.dpir_prox_mask(hnd, x0.ptr, _ptr(y), _ptr(mask), float(tau), cfg.guidance_scale, B, H, W))
-            elif deb:
-                # main_ddpir_deblur.py:291-295 through the entry that replaces those lines as a whole (dpir_prox_fft_apply): the kernels and the
-                # roundings of dpir_run_loop's data step, which at guidance_scale 1 writes 2 data_solution(.) - 1 without forming x0 + 1 (. - x0)
-                eng._check(lib.dpir_prox_fft_apply(hnd, FB.spectra.handle, x0.ptr, float(tau), float(cfg.guidance_scale)))
             elif cfg.task == "deblur" or cfg.sr_mode == "blur":
-                x0_p = eng.empty(shape)
-                eng._check(lib.dpir_finalize(hnd, x0.ptr, x0_p.ptr, None, B, H, W))          # x0/2+.5
-                x0_p = sr.data_solution(x0_p, FB, FBC, F2B, FBFy, tau, cfg.sf)
-                a, b = x0.numpy(), x0_p.numpy() * np.float32(2) - np.float32(1)
-                x0.copy_from(a + np.float32(cfg.guidance_scale) * (b - a))
+                # main_ddpir.py:395-400 / main_ddpir_deblur.py:291-295 through the entry that replaces those lines as a whole (dpir_prox_fft_apply):
+                # the kernels and the roundings of dpir_run_loop's data step, which on the half-spectrum layouts at guidance_scale 1 writes
+                # 2 data_solution(.) - 1 without forming x0 + 1 (. - x0).  (Forming the blend on the host from sr.data_solution's output differs
+                # from that by an ulp of x0 -- enough to separate the two loops' progress panels, which are compared bit for bit.)
+                eng._check(lib.dpir_prox_fft_apply(hnd, FB.spectra.handle, x0.ptr, float(tau), float(cfg.guidance_scale)))
             else:
                 eng._check(lib.dpir_prox_ibp(hnd, x0.ptr, _ptr(y), float(tau), cfg.gamma, cfg.inIter, cfg.sf, B, H, W))
             n1 = eng.to_device(np.asarray(noise_fn(shape), np.float32))
@@ -610,18 +736,22 @@ def restore_batch_stepwise(model, diffusion, cfg: LoopConfig, y, k=None, mask=No
             eng._check(lib.dpir_renoise(hnd, x.ptr, x0.ptr, C.byref(arr[i]), n1.ptr, n2.ptr, B, H, W))
     finally:
         utils_model.set_randn_like(None)
+    if hp:
+        hp.take(len(steps) - 1, x)
+        hp.finish()
     out = eng.empty(shape)
     eng._check(lib.dpir_finalize(hnd, x.ptr, out.ptr, None, B, H, W))
     eng.sync()
     return out
 
 
-def _stepwise_inpaint_resample(model, diffusion, cfg: LoopConfig, y, mask, noise_fn, labels):
+def _stepwise_inpaint_resample(model, diffusion, cfg: LoopConfig, y, mask, noise_fn, labels, progress=None):
     """main_ddpir_inpainting.py:190-303 over the drop-in plugs, one launch per expression: the unfused statement of dpir_run_inpaint_loop.
     Host noise is taken through draw_inpaint_host_noise (the program's per-image draw order)."""
     from . import utils_model
     eng: Engine = model.engine
     dt, rows, arr = _inpaint_rows(cfg)
+    hp = None if progress is None else _HostProgress(progress, cfg, rows, y, mask)
     B, _, H, W = y.shape
     shape, numel = (B, 3, H, W), B * 3 * H * W
     lib, hnd = eng.lib, eng.h
@@ -636,6 +766,8 @@ def _stepwise_inpaint_resample(model, diffusion, cfg: LoopConfig, y, mask, noise
         for f, _ in _lib.Step._fields_:
             setattr(steps[s], f, r[f])
     for s, r in enumerate(rows):
+        if hp:
+            hp.take(s - 1, x)                               # :302-309 of the row group that just ended, ahead of this row's mix
         if cfg.generate_mode == "repaint":                  # :244-246
             nr = eng.to_device(nz["rp"][s])
             eng._check(lib.dpir_repaint_mix(hnd, x.ptr, _ptr(y), _ptr(mask), C.byref(steps[s]), nr.ptr, B, H, W))
@@ -653,6 +785,9 @@ def _stepwise_inpaint_resample(model, diffusion, cfg: LoopConfig, y, mask, noise
             eng._check(lib.dpir_ewise(hnd, 2, x.ptr, None, 0, float(np.float32(r["sae"])), x.ptr, numel))
             eng._check(lib.dpir_ewise(hnd, 2, nb.ptr, None, 0, float(np.float32(r["sb"])), nb.ptr, numel))
             eng._check(lib.dpir_ewise(hnd, 0, x.ptr, nb.ptr, numel, 0.0, x.ptr, numel))
+    if hp:
+        hp.take(len(rows) - 1, x)
+        hp.finish()
     out = eng.empty(shape)
     eng._check(lib.dpir_finalize(hnd, x.ptr, out.ptr, None, B, H, W))
     eng.sync()

@@ -103,6 +103,42 @@ def make_seq(T: int, iter_num: int, skip_type: str = "quad") -> List[int]:
     return seq
 
 
+def progress_seq(seq, program: str = "main_ddpir") -> List[int]:
+    """The seq values whose steps keep a panel of the progressive strip (save_progressive), literally as the reference builds them:
+    main_ddpir.py:336-338 = main_ddpir_deblur.py:252-254 = main_ddpir_sisr.py:275-277 (`max(., 1)`, seq[-1] appended only when it is not
+    last already) and main_ddpir_inpainting.py:227-228 (no max: raises for fewer than 10 entries; seq[-1] appended unconditionally)."""
+    seq = list(seq)
+    if program == "main_ddpir_inpainting":
+        if len(seq) < 10:
+            raise ValueError("main_ddpir_inpainting.py:227 `progress_seq = seq[::(len(seq)//10)]` raises for a schedule of fewer than 10 entries "
+                             f"(got {len(seq)}): there is no behaviour to mirror")
+        ps = seq[::(len(seq) // 10)]
+        ps.append(seq[-1])
+        return ps
+    if program not in ("main_ddpir", "main_ddpir_deblur", "main_ddpir_sisr"):
+        raise ValueError(f"unknown program {program!r}")
+    ps = seq[::max(len(seq) // 10, 1)]
+    if ps[-1] != seq[-1]:
+        ps.append(seq[-1])
+    return ps
+
+
+def progress_panels(seq, visited, program: str = "main_ddpir") -> List[int]:
+    """For every visited step -- `visited` lists the indices i into seq that the loop does not skip (t_i <= t_start; the `continue` of
+    main_ddpir_deblur.py:262-263 / main_ddpir_inpainting.py:236-237 precedes the snapshot block), one entry per timestep, not per
+    resampling sub-step -- its panel index in the strip, or -1.  Membership is by VALUE (`seq[i] in progress_seq`, main_ddpir_deblur.py:361,
+    main_ddpir_inpainting.py:304), so every occurrence of a duplicated seq value keeps a panel; the final step (seq[i] == seq[-1]) always does."""
+    ps = progress_seq(seq, program)
+    out, p = [], 0
+    for i in visited:
+        if seq[i] in ps:
+            out.append(p)
+            p += 1
+        else:
+            out.append(-1)
+    return out
+
+
 def build_steps(*, iter_num: int, sigma: float, lambda_: float, zeta: float, eta: float = 0.0,
                 skip_type: str = "quad", T: int = 1000, beta_start=0.0001, beta_end=0.02,
                 t_start: int = None, generate_mode: str = "DiffPIR", model_output_type: str = "pred_xstart"):
@@ -135,7 +171,7 @@ def build_steps(*, iter_num: int, sigma: float, lambda_: float, zeta: float, eta
         c1, c2 = dtab.c1c2(t_i)
         st = dict(t=t_i, last=int(last), c1=float(c1), c2=float(c2), tau=float(rhos[t_i]),
                   sa_t=float(dt.sqrt_ac[t_i]), s1m_t=float(dt.sqrt_1m_ac[t_i]),
-                  sa_p=0.0, k1=0.0, q=0.0, es=0.0, k2=0.0, t_im1=None)
+                  sa_p=0.0, k1=0.0, q=0.0, es=0.0, k2=0.0, t_im1=None, seq_i=i, seq=seq[i])
         if not last:
             t_p = t_list[i + 1]
             # main_ddpir.py:454-456 with 0-dim float32 tensors
@@ -183,7 +219,7 @@ def build_inpaint_rows(*, iter_num: int, iter_num_U: int, sigma: float, lambda_:
         c1, c2 = dtab.c1c2(t_i)
         base = dict(t=t_i, last=int(last), pos=pos, back=0, c1=float(c1), c2=float(c2), tau=float(rhos[t_i]), sa_t=float(dt.sqrt_ac[t_i]),
                     s1m_t=float(dt.sqrt_1m_ac[t_i]), sa_p=0.0, k1=0.0, q=0.0, es=0.0, k2=0.0, sae=0.0, sb=0.0, sa_n=0.0, s1m_n=0.0,
-                    mix_next=0, reserved=0, t_im1=None, u=0)
+                    mix_next=0, reserved=0, t_im1=None, u=0, seq_i=i, seq=seq[i])
         if not last:
             t_p = t_list[i + 1]
             s1m_p, s1m_t = t_s1m[t_p], t_s1m[t_i]

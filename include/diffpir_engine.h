@@ -304,6 +304,40 @@ int dpir_inpaint_step(dpir_engine* e, float* x_dev, const float* eps_dev, int ep
 int dpir_run_inpaint_loop(dpir_engine* e, const dpir_loop_desc* d, const dpir_inpaint_row* rows_host, int n_rows, const float* noise_back_dev,
                           float* out_f32_dev, uint8_t* out_u8_dev);
 
+/* ---- progressive snapshots (save_progressive / log_process / save_progressive_mask) ----------- */
+/* dpir_progress_snapshot replaces main_ddpir_deblur.py:359-371 = main_ddpir_sisr.py:386-398 = main_ddpir_inpainting.py:302-313 for one panel
+ * (x_show = x/2+.5 kept where seq[i] is in progress_seq, np.max / np.min of it for log_process), the cv2.hconcat of the kept panels
+ * (main_ddpir_deblur.py:400-406, main_ddpir_inpainting.py:356-359: each panel is written at its column block of the strip instead) and
+ * main_ddpir_inpainting.py:361-366 (y_t mask + (1 - mask) x_show; that program's y is in [-1,1], hence its y/2+0.5 -- y_dev here is in [0,1]).
+ * One pass over x_dev [B,3,H,W] for panel `panel` of `n_panels`; every output is optional (NULL: not written):
+ *   strip_f32 [B,3,H,n_panels W] = x/2+.5 and strip_u8 [B,H,n_panels W,3], both bit-equal to dpir_finalize's outputs of the same x;
+ *   masked_f32 / masked_u8: the same two layouts of the masked blend (need y_dev and mask_dev [B,3,H,W], mask uint8 {0,1});
+ *   minmax_dev [n_panels,B,2]: (max, min) of image b's panel at [panel][b], exact, float32 (4-byte aligned).
+ * Only the panel's columns (and its minmax row) are written.  Asynchronous on the engine stream.  DPIR_ERR_INVALID, nothing launched: panel
+ * outside [0, n_panels), a masked output without y_dev and mask_dev, a bad shape (see the conventions above; n_panels W must fit an int). */
+int dpir_progress_snapshot(dpir_engine* e, const float* x_dev, const float* y_dev, const uint8_t* mask_dev, int panel, int n_panels,
+                           float* strip_f32, uint8_t* strip_u8, float* masked_f32, uint8_t* masked_u8, float* minmax_dev, int B, int H, int W);
+
+/* The same film strip out of the whole-loop entries, which never return to the host between steps.  Replaces the `if save_progressive and
+ * (seq[i] in progress_seq)` blocks cited above inside the loops of main_ddpir.py:336-338, main_ddpir_deblur.py:242-254 and
+ * main_ddpir_inpainting.py:217-228 (diffpir_amd/schedule.py progress_panels computes panel_of_step_host from those recipes). */
+typedef struct dpir_progress_desc {
+    const int32_t* panel_of_step_host;   /* [n_entries]: the panel taken after step i (dpir_run_loop, dpir_run_dps_loop, dpir_run_deblur_grad_loop) or
+                                          * after row r (dpir_run_inpaint_loop: the last sub-step of the timestep), or -1 for none.  Copied. */
+    int32_t n_entries;                   /* must equal the loop call's n_steps / n_rows */
+    int32_t n_panels;
+    float* strip_f32; uint8_t* strip_u8; /* as dpir_progress_snapshot, for the loop's B, H, W; any may be NULL */
+    float* masked_f32; uint8_t* masked_u8;   /* inpainting loops only (the descriptor's y_dev and mask_dev) */
+    float* minmax_dev;
+} dpir_progress_desc;
+/* Arms the NEXT call of dpir_run_loop / dpir_run_inpaint_loop / dpir_run_dps_loop / dpir_run_deblur_grad_loop on this engine, and only that call: the
+ * arming is cleared when the call returns, whether it succeeded or not.  NULL disarms.  A step skipped by skip_dead_final_eval still yields its
+ * panel (the unchanged x).  The snapshots are launched on the engine stream between the steps, outside the captured step graphs: an armed
+ * call replays the same graphs as an unarmed one and computes the same result; an unarmed call launches nothing new.  The loop call returns
+ * DPIR_ERR_INVALID before anything is launched when n_entries differs from its n_steps / n_rows or a masked strip is armed for a loop without a
+ * mask.  DPIR_ERR_INVALID here: n_panels < 1, an entry outside [-1, n_panels), n_entries < 1 or a NULL table. */
+int dpir_set_progress(dpir_engine* e, const dpir_progress_desc* desc);
+
 /* ---- gradient-based sampling (generate_mode 'DPS_y0') ---------------------- */
 /* Replaces what torch.autograd does for the reference's DPS branch (main_ddpir.py:370-373, 434-438 with
  * utils_model.grad_and_value, utils/utils_model.py:390-394).  Gradient mode must be switched on BEFORE dpir_load_unet: it builds
