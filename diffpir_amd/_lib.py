@@ -33,6 +33,11 @@ class Step(C.Structure):
                 ("k1", C.c_float), ("q", C.c_float), ("es", C.c_float), ("k2", C.c_float)]
 
 
+class ImageStep(C.Structure):
+    """dpir_image_step: one image's (tau, k1, k2) of one step (schedule.build_image_table)."""
+    _fields_ = [("tau", C.c_float), ("k1", C.c_float), ("k2", C.c_float), ("reserved", C.c_float)]
+
+
 class LoopDesc(C.Structure):
     _fields_ = [("task", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("sf", C.c_int32),
                 ("kh", C.c_int32), ("kw", C.c_int32), ("in_iter", C.c_int32), ("gamma", C.c_float),
@@ -178,6 +183,9 @@ SIGNATURES = {
     "dpir_degrade": (C.c_int, [C.c_void_p, C.POINTER(DegradeDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dpir_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dpir_run_loop": (C.c_int, [C.c_void_p, C.POINTER(LoopDesc), C.POINTER(Step), C.c_int, C.c_void_p, C.c_void_p]),
+    "dpir_run_loop_per_image": (C.c_int, [C.c_void_p, C.POINTER(LoopDesc), C.POINTER(Step), C.c_int, C.POINTER(ImageStep), C.POINTER(C.c_int64),
+                                          C.c_void_p, C.c_void_p]),
+    "dpir_randn_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int]),
     "dpir_inpaint_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(InpaintRow), C.c_int, C.c_float,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "dpir_run_inpaint_loop": (C.c_int, [C.c_void_p, C.POINTER(LoopDesc), C.POINTER(InpaintRow), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

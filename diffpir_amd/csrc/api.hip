@@ -487,13 +487,13 @@ int dpir_resize_down(dpir_engine* e, const float* x, float* out, int sf, int B, 
 }
 
 static Status prox_ibp_impl(dpir_engine* e, float* x0, const float* y, float rho, float gamma, int in_iter, int sf, int B, int H, int W,
-                            const StepDev* sp = nullptr, const LoopDev* lp = nullptr) {
+                            const StepDev* sp = nullptr, const LoopDev* lp = nullptr, bool per_image = false) {
     float* d = nullptr;
     DPIR_TRY(e->ws.getT("ibp#down", (size_t)B * 3 * (H / sf) * (W / sf), &d));
     for (int it = 0; it < in_iter; ++it) {
         DPIR_TRY(resize_down_impl(e, x0, 0.5f, 0.5f, d, sf, B, H, W));      // down(x0/2+.5)
         ProfScope ps(&e->prof, PC_ELEM);
-        DPIR_TRY(launch_ibp_update(e->stream, x0, y, d, gamma, rho, sf, B * 3, H, W, sp, lp));
+        DPIR_TRY(launch_ibp_update(e->stream, x0, y, d, gamma, rho, sf, B * 3, H, W, sp, lp, per_image));
     }
     return Status{};
 }
@@ -613,6 +613,21 @@ int dpir_randn(dpir_engine* e, float* out, uint64_t seed, uint64_t stream_id, in
     return DPIR_OK;
 }
 
+int dpir_randn_indexed(dpir_engine* e, float* out, uint64_t seed, uint64_t stream_id, const int64_t* image_index, int B, int C, int H, int W) {
+    if (!e || !out || !image_index) return fail(e, invalid("dpir_randn_indexed: null argument"));
+    API_TRY(e, check_shape("dpir_randn_indexed", B, H, W));
+    if (C < 1 || (long long)C * H * W > 0x7fffffffLL) return fail(e, invalid("dpir_randn_indexed: C must be >= 1 and C * H * W in range"));
+    (void)hipSetDevice(e->device);
+    long long* idx = nullptr;
+    API_TRY(e, e->ws.getT("randn#idx", (size_t)B, &idx));
+    static_assert(sizeof(long long) == sizeof(int64_t), "the image numbers are copied as they are");
+    API_HIP(e, hipMemcpyAsync(idx, image_index, sizeof(int64_t) * B, hipMemcpyHostToDevice, e->stream));
+    API_HIP(e, hipStreamSynchronize(e->stream));        // the host array is the caller's
+    ProfScope ps(&e->prof, PC_ELEM);
+    API_TRY(e, launch_randn(e->stream, out, seed, stream_id, 0, B, (size_t)C * H * W, nullptr, nullptr, idx));
+    return DPIR_OK;
+}
+
 int dpir_ewise(dpir_engine* e, int op, const float* x_dev, const float* y_dev, size_t y_numel, float scalar, float* out_dev, size_t numel) {
     if (!e || !x_dev || !out_dev) return fail(e, invalid("dpir_ewise: null argument"));
     (void)hipSetDevice(e->device);
@@ -685,7 +700,10 @@ int dpir_metrics(dpir_engine* e, const float* x0, const uint8_t* gt, int B, int 
 // ------------------------------------------------------------------------------------------ whole loop
 namespace {
 struct LoopBufs { float *x, *x0, *out6, *n1, *n2, *init_src; int *t_dev, *y_dev; StepDev *steps_dev, *cur; LoopDev* lp;
-                  float* film; };   // film: hoisted FiLM table [n_steps][film_rows] (class-unconditional models) or null
+                  float* film;      // film: hoisted FiLM table [n_steps][film_rows] (class-unconditional models) or null
+                  // dpir_run_loop_per_image: the (tau, k1, k2, 0) table [n_steps][B] and the Philox image numbers [B] (both filled when per_image: a table
+                  // the caller left out repeats the step's own scalars / image_offset + b); per_image selects the kernels' per-image instantiations
+                  float4* img; long long* imgidx; bool per_image; };
 
 __global__ void fill_t_kernel(int* p, const StepDev* sp, int n) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -704,7 +722,7 @@ Status loop_init(dpir_engine* e, const dpir_loop_desc& d, const LoopBufs& b, Pro
         src = b.init_src;
     }
     const float* n0 = d.noise_init_dev;
-    if (!n0) { DPIR_TRY(launch_randn(s, b.n2, d.seed, 0, d.image_offset, B, (size_t)3 * H * W)); n0 = b.n2; }
+    if (!n0) { DPIR_TRY(launch_randn(s, b.n2, d.seed, 0, d.image_offset, B, (size_t)3 * H * W, nullptr, nullptr, b.per_image ? b.imgidx : nullptr)); n0 = b.n2; }
     {
         ProfScope ps(&e->prof, PC_ELEM);
         DPIR_TRY(launch_init_x(s, src, d.task == DPIR_TASK_INPAINT ? d.mask_dev : nullptr, n0, d.sa_start, d.s1m_start, b.x, total));
@@ -723,13 +741,13 @@ Status loop_step(dpir_engine* e, const dpir_loop_desc& d, const LoopBufs& b, Pro
         ProfScope ps(&e->prof, PC_ELEM);
         const float* nr = d.noise_rp_dev;
         size_t rstride = total;
-        if (!nr) { DPIR_TRY(launch_randn(s, b.n1, d.seed, 3, d.image_offset, B, (size_t)3 * H * W, b.cur, b.lp)); nr = b.n1; rstride = 0; }
+        if (!nr) { DPIR_TRY(launch_randn(s, b.n1, d.seed, 3, d.image_offset, B, (size_t)3 * H * W, b.cur, b.lp, nullptr, b.per_image)); nr = b.n1; rstride = 0; }
         DPIR_TRY(launch_repaint_mix(s, b.x, d.y_dev, d.mask_dev, nr, 0.f, 0.f, total, b.cur, rstride, b.lp));
     }
     if (!b.film) hipLaunchKernelGGL(fill_t_kernel, dim3((B + 255) / 256), dim3(256), 0, s, b.t_dev, b.cur, B);
     DPIR_TRY(unet_forward(e, b.x, b.t_dev, b.y_dev, b.out6, B, H, W, b.film, b.film ? b.cur : nullptr));
     bool fused = false;       // the data step and the re-noise inside the prox's own three launches (half layouts): nothing is left to do here
-    DPIR_TRY(prox_fused_step(e, *prox, d, last, with_n1, b.x, b.out6, b.x0, b.cur, b.lp, &fused));
+    DPIR_TRY(prox_fused_step(e, *prox, d, last, with_n1, b.x, b.out6, b.x0, b.cur, b.lp, &fused, b.per_image));
     if (fused) return Status{};
     {
         ProfScope ps(&e->prof, PC_ELEM);
@@ -742,23 +760,23 @@ Status loop_step(dpir_engine* e, const dpir_loop_desc& d, const LoopBufs& b, Pro
         DPIR_TRY(prox_first_order_impl(e, b.x0, d.y_dev, 0.f, d.sf, B, H, W, b.cur, b.lp));
     } else if (d.task == DPIR_TASK_INPAINT) {
         ProfScope ps(&e->prof, PC_ELEM);
-        DPIR_TRY(launch_prox_mask(s, b.x0, d.y_dev, d.mask_dev, 0.f, d.guidance, total, b.cur, b.lp));
+        DPIR_TRY(launch_prox_mask(s, b.x0, d.y_dev, d.mask_dev, 0.f, d.guidance, total, b.cur, b.lp, b.per_image));
     } else if (d.task == DPIR_TASK_SR_CUBIC) {
-        DPIR_TRY(prox_ibp_impl(e, b.x0, d.y_dev, 0.f, d.gamma, d.in_iter, d.sf, B, H, W, b.cur, b.lp));
+        DPIR_TRY(prox_ibp_impl(e, b.x0, d.y_dev, 0.f, d.gamma, d.in_iter, d.sf, B, H, W, b.cur, b.lp, b.per_image));
     } else {
-        DPIR_TRY(prox_data_solution(e, *prox, b.x0, 0.5f, 0.5f, 1.f, b.x0, 2.f, -1.f, b.x0, d.guidance, b.cur));
+        DPIR_TRY(prox_data_solution(e, *prox, b.x0, 0.5f, 0.5f, 1.f, b.x0, 2.f, -1.f, b.x0, d.guidance, b.cur, b.per_image ? b.lp : nullptr));
     }
     const float *n1 = nullptr, *n2 = nullptr;
     size_t stride = 0;
     ProfScope ps(&e->prof, PC_ELEM);
     if (with_n1) {
         if (d.noise_n1_dev) n1 = d.noise_n1_dev;
-        else { DPIR_TRY(launch_randn(s, b.n1, d.seed, 1, d.image_offset, B, (size_t)3 * H * W, b.cur, b.lp)); n1 = b.n1; }
+        else { DPIR_TRY(launch_randn(s, b.n1, d.seed, 1, d.image_offset, B, (size_t)3 * H * W, b.cur, b.lp, nullptr, b.per_image)); n1 = b.n1; }
     }
     if (d.noise_n2_dev) { n2 = d.noise_n2_dev; stride = total; }
-    else { DPIR_TRY(launch_randn(s, b.n2, d.seed, 2, d.image_offset, B, (size_t)3 * H * W, b.cur, b.lp)); n2 = b.n2; }
+    else { DPIR_TRY(launch_randn(s, b.n2, d.seed, 2, d.image_offset, B, (size_t)3 * H * W, b.cur, b.lp, nullptr, b.per_image)); n2 = b.n2; }
     if (with_n1 && d.noise_n1_dev && !d.noise_n2_dev) return invalid("host n1 noise requires host n2 noise");
-    DPIR_TRY(launch_renoise(s, b.x, b.x0, RenoiseCoef{}, n1, n2, total, b.cur, stride, b.lp));
+    DPIR_TRY(launch_renoise(s, b.x, b.x0, RenoiseCoef{}, n1, n2, total, b.cur, stride, b.lp, b.per_image));
     DPIR_HIP(hipGetLastError());
     return Status{};
 }
@@ -766,7 +784,8 @@ Status loop_step(dpir_engine* e, const dpir_loop_desc& d, const LoopBufs& b, Pro
 
 extern "C" {
 
-static int run_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, int n_steps, float* out_f32, uint8_t* out_u8);
+static int run_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, int n_steps, const dpir_image_step* per_image,
+                         const int64_t* image_index, float* out_f32, uint8_t* out_u8);
 
 // Runs a whole-loop call and, in the f16 modes with the fused hop on, looks at the guard word afterwards: on a hop time-out the loop is run again
 // on the unfused path.  Shared by dpir_run_loop and dpir_run_inpaint_loop.
@@ -785,7 +804,16 @@ static int run_with_hop_guard(dpir_engine* e, const std::function<int()>& once) 
 
 int dpir_run_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, int n_steps, float* out_f32, uint8_t* out_u8) {
     ProgressOneShot one_shot{e};
-    return run_with_hop_guard(e, [&] { return run_loop_once(e, dd, steps, n_steps, out_f32, out_u8); });
+    return run_with_hop_guard(e, [&] { return run_loop_once(e, dd, steps, n_steps, nullptr, nullptr, out_f32, out_u8); });
+}
+int dpir_run_loop_per_image(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, int n_steps, const dpir_image_step* per_image,
+                            const int64_t* image_index, float* out_f32, uint8_t* out_u8) {
+    ProgressOneShot one_shot{e};
+    // refused before anything is enqueued: the first-order data step normalises by ONE residual norm of the whole batch (main_ddpir.py:425-427)
+    if (e && dd && per_image && dd->first_order)
+        return fail(e, Status{DPIR_ERR_UNSUPPORTED, "dpir_run_loop_per_image: the first-order data step (sub_1_analytic: false) has no per-image form: it "
+                                                    "normalises by a batch-wide residual norm"});
+    return run_with_hop_guard(e, [&] { return run_loop_once(e, dd, steps, n_steps, per_image, image_index, out_f32, out_u8); });
 }
 
 // The captured-step cache shared by dpir_run_loop and dpir_run_inpaint_loop: the graph for `key` (ws_generation is filled in here), or -- on a
@@ -815,7 +843,8 @@ static int cached_step_graph(dpir_engine* e, dpir_engine::GraphKey key, const st
     return DPIR_OK;
 }
 
-static int run_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, int n_steps, float* out_f32, uint8_t* out_u8) {
+static int run_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, int n_steps, const dpir_image_step* per_image,
+                         const int64_t* image_index, float* out_f32, uint8_t* out_u8) {
     if (!e || !dd || !steps || n_steps <= 0) return fail(e, invalid("dpir_run_loop: null argument"));
     (void)hipSetDevice(e->device);
     const dpir_loop_desc& d = *dd;
@@ -847,6 +876,11 @@ static int run_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_st
     API_TRY(e, e->ws.getT("loop#steps", (size_t)n_steps, &b.steps_dev));
     API_TRY(e, e->ws.getT("loop#cur", (size_t)1, &b.cur));
     API_TRY(e, e->ws.getT("loop#lp", (size_t)1, &b.lp));
+    // the per-image tables are workspace buffers of EVERY call (a uniform one leaves them unwritten): were they allocated by the first per-image call, the
+    // workspace generation would move and orphan the uniform steps already captured
+    API_TRY(e, e->ws.getT("loop#img", (size_t)n_steps * B, &b.img));
+    API_TRY(e, e->ws.getT("loop#imgidx", (size_t)B, &b.imgidx));
+    b.per_image = per_image != nullptr || image_index != nullptr;
     API_TRY(e, upload_ints(e, "loop#y", d.labels_host, B, &b.y_dev));
     const bool hoist_film = e->net.desc.num_classes == 0;
     if (hoist_film) API_TRY(e, e->ws.getT("loop#film", (size_t)n_steps * e->net.film_rows, &b.film));
@@ -874,7 +908,22 @@ static int run_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_st
             // iter_num > T/2): each is a dead denoiser call, prox and re-noise are skipped (main_ddpir.py:384, 448)
             if (i > 0 && steps[i - 1].last && !st.last) return fail(e, invalid("dpir_run_loop: a non-final step may not follow a final step"));
         }
-        LoopDev hl{d.y_dev, d.mask_dev, d.noise_n1_dev, d.noise_n2_dev, d.noise_rp_dev, (unsigned long long)d.seed, (long long)d.image_offset};
+        LoopDev hl{d.y_dev, d.mask_dev, d.noise_n1_dev, d.noise_n2_dev, d.noise_rp_dev, (unsigned long long)d.seed, (long long)d.image_offset,
+                   b.per_image ? b.img : nullptr, b.per_image ? b.imgidx : nullptr, B, 0};
+        std::vector<float4> himg;
+        std::vector<long long> hidx;
+        if (b.per_image) {
+            himg.resize((size_t)n_steps * B);
+            for (int i = 0; i < n_steps; ++i)
+                for (int n = 0; n < B; ++n) {
+                    const dpir_image_step* r = per_image ? per_image + (size_t)i * B + n : nullptr;
+                    himg[(size_t)i * B + n] = r ? make_float4(r->tau, r->k1, r->k2, 0.f) : make_float4(steps[i].tau, steps[i].k1, steps[i].k2, 0.f);
+                }
+            hidx.resize(B);
+            for (int n = 0; n < B; ++n) hidx[n] = image_index ? (long long)image_index[n] : (long long)d.image_offset + n;
+            API_HIP(e, hipMemcpyAsync(b.img, himg.data(), sizeof(float4) * himg.size(), hipMemcpyHostToDevice, e->stream));
+            API_HIP(e, hipMemcpyAsync(b.imgidx, hidx.data(), sizeof(long long) * B, hipMemcpyHostToDevice, e->stream));
+        }
         API_HIP(e, hipMemcpyAsync(b.steps_dev, hs.data(), sizeof(StepDev) * n_steps, hipMemcpyHostToDevice, e->stream));
         API_HIP(e, hipMemcpyAsync(b.lp, &hl, sizeof(hl), hipMemcpyHostToDevice, e->stream));
         API_HIP(e, hipStreamSynchronize(e->stream));
@@ -909,6 +958,7 @@ static int run_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_st
             k.host_n1 = d.noise_n1_dev != nullptr; k.host_n2 = d.noise_n2_dev != nullptr; k.host_rp = d.noise_rp_dev != nullptr;
             k.has_labels = d.labels_host != nullptr;
             k.gamma = d.gamma; k.guidance = d.guidance;
+            k.per_image = per_image != nullptr; k.image_index = image_index != nullptr;
             bool ran = false;
             if (int rc = cached_step_graph(e, k, [&] { return loop_step(e, d, b, &prox, last, with_n1); }, g_step, g_last, &g, &ran)) return rc;
             if (ran) continue;   // this step was executed eagerly

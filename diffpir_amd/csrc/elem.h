@@ -16,18 +16,24 @@ struct StepDev {
 
 // Per-batch values of dpir_run_loop that kernels read on the device (fixed address): with them out of the kernel
 // arguments, ONE captured step graph serves every batch of the same shape (new y / mask / noise pointers, seed and
-// image offset only rewrite this 64-byte block).
+// image offset only rewrite this 80-byte block).
 struct LoopDev {
     const float* y; const uint8_t* mask;
     const float* n1; const float* n2; const float* nrp;     // host-fed noise tensors (parity mode) or null
     unsigned long long seed; long long image_offset;
+    // dpir_run_loop_per_image (null otherwise): image n at step i uses img[i * B + n] = (tau, k1, k2, 0) in place of the step's own, and
+    // imgidx[n] in place of image_offset + n as its Philox image number.  Read by the per-image instantiations only (PI = true).
+    const float4* img; const long long* imgidx; int B, pad;
 };
+// the per-image row of image n at the current step
+__device__ __forceinline__ float4 image_row(const StepDev* sp, const LoopDev* lp, size_t n) { return lp->img[(size_t)sp->i * lp->B + n]; }
 
 Status launch_xstart(hipStream_t s, const float* x, const float* out6, int out_ch, float c1, float c2, float* x0, int B, int HW, const StepDev* sp = nullptr);
+// per_image (here and below; needs sp and lp): the per-image instantiation, which reads tau / k1 / k2 / the Philox image number from lp->img / lp->imgidx
 Status launch_prox_mask(hipStream_t s, float* x0, const float* y, const uint8_t* mask, float tau, float g, size_t total, const StepDev* sp = nullptr,
-                        const LoopDev* lp = nullptr);
+                        const LoopDev* lp = nullptr, bool per_image = false);
 Status launch_renoise(hipStream_t s, float* x, const float* x0, const RenoiseCoef& c, const float* n1, const float* n2, size_t total,
-                      const StepDev* sp = nullptr, size_t noise_step_stride = 0, const LoopDev* lp = nullptr);
+                      const StepDev* sp = nullptr, size_t noise_step_stride = 0, const LoopDev* lp = nullptr, bool per_image = false);
 // repaint conditioning before the denoiser call; sp != null: coefficients and the host-noise step offset come from the device step
 Status launch_repaint_mix(hipStream_t s, float* x, const float* y, const uint8_t* mask, const float* n, float sa, float s1m, size_t total,
                           const StepDev* sp = nullptr, size_t noise_step_stride = 0, const LoopDev* lp = nullptr);
@@ -39,10 +45,11 @@ Status launch_affine(hipStream_t s, const float* x, float a, float b, float* out
 Status launch_band_resample(hipStream_t s, const float* in, const float* w, const int* idx, int taps, int P, int L_in,
                             int L_out, int inner, float pa, float pb, float* out);
 Status launch_ibp_update(hipStream_t s, float* x0, const float* y, const float* d, float gamma, float rho, int sf, int P, int H, int W,
-                         const StepDev* sp = nullptr, const LoopDev* lp = nullptr);
+                         const StepDev* sp = nullptr, const LoopDev* lp = nullptr, bool per_image = false);
 Status launch_bicubic_up(hipStream_t s, const float* in, float* out, int P, int h, int w, int sf);
 Status launch_randn(hipStream_t s, float* out, uint64_t seed, uint64_t stream_id, int64_t image_offset, int B, size_t per_image,
-                    const StepDev* sp = nullptr, const LoopDev* lp = nullptr);   // sp: stream_id += 4 * sp->i; lp: seed / image_offset from the device block
+                    const StepDev* sp = nullptr, const LoopDev* lp = nullptr,    // sp: stream_id += 4 * sp->i; lp: seed / image_offset from the device block
+                    const long long* image_index = nullptr, bool loop_index = false);   // row n is image image_index[n] (device, [B]), or lp->imgidx[n] (loop_index)
 // degrade.hip: degradation synthesis on the uint8 ground truth and per-image metric sums
 Status launch_blur_wrap_u8(hipStream_t s, const uint8_t* gt, const float* k, int kh, int kw, int B, int H, int W, float* out);
 Status launch_u8_to_single(hipStream_t s, const uint8_t* gt, const uint8_t* mask, int B, int HW, float* out);
@@ -61,7 +68,8 @@ struct FftPlan {
 Status launch_fft_rows(hipStream_t s, const FftPlan& pw, float2* buf, const float* real_in, float pa, float pb,
                        int P, int H, int W, bool inverse);
 Status launch_fft_rows_real3(hipStream_t s, const FftPlan& pw, float2* buf, const float* real_in, float pa, float pb, float pm,
-                             int P, int H, int W, const StepDev* sp = nullptr);   // sp: pm = sp->tau
+                             int P, int H, int W, const StepDev* sp = nullptr,    // sp: pm = sp->tau
+                             const LoopDev* pil = nullptr);                       // pil (with sp): pm = the row's image's tau, per-image instantiation
 // columns forward only (used by pre_calculate)
 Status launch_fft_cols(hipStream_t s, const FftPlan& ph, float2* buf, int P, int H, int W, bool inverse);
 // fused column pass of data_solution: col-FFT -> closed-form spectral solve -> inverse col-FFT
@@ -75,6 +83,7 @@ struct SolveArgs {
     // fft2.hip, sf > 1: mean of F2B over the aliases [B][H/sf][W/sf/2+1] and the slot map of the permuted half-spectrum layout
     const float* invW = nullptr; const int* slot_col = nullptr;
     int images = 0;      // fft4.hip: set by the launcher (planes / 3)
+    const LoopDev* pil = nullptr;   // non-null (with sp): alpha = the plane's image's tau; selects the per-image instantiation
 };
 Status launch_fft_cols_solve(hipStream_t s, const FftPlan& ph, float2* buf, const SolveArgs& a, int B, int H, int W);
 // inverse rows with real output: out = Re(ifft_row)*oa + ob, optionally blended: out = base + g*(val - base)
@@ -89,11 +98,13 @@ Status launch_precalc_finish(hipStream_t s, const float2* FB, float2* FBFy_inout
 bool fft2_supported(int H, int W, int sf);
 // eps6 != null (loop only): the row source is x0 = clamp(c1 x - c2 eps) computed on the fly from x and the UNet output
 Status launch_rfft_rows(hipStream_t s, const float2* twN, const float* x, float pa, float pb, float pm, const StepDev* sp,
-                        float2* out, int P, int N, const float* eps6 = nullptr, int out_ch = 0, const int* slot_col = nullptr);
-struct RowsFuse { const float* eps6; int out_ch; };      // eps -> x0 prologue of the row pass (loop only)
+                        float2* out, int P, int N, const float* eps6 = nullptr, int out_ch = 0, const int* slot_col = nullptr, const LoopDev* pil = nullptr);
+// eps -> x0 prologue of the row pass (loop only); pil non-null (with sp): pm = the row's image's tau, per-image instantiation
+struct RowsFuse { const float* eps6; int out_ch; const LoopDev* pil; };
 // fused re-noise epilogue of the inverse row pass (loop only; xt == null: none): x_t <- renoise(x_t, x0'), noise host-fed (n2 [, n1] + step stride,
 // pointers re-read from lp when given) or Philox (n2 == null; seed / image offset from lp)
-struct RenoiseFuse { float* xt; const StepDev* sp; const LoopDev* lp; const float* n1; const float* n2; size_t stride; int with_n1; };
+// per_image: k1 / k2 and the Philox image number of the element's image (lp->img, lp->imgidx), per-image instantiation
+struct RenoiseFuse { float* xt; const StepDev* sp; const LoopDev* lp; const float* n1; const float* n2; size_t stride; int with_n1; int per_image; };
 Status launch_irfft_rows(hipStream_t s, const float2* twN, const float2* in, float* out, float scale, float oa, float ob,
                          const float* blend, float g, int P, int N, const RenoiseFuse& rn, const int* col_slot);
 // sf > 1 on the half-spectrum path: zero-stuffed real up-sampling (the alias-grouped column permutation and the alias mean of F2B: prox.hip)
@@ -103,7 +114,7 @@ Status launch_precalc_finish2(hipStream_t s, const float2* FB, float2* FBFy, flo
 // fft4.hip: one wave per N-point transform, column-major half spectrum [plane][slot][row] (NC slots per plane); N x N = 256 x 256 or 512 x 512, sf 1 / 2 / 4
 bool fft4_supported(int H, int W, int sf);
 Status launch_rfft4_rows(hipStream_t s, const float2* tw, int N, const float* x, float pa, float pb, float pm, const StepDev* sp, float2* out, int P, int NC,
-                         const float* eps6, int out_ch, const int* slot_col);
+                         const float* eps6, int out_ch, const int* slot_col, const LoopDev* pil = nullptr);
 Status launch_irfft4_rows(hipStream_t s, const float2* tw, int N, const float2* in, float* out, float scale, float oa, float ob, const float* blend, float g,
                           int P, int NC, const RenoiseFuse& rn, const int* col_slot);
 Status launch_cfft4_cols(hipStream_t s, const float2* tw, int N, float2* buf, const SolveArgs& a, bool solve, int P, int NC);

@@ -38,11 +38,16 @@ Status launch_xstart(hipStream_t s, const float* x, const float* out6, int out_c
 }
 
 // ---------------------------------------------------------------- masked prox
+// PI (here and below): the per-image instantiation of dpir_run_loop_per_image -- tau / k1 / k2 of the ELEMENT's image (the grid-stride loop crosses
+// image boundaries) from lp->img; the uniform instantiation is the code it was before
+template <bool PI>
 __global__ void prox_mask_kernel(float* x0, const float* y, const uint8_t* mask, float tau, float g, size_t total, const StepDev* sp,
                                  const LoopDev* lp) {
     if (sp) tau = sp->tau;
     if (lp) { y = lp->y; mask = lp->mask; }
+    const size_t chw = PI ? total / lp->B : 1;
     GRID_STRIDE(i, total) {
+        if (PI) tau = image_row(sp, lp, i / chw).x;
         float m = (float)mask[i];
         float v = x0[i];
         float num = m * (2.0f * y[i] - 1.0f) + tau * v;
@@ -51,8 +56,10 @@ __global__ void prox_mask_kernel(float* x0, const float* y, const uint8_t* mask,
     }
 }
 Status launch_prox_mask(hipStream_t s, float* x0, const float* y, const uint8_t* mask, float tau, float g, size_t total, const StepDev* sp,
-                        const LoopDev* lp) {
-    hipLaunchKernelGGL(prox_mask_kernel, grid1d(total), dim3(256), 0, s, x0, y, mask, tau, g, total, sp, lp);
+                        const LoopDev* lp, bool per_image) {
+    if (per_image && !(sp && lp)) return invalid("prox_mask: the per-image form reads the device step and loop blocks");
+    if (per_image) hipLaunchKernelGGL(prox_mask_kernel<true>, grid1d(total), dim3(256), 0, s, x0, y, mask, tau, g, total, sp, lp);
+    else hipLaunchKernelGGL(prox_mask_kernel<false>, grid1d(total), dim3(256), 0, s, x0, y, mask, tau, g, total, sp, lp);
     DPIR_HIP(hipGetLastError());
     return Status{};
 }
@@ -77,6 +84,7 @@ Status launch_repaint_mix(hipStream_t s, float* x, const float* y, const uint8_t
 }
 
 // ---------------------------------------------------------------- re-noise
+template <bool PI>
 __global__ void renoise_kernel(float* x, const float* x0, RenoiseCoef c, const float* n1, const float* n2, size_t total,
                                const StepDev* sp, size_t stride, const LoopDev* lp) {
     if (lp && stride) { if (n1) n1 = lp->n1; n2 = lp->n2; }     // host-fed noise: this batch's tensors
@@ -85,7 +93,9 @@ __global__ void renoise_kernel(float* x, const float* x0, RenoiseCoef c, const f
         if (n1) n1 += (size_t)sp->i * stride;
         n2 += (size_t)sp->i * stride;
     }
+    const size_t chw = PI ? total / lp->B : 1;
     GRID_STRIDE(i, total) {
+        if (PI) { const float4 im = image_row(sp, lp, i / chw); c.k1 = im.y; c.k2 = im.z; }
         float a = x0[i];
         float eps = (x[i] - c.sa_t * a) / c.s1m_t;
         float inner = c.q * eps;
@@ -96,8 +106,10 @@ __global__ void renoise_kernel(float* x, const float* x0, RenoiseCoef c, const f
     }
 }
 Status launch_renoise(hipStream_t s, float* x, const float* x0, const RenoiseCoef& c, const float* n1, const float* n2, size_t total,
-                      const StepDev* sp, size_t noise_step_stride, const LoopDev* lp) {
-    hipLaunchKernelGGL(renoise_kernel, grid1d(total), dim3(256), 0, s, x, x0, c, n1, n2, total, sp, noise_step_stride, lp);
+                      const StepDev* sp, size_t noise_step_stride, const LoopDev* lp, bool per_image) {
+    if (per_image && !(sp && lp)) return invalid("renoise: the per-image form reads the device step and loop blocks");
+    if (per_image) hipLaunchKernelGGL(renoise_kernel<true>, grid1d(total), dim3(256), 0, s, x, x0, c, n1, n2, total, sp, noise_step_stride, lp);
+    else hipLaunchKernelGGL(renoise_kernel<false>, grid1d(total), dim3(256), 0, s, x, x0, c, n1, n2, total, sp, noise_step_stride, lp);
     DPIR_HIP(hipGetLastError());
     return Status{};
 }
@@ -202,12 +214,14 @@ Status launch_band_resample(hipStream_t s, const float* in, const float* w, cons
 }
 
 // IBP update: x0 <- 2*( z + gamma*(y - d)[up nearest]/(1+rho) ) - 1, z = x0/2+.5   (main_ddpir.py:404-406)
+template <bool PI>
 __global__ void ibp_update_kernel(float* x0, const float* y, const float* d, float gamma, float rho, int sf, int H, int W, size_t total,
                                   const StepDev* sp, const LoopDev* lp) {
     if (sp) rho = sp->tau;
     if (lp) y = lp->y;
     GRID_STRIDE(i, total) {
         size_t plane = i / ((size_t)H * W);
+        if (PI) rho = image_row(sp, lp, plane / 3).x;
         size_t r = i - plane * (size_t)H * W;
         int yy = (int)(r / W), xx = (int)(r - (size_t)yy * W);
         int h = H / sf, w = W / sf;
@@ -219,9 +233,11 @@ __global__ void ibp_update_kernel(float* x0, const float* y, const float* d, flo
     }
 }
 Status launch_ibp_update(hipStream_t s, float* x0, const float* y, const float* d, float gamma, float rho, int sf, int P, int H, int W,
-                         const StepDev* sp, const LoopDev* lp) {
+                         const StepDev* sp, const LoopDev* lp, bool per_image) {
     size_t total = (size_t)P * H * W;
-    hipLaunchKernelGGL(ibp_update_kernel, grid1d(total), dim3(256), 0, s, x0, y, d, gamma, rho, sf, H, W, total, sp, lp);
+    if (per_image && !(sp && lp)) return invalid("ibp_update: the per-image form reads the device step and loop blocks");
+    if (per_image) hipLaunchKernelGGL(ibp_update_kernel<true>, grid1d(total), dim3(256), 0, s, x0, y, d, gamma, rho, sf, H, W, total, sp, lp);
+    else hipLaunchKernelGGL(ibp_update_kernel<false>, grid1d(total), dim3(256), 0, s, x0, y, d, gamma, rho, sf, H, W, total, sp, lp);
     DPIR_HIP(hipGetLastError());
     return Status{};
 }
@@ -273,25 +289,31 @@ Status launch_bicubic_up(hipStream_t s, const float* in, float* out, int P, int 
 
 // ---------------------------------------------------------------- Philox4x32-10 + Box-Muller (philox.h)
 // one thread produces 4 normals for elements [4j, 4j+4) of image (image_offset + n); counter = (j, image, stream)
+// PI: image number of row n = idx[n] (dpir_randn_indexed), or lp->imgidx[n] when idx is null (dpir_run_loop_per_image)
+template <bool PI>
 __global__ void randn_kernel(float* out, uint64_t seed, uint64_t stream_id, int64_t image_offset, size_t per_image, size_t total4,
-                             const StepDev* sp, const LoopDev* lp) {
+                             const StepDev* sp, const LoopDev* lp, const long long* idx) {
     // draw kinds per step: 1 = eta term, 2 = zeta term, 3 = repaint mix -> a stride of 4 keeps every (kind, step) pair distinct
     if (sp) stream_id += 4 * (uint64_t)sp->i;
     if (lp) { seed = lp->seed; image_offset = lp->image_offset; }
+    if (PI && !idx) idx = lp->imgidx;
     GRID_STRIDE(i, total4) {
         size_t q = (per_image + 3) / 4;
         size_t n = i / q, j = i - n * q;
         float z[4];
-        philox_normal4(seed, stream_id, (uint64_t)(image_offset + (int64_t)n), j, z);
+        philox_normal4(seed, stream_id, (uint64_t)(PI ? (int64_t)idx[n] : image_offset + (int64_t)n), j, z);
         float* o = out + n * per_image + j * 4;
         for (int e = 0; e < 4; ++e)
             if (j * 4 + e < per_image) o[e] = z[e];
     }
 }
 Status launch_randn(hipStream_t s, float* out, uint64_t seed, uint64_t stream_id, int64_t image_offset, int B, size_t per_image,
-                    const StepDev* sp, const LoopDev* lp) {
+                    const StepDev* sp, const LoopDev* lp, const long long* image_index, bool loop_index) {
     size_t total4 = (size_t)B * ((per_image + 3) / 4);
-    hipLaunchKernelGGL(randn_kernel, grid1d(total4), dim3(256), 0, s, out, seed, stream_id, image_offset, per_image, total4, sp, lp);
+    if (loop_index && !lp) return invalid("randn: the loop's image numbers live in the device loop block");
+    if (image_index || loop_index)
+        hipLaunchKernelGGL(randn_kernel<true>, grid1d(total4), dim3(256), 0, s, out, seed, stream_id, image_offset, per_image, total4, sp, lp, image_index);
+    else hipLaunchKernelGGL(randn_kernel<false>, grid1d(total4), dim3(256), 0, s, out, seed, stream_id, image_offset, per_image, total4, sp, lp, image_index);
     DPIR_HIP(hipGetLastError());
     return Status{};
 }

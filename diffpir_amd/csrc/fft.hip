@@ -57,19 +57,24 @@ __device__ __forceinline__ void load_twiddles(float2* lds_tw, const float2* tw, 
 
 // ---------------------------------------------------------------- rows, forward (optionally real input)
 // grid: total_rows / R blocks; block: 256 threads; R rows of W points
+// PI: the per-image instantiation of dpir_run_loop_per_image -- pm = tau of the ROW's image (a workgroup's R rows may span images)
+template <bool PI>
 __global__ __launch_bounds__(256) void fft_rows_fwd_kernel(float2* buf, const float* real_in, float pa, float pb, float pm,
-                                                            int W, int logW, int R, size_t total_rows, const float2* tw, const StepDev* sp) {
+                                                            int W, int logW, int R, size_t total_rows, const float2* tw, const StepDev* sp,
+                                                            const LoopDev* lp) {
     extern __shared__ __attribute__((aligned(16))) float2 sm[];
     float2* lds_tw = sm;
     float2* d = sm + (W >> 1);
     if (sp) pm = sp->tau;
     load_twiddles(lds_tw, tw, W);
     size_t row0 = (size_t)blockIdx.x * R;
+    const size_t rows_per_image = PI ? total_rows / lp->B : 1;
     for (int i = threadIdx.x; i < R * W; i += 256) {
         size_t row = row0 + (i >> logW);
         float2 v = make_float2(0.f, 0.f);
         if (row < total_rows) {
             size_t g = row * W + (i & (W - 1));
+            if (PI) pm = image_row(sp, lp, row / rows_per_image).x;
             if (real_in) v.x = (real_in[g] * pa + pb) * pm;
             else v = buf[g];
         }
@@ -112,7 +117,7 @@ __global__ __launch_bounds__(256) void ifft_rows_real_kernel(const float2* buf, 
 // ---------------------------------------------------------------- columns: FFT -> (solve) -> inverse FFT
 constexpr int CW = 16;   // columns per workgroup (128-byte row segments)
 
-template <int MODE>   // 0: forward only, 1: inverse only, 2: forward + solve + inverse
+template <int MODE, bool PI = false>   // 0: forward only, 1: inverse only, 2: forward + solve + inverse; PI: alpha = tau of the plane's image (a.pil)
 __global__ __launch_bounds__(256) void fft_cols_kernel(float2* buf, SolveArgs a, int H, int W, int logH, const float2* tw) {
     extern __shared__ __attribute__((aligned(16))) float2 sm[];
     float2* lds_tw = sm;
@@ -131,6 +136,7 @@ __global__ __launch_bounds__(256) void fft_cols_kernel(float2* buf, SolveArgs a,
     if (MODE != 1) batched_fft_lds<false>(d, CW, HS, logH, lds_tw);
     if (MODE == 2) {
         if (a.sp) a.alpha = a.sp->tau;
+        if (PI) a.alpha = image_row(a.sp, a.pil, plane / 3).x;
         // one work item per sf x sf alias tile (rows/cols are in bit-reversed storage order)
         const int sf = a.sf;
         const int n_img = plane / 3;
@@ -196,32 +202,35 @@ Status launch_fft_rows(hipStream_t s, const FftPlan& pw, float2* buf, const floa
     int R = W >= 1024 ? 1 : 1024 / W;
     size_t rows = (size_t)P * H;
     size_t lds = ((W >> 1) + (size_t)R * W) * sizeof(float2);
-    hipLaunchKernelGGL(fft_rows_fwd_kernel, dim3((unsigned)((rows + R - 1) / R)), dim3(256), lds, s, buf, real_in, pa, pb, 1.0f,
-                       W, pw.logN, R, rows, pw.tw, (const StepDev*)nullptr);
+    hipLaunchKernelGGL(fft_rows_fwd_kernel<false>, dim3((unsigned)((rows + R - 1) / R)), dim3(256), lds, s, buf, real_in, pa, pb, 1.0f,
+                       W, pw.logN, R, rows, pw.tw, (const StepDev*)nullptr, (const LoopDev*)nullptr);
     DPIR_HIP(hipGetLastError());
     return Status{};
 }
 
 // real input with the reference's two-step prologue: v = (x*pa + pb) * pm
 Status launch_fft_rows_real3(hipStream_t s, const FftPlan& pw, float2* buf, const float* real_in, float pa, float pb, float pm,
-                             int P, int H, int W, const StepDev* sp) {
+                             int P, int H, int W, const StepDev* sp, const LoopDev* pil) {
     DPIR_TRY(check_dims(H, W));
     if (pw.N != W) return invalid("fft rows: plan size mismatch");
     int R = W >= 1024 ? 1 : 1024 / W;
     size_t rows = (size_t)P * H;
     size_t lds = ((W >> 1) + (size_t)R * W) * sizeof(float2);
-    hipLaunchKernelGGL(fft_rows_fwd_kernel, dim3((unsigned)((rows + R - 1) / R)), dim3(256), lds, s, buf, real_in, pa, pb, pm,
-                       W, pw.logN, R, rows, pw.tw, sp);
+    if (pil && !sp) return invalid("fft rows: the per-image form reads the device step block");
+    if (pil) hipLaunchKernelGGL(fft_rows_fwd_kernel<true>, dim3((unsigned)((rows + R - 1) / R)), dim3(256), lds, s, buf, real_in, pa, pb, pm,
+                                W, pw.logN, R, rows, pw.tw, sp, pil);
+    else hipLaunchKernelGGL(fft_rows_fwd_kernel<false>, dim3((unsigned)((rows + R - 1) / R)), dim3(256), lds, s, buf, real_in, pa, pb, pm,
+                            W, pw.logN, R, rows, pw.tw, sp, pil);
     DPIR_HIP(hipGetLastError());
     return Status{};
 }
 
-template <int MODE>
+template <int MODE, bool PI = false>
 static Status launch_cols_mode(hipStream_t s, const FftPlan& ph, float2* buf, const SolveArgs& a, int P, int H, int W) {
     DPIR_TRY(check_dims(H, W));
     if (ph.N != H) return invalid("fft cols: plan size mismatch");
     size_t lds = ((H >> 1) + (size_t)CW * (H + 1)) * sizeof(float2);
-    auto fn = fft_cols_kernel<MODE>;
+    auto fn = fft_cols_kernel<MODE, PI>;
     static LdsAttrOnce attr;
     DPIR_HIP(attr.set(reinterpret_cast<const void*>(fn), 160 * 1024));
     hipLaunchKernelGGL(fn, dim3((unsigned)(P * (W / CW))), dim3(256), lds, s, buf, a, H, W, ph.logN, ph.tw);
@@ -237,7 +246,8 @@ Status launch_fft_cols(hipStream_t s, const FftPlan& ph, float2* buf, int P, int
 
 Status launch_fft_cols_solve(hipStream_t s, const FftPlan& ph, float2* buf, const SolveArgs& a, int B, int H, int W) {
     if (a.sf < 1 || (CW % a.sf) || (H % a.sf)) return Status{DPIR_ERR_UNSUPPORTED, "fft prox: sf must be 1, 2, 4, 8 or 16"};
-    return launch_cols_mode<2>(s, ph, buf, a, B * 3, H, W);
+    if (a.pil && !a.sp) return invalid("fft cols: the per-image form reads the device step block");
+    return a.pil ? launch_cols_mode<2, true>(s, ph, buf, a, B * 3, H, W) : launch_cols_mode<2>(s, ph, buf, a, B * 3, H, W);
 }
 
 Status launch_ifft_rows_real(hipStream_t s, const FftPlan& pw, const float2* buf, float* out, float scale, float oa, float ob,

@@ -28,27 +28,27 @@ namespace dpir {
 
 // The three passes as one kernel each; the bodies live in fft2_body.h (shared with the persistent single launch, fft3.hip).
 // rows forward: grid ceil(total_rows/2 / SLOTS), block THREADS = SLOTS*R.
-template <int R, int RJ, int THREADS>
+template <int R, int RJ, int THREADS, bool PI = false>
 __global__ __launch_bounds__(THREADS) void rfft_rows_kernel(const float* x, float pa, float pb, float pm, const StepDev* sp, float2* out,
                                                          int WP, size_t total_rows, const float2* tw, RowsFuse fu, const int* slot_col) {
     extern __shared__ __attribute__((aligned(16))) float2 sm2[];
-    rfft_rows_body<R, RJ, THREADS, false>(sm2, blockIdx.x, x, pa, pb, pm, sp, out, WP, total_rows, tw, fu, slot_col);
+    rfft_rows_body<R, RJ, THREADS, false, PI>(sm2, blockIdx.x, x, pa, pb, pm, sp, out, WP, total_rows, tw, fu, slot_col);
 }
-template <int R, int RJ, int THREADS>
+template <int R, int RJ, int THREADS, bool PI = false>
 __global__ __launch_bounds__(THREADS) void irfft_rows_kernel(const float2* in, float* out, float scale, float oa, float ob,
                                                           const float* blend_base, float g, int WP, size_t total_rows, const float2* tw, RenoiseFuse rn,
                                                           const int* col_slot) {
     extern __shared__ __attribute__((aligned(16))) float2 sm2[];
-    irfft_rows_body<R, RJ, THREADS, false>(sm2, blockIdx.x, in, out, scale, oa, ob, blend_base, g, WP, total_rows, tw, rn, col_slot, NoWait{});
+    irfft_rows_body<R, RJ, THREADS, false, NoWait, PI>(sm2, blockIdx.x, in, out, scale, oa, ob, blend_base, g, WP, total_rows, tw, rn, col_slot, NoWait{});
 }
 // columns: one workgroup per (plane, strip of CS = THREADS/R columns)
-template <int R, int RJ, int MODE, int THREADS, int SF>
+template <int R, int RJ, int MODE, int THREADS, int SF, bool PI = false>
 __global__ __launch_bounds__(THREADS) void cfft_cols_kernel(float2* buf, SolveArgs a, int WP, const float2* tw) {
     extern __shared__ __attribute__((aligned(16))) float2 sm2[];
     constexpr int CS = THREADS / R;
     const int strips = WP / CS;
     const int plane = blockIdx.x / strips;
-    cfft_cols_body<R, RJ, MODE, THREADS, SF, false>(sm2, plane, blockIdx.x - plane * strips, buf, a, WP, tw, NoWait{});
+    cfft_cols_body<R, RJ, MODE, THREADS, SF, false, NoWait, true, PI>(sm2, plane, blockIdx.x - plane * strips, buf, a, WP, tw, NoWait{});
 }
 
 // zero-stuffed up-sampling of the measurement as a REAL image (utils_sisr.upsample, :44-52)
@@ -96,13 +96,13 @@ static size_t rows_lds() {      // twiddles + max(exchange area, natural-order /
 template <int R, int RJ>
 static size_t cols_lds() { return (size_t)(R * RJ + (ColCfg<R>::THREADS / R) * (RJ * (R + 1) + 1)) * sizeof(float2); }
 
-template <int R, int RJ>
+template <int R, int RJ, bool PI = false>
 static Status rfft_rows_R(hipStream_t s, const float* x, float pa, float pb, float pm, const StepDev* sp, float2* out, int P, int N,
                           const float2* tw, RowsFuse fu, const int* slot_col) {
     int WP = fft2_padded_width(N);
     size_t rows = (size_t)P * N, pairs = (rows + 1) / 2;
     constexpr int SLOTS = ROW_THREADS / R;
-    auto fn = rfft_rows_kernel<R, RJ, ROW_THREADS>;
+    auto fn = rfft_rows_kernel<R, RJ, ROW_THREADS, PI>;
     static LdsAttrOnce attr;
     DPIR_HIP(attr.set(reinterpret_cast<const void*>(fn), 160 * 1024));
     const size_t lds = rows_lds<R, RJ>();
@@ -111,20 +111,26 @@ static Status rfft_rows_R(hipStream_t s, const float* x, float pa, float pb, flo
     return Status{};
 }
 Status launch_rfft_rows(hipStream_t s, const float2* twN, const float* x, float pa, float pb, float pm, const StepDev* sp,
-                        float2* out, int P, int N, const float* eps6, int out_ch, const int* slot_col) {
+                        float2* out, int P, int N, const float* eps6, int out_ch, const int* slot_col, const LoopDev* pil) {
     if (eps6 && !sp) return invalid("rfft_rows: the fused x0 prologue reads its coefficients from the device step block");
-    const RowsFuse fu{eps6, out_ch};
+    if (pil && !sp) return invalid("rfft_rows: the per-image form reads the device step block");
+    const RowsFuse fu{eps6, out_ch, pil};
+    if (pil) {
+        if (N == 512) return rfft_rows_R<16, 32, true>(s, x, pa, pb, pm, sp, out, P, N, twN, fu, slot_col);
+        return N == 256 ? rfft_rows_R<16, 16, true>(s, x, pa, pb, pm, sp, out, P, N, twN, fu, slot_col)
+                        : rfft_rows_R<8, 8, true>(s, x, pa, pb, pm, sp, out, P, N, twN, fu, slot_col);
+    }
     if (N == 512) return rfft_rows_R<16, 32>(s, x, pa, pb, pm, sp, out, P, N, twN, fu, slot_col);
     return N == 256 ? rfft_rows_R<16, 16>(s, x, pa, pb, pm, sp, out, P, N, twN, fu, slot_col) : rfft_rows_R<8, 8>(s, x, pa, pb, pm, sp, out, P, N, twN, fu, slot_col);
 }
 
-template <int R, int RJ>
+template <int R, int RJ, bool PI = false>
 static Status irfft_rows_R(hipStream_t s, const float2* in, float* out, float scale, float oa, float ob, const float* blend, float g,
                            int P, int N, const float2* tw, RenoiseFuse rn, const int* col_slot) {
     int WP = fft2_padded_width(N);
     size_t rows = (size_t)P * N, pairs = (rows + 1) / 2;
     constexpr int SLOTS = ROW_THREADS / R;
-    auto fn = irfft_rows_kernel<R, RJ, ROW_THREADS>;
+    auto fn = irfft_rows_kernel<R, RJ, ROW_THREADS, PI>;
     static LdsAttrOnce attr;
     DPIR_HIP(attr.set(reinterpret_cast<const void*>(fn), 160 * 1024));
     const size_t lds = rows_lds<R, RJ>();
@@ -135,12 +141,18 @@ static Status irfft_rows_R(hipStream_t s, const float2* in, float* out, float sc
 }
 Status launch_irfft_rows(hipStream_t s, const float2* twN, const float2* in, float* out, float scale, float oa, float ob,
                          const float* blend, float g, int P, int N, const RenoiseFuse& rn, const int* col_slot) {
+    if (rn.per_image && !(rn.xt && rn.sp && rn.lp)) return invalid("irfft_rows: the per-image form is the fused re-noise's");
+    if (rn.per_image) {
+        if (N == 512) return irfft_rows_R<16, 32, true>(s, in, out, scale, oa, ob, blend, g, P, N, twN, rn, col_slot);
+        return N == 256 ? irfft_rows_R<16, 16, true>(s, in, out, scale, oa, ob, blend, g, P, N, twN, rn, col_slot)
+                        : irfft_rows_R<8, 8, true>(s, in, out, scale, oa, ob, blend, g, P, N, twN, rn, col_slot);
+    }
     if (N == 512) return irfft_rows_R<16, 32>(s, in, out, scale, oa, ob, blend, g, P, N, twN, rn, col_slot);
     return N == 256 ? irfft_rows_R<16, 16>(s, in, out, scale, oa, ob, blend, g, P, N, twN, rn, col_slot)
                     : irfft_rows_R<8, 8>(s, in, out, scale, oa, ob, blend, g, P, N, twN, rn, col_slot);
 }
 
-template <int R, int RJ, int MODE, int SF = 1>
+template <int R, int RJ, int MODE, int SF = 1, bool PI = false>
 static Status cfft_cols_RM(hipStream_t s, float2* buf, const SolveArgs& a, int P, int N, const float2* tw) {
     int WP = fft2_padded_width(N);
     constexpr int COL_THREADS = ColCfg<R>::THREADS;
@@ -150,7 +162,7 @@ static Status cfft_cols_RM(hipStream_t s, float2* buf, const SolveArgs& a, int P
         if (a.sf != SF || SF < 2 || RJ % SF || CS % SF || !a.invW || !a.slot_col) return invalid("cfft_cols: bad sf > 1 arguments");
         extra = ((size_t)CS * (N / a.sf) + (size_t)(CS / a.sf) * (N / a.sf)) * sizeof(float2);
     }
-    auto fn = cfft_cols_kernel<R, RJ, MODE, COL_THREADS, SF>;
+    auto fn = cfft_cols_kernel<R, RJ, MODE, COL_THREADS, SF, PI>;
     static LdsAttrOnce attr;
     DPIR_HIP(attr.set(reinterpret_cast<const void*>(fn), 160 * 1024));
     const size_t lds = cols_lds<R, RJ>() + extra;
@@ -161,8 +173,11 @@ static Status cfft_cols_RM(hipStream_t s, float2* buf, const SolveArgs& a, int P
 Status launch_cfft_cols(hipStream_t s, const float2* twN, float2* buf, const SolveArgs& a, bool solve, int P, int N) {
     const int m = !solve ? 0 : (a.sf > 1 ? 3 : 2);
     if (m == 3 && a.sf != 2 && a.sf != 4) return invalid("cfft_cols: sf must be 2 or 4 on the half-spectrum path");
+    if (a.pil && !(solve && a.sp)) return invalid("cfft_cols: the per-image form is the solve's and reads the device step block");
 #define DPIR_COLS(RT, RJ_)                                                                                              \
     do {                                                                                                                \
+        if (a.pil && m == 3) return a.sf == 2 ? cfft_cols_RM<RT, RJ_, 3, 2, true>(s, buf, a, P, N, twN) : cfft_cols_RM<RT, RJ_, 3, 4, true>(s, buf, a, P, N, twN); \
+        if (a.pil) return cfft_cols_RM<RT, RJ_, 2, 1, true>(s, buf, a, P, N, twN);                                         \
         if (m == 3) return a.sf == 2 ? cfft_cols_RM<RT, RJ_, 3, 2>(s, buf, a, P, N, twN) : cfft_cols_RM<RT, RJ_, 3, 4>(s, buf, a, P, N, twN); \
         return m == 2 ? cfft_cols_RM<RT, RJ_, 2>(s, buf, a, P, N, twN) : cfft_cols_RM<RT, RJ_, 0>(s, buf, a, P, N, twN);    \
     } while (0)

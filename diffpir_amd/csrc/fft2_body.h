@@ -51,7 +51,9 @@ struct NoWait { __device__ __forceinline__ void operator()() const {} };
 // One slot = one PAIR of real rows; a job = SLOTS = THREADS / R consecutive pairs starting at pair bid * SLOTS.
 // Fused loop prologue (dpir_run_loop): when `eps6` is given, the row loaded is not x but the denoiser's clamped x0 prediction
 // x0 = clamp(c1*x - c2*eps, -1, 1) (gaussian_diffusion.py:297,328-333), evaluated while staging -- x0 is never materialised.
-template <int R, int RJ, int THREADS, bool PERSIST>
+// PI (all three bodies): the per-image instantiation of dpir_run_loop_per_image -- tau / k1 / k2 / the Philox image number of the row's (plane's,
+// element's) image from the device loop block (fu.pil, a.pil, rn.lp); PI = false is the code as it was.
+template <int R, int RJ, int THREADS, bool PERSIST, bool PI = false>
 __device__ __forceinline__ void rfft_rows_body(float2* sm2, size_t bid, const float* x, float pa, float pb, float pm, const StepDev* sp, float2* out,
                                                int WP, size_t total_rows, const float2* tw, RowsFuse fu, const int* slot_col) {
     constexpr int N = R * RJ, SLOTS = THREADS / R;
@@ -74,6 +76,7 @@ __device__ __forceinline__ void rfft_rows_body(float2* sm2, size_t bid, const fl
     const size_t pair = bid * SLOTS + slot;
     const size_t ra = 2 * pair, rb = 2 * pair + 1;
     const bool va = ra < total_rows, vb = rb < total_rows;
+    if (PI) pm = va ? image_row(sp, fu.pil, ra / ((size_t)3 * N)).x : 0.f;      // rows 2 pair and 2 pair + 1 are rows of one plane (N is even)
     // coalesced float4 loads of the block's 2*SLOTS rows into LDS, then the strided gather of the two-pass layout
     float* stage = reinterpret_cast<float*>(zbuf);          // [2*SLOTS][N + 4] floats == SLOTS*(N+4) float2
     {
@@ -154,7 +157,7 @@ __device__ __forceinline__ void rfft_rows_body(float2* sm2, size_t bid, const fl
 // STORED is the re-noised iterate (main_ddpir.py:451-456)
 //     eps = (x_t - sa_t x0') / s1m_t;   x = sa_p x0' + k1 (q eps + es n1) + k2 n2
 // written over x_t; n1 / n2 are host-fed tensors or Philox draws (same (seed, image, stream, counter) as randn_kernel).
-template <int R, int RJ, int THREADS, bool PERSIST, class Wait>
+template <int R, int RJ, int THREADS, bool PERSIST, class Wait, bool PI = false>
 __device__ __forceinline__ void irfft_rows_body(float2* sm2, size_t bid, const float2* in, float* out, float scale, float oa, float ob,
                                                 const float* blend_base, float g, int WP, size_t total_rows, const float2* tw, RenoiseFuse rn,
                                                 const int* col_slot, Wait wait) {
@@ -265,12 +268,14 @@ __device__ __forceinline__ void irfft_rows_body(float2* sm2, size_t bid, const f
                     z1[0] = t1.x; z1[1] = t1.y; z1[2] = t1.z; z1[3] = t1.w;
                 }
             } else {
-                const uint64_t img = (uint64_t)(rn.lp->image_offset + (long long)n);
+                const uint64_t img = (uint64_t)(PI ? rn.lp->imgidx[n] : rn.lp->image_offset + (long long)n);
                 philox_normal4(rn.lp->seed, 2 + 4 * (uint64_t)st.i, img, e >> 2, z2);
                 if (rn.with_n1) philox_normal4(rn.lp->seed, 1 + 4 * (uint64_t)st.i, img, e >> 2, z1);
             }
             const float4 xo = pre[j];
             const float xv[4] = {xo.x, xo.y, xo.z, xo.w}, av[4] = {q.x, q.y, q.z, q.w};
+            float k1 = st.k1, k2 = st.k2;
+            if (PI) { const float4 im = image_row(rn.sp, rn.lp, n); k1 = im.y; k2 = im.z; }
             float rv[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -278,8 +283,8 @@ __device__ __forceinline__ void irfft_rows_body(float2* sm2, size_t bid, const f
                 const float eps = (xv[u] - st.sa_t * a) / st.s1m_t;
                 float inner = st.q * eps;
                 if (rn.with_n1) inner = inner + st.es * z1[u];
-                float v = st.sa_p * a + st.k1 * inner;
-                v = v + st.k2 * z2[u];
+                float v = st.sa_p * a + k1 * inner;
+                v = v + k2 * z2[u];
                 rv[u] = v;
             }
             *reinterpret_cast<float4*>(rn.xt + gi) = make_float4(rv[0], rv[1], rv[2], rv[3]);
@@ -293,7 +298,7 @@ __device__ __forceinline__ void irfft_rows_body(float2* sm2, size_t bid, const f
 // A strip of CS = THREADS/R columns of one plane; thread = (column c, t).  MODE 0: forward only; MODE 2: forward ->
 // solve (sf = 1: FX = (FR - conj(FB) * (FB*FR)/(F2B+alpha)) / alpha, FR = FBFy + F(alpha x)) -> inverse; MODE 3: the same for sf > 1.
 // PERSIST: FBFy (what the solve adds to the transformed data; it does not depend on the row jobs) is requested before the wait.
-template <int R, int RJ, int MODE, int THREADS, int SF, bool PERSIST, class Wait, bool PREFETCH = true>
+template <int R, int RJ, int MODE, int THREADS, int SF, bool PERSIST, class Wait, bool PREFETCH = true, bool PI = false>
 __device__ __forceinline__ void cfft_cols_body(float2* sm2, int plane, int strip, float2* buf, const SolveArgs& a, int WP, const float2* tw, Wait wait) {
     constexpr int N = R * RJ, CS = THREADS / R;
     float2* twN = sm2;
@@ -330,6 +335,7 @@ __device__ __forceinline__ void cfft_cols_body(float2* sm2, int plane, int strip
     fft_two_pass<R, RJ, false>(v, t, xch + c * XST, twN);
     if (MODE == 2) {
         float alpha = a.sp ? a.sp->tau : a.alpha;
+        if (PI) alpha = image_row(a.sp, a.pil, plane / 3).x;
         const int n_img = plane / 3;
         const float2* FB = a.FB + (size_t)n_img * N * WP + col;
         const float* F2B = a.F2B + (size_t)n_img * N * WP + col;
@@ -351,6 +357,7 @@ __device__ __forceinline__ void cfft_cols_body(float2* sm2, int plane, int strip
         // sf > 1 (utils_sisr.py:65-75 with `splits`): FBR = mean over the sf x sf aliases of FB * FR, FX = (FR - conj(FB) R~) / alpha with
         // R = FBR / (invW + alpha) tiled back over the aliases.  Slot c of the strip = alias b = c % sf of fold group c / sf.
         float alpha = a.sp ? a.sp->tau : a.alpha;
+        if (PI) alpha = image_row(a.sp, a.pil, plane / 3).x;
         constexpr int sf = SF, Hs = N / SF, KH = RJ / SF, ngrp = CS / SF;
         const int s0 = strip * CS;                                        // first slot of the strip
         const int QW = N / sf / 2 + 1;                                    // fold groups per row: q <= Ws / 2

@@ -16,20 +16,20 @@
 namespace dpir {
 
 // the three passes as one launch each (named kernels: they are what the rocprofv3 summaries under profiles/ list) (bodies: fft4_body.h)
-template <int N>
+template <int N, bool PI = false>
 __global__ __launch_bounds__(RTHREADS) void rfft4_rows_kernel(const float* x, float pa, float pb, float pm, const StepDev* sp, float2* out, int NC,
                                                              const float2* tw, RowsFuse fu, const int* slot_col) {
     extern __shared__ __attribute__((aligned(16))) float2 sm4[];
-    rows4_body<N, false>(sm4, blockIdx.x, x, pa, pb, pm, sp, out, NC, tw, WaveTwN<N>{}, fu, slot_col);
+    rows4_body<N, false, PI>(sm4, blockIdx.x, x, pa, pb, pm, sp, out, NC, tw, WaveTwN<N>{}, fu, slot_col);
 }
-template <int N>
+template <int N, bool PI = false>
 __global__ __launch_bounds__(RTHREADS) void irfft4_rows_kernel(const float2* in, float* out, float scale, float oa, float ob, const float* blend_base, float g,
                                                               int NC, const float2* tw, RenoiseFuse rn, const int* col_slot) {
     extern __shared__ __attribute__((aligned(16))) float2 sm4[];
-    irows4_body<N, false>(sm4, blockIdx.x, in, out, scale, oa, ob, blend_base, g, NC, tw, WaveTwN<N>{}, rn, col_slot, NoWait4{});
+    irows4_body<N, false, NoWait4, PI>(sm4, blockIdx.x, in, out, scale, oa, ob, blend_base, g, NC, tw, WaveTwN<N>{}, rn, col_slot, NoWait4{});
 }
 // grid: P * ceil(NC / 4) workgroups of four waves: one item each
-template <int MODE, int SF, int N>
+template <int MODE, int SF, int N, bool PI = false>
 __global__ __launch_bounds__(THREADS4) void cfft4_cols_kernel(float2* buf, SolveArgs a, int NC, const float2* tw) {
     extern __shared__ __attribute__((aligned(16))) float2 sm4[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(THREADS4) void cfft4_cols_kernel(float2* buf, Solve
         item = blockIdx.x - plane * groups;
     }
     const WaveTwN<N> w = wave_tw_load<N>(tw, lane);
-    cols4_item_body<MODE, SF, N>(sm4 + wave * wlds(N), sm4 + WAVES * wlds(N), plane, item, wave, buf, a, NC, w, NoWait4{});
+    cols4_item_body<MODE, SF, N, NoWait4, PI>(sm4 + wave * wlds(N), sm4 + WAVES * wlds(N), plane, item, wave, buf, a, NC, w, NoWait4{});
 }
 
 bool fft4_supported(int H, int W, int sf) { return H == W && (H == 256 || H == 512) && (sf == 1 || sf == 2 || sf == 4); }
@@ -58,42 +58,48 @@ bool fft4_supported(int H, int W, int sf) { return H == W && (H == 256 || H == 5
 static size_t lds4(int N, bool fold, int sf) { return ((size_t)WAVES * wlds(N) + (fold ? (size_t)WAVES * (N / sf) : 0)) * sizeof(float2); }
 static size_t lds4_rows(int N, int NC) { return (size_t)RW * wlds(N) * sizeof(float2) + (size_t)NC * TST * sizeof(float4); }
 
-template <int N>
+template <int N, bool PI = false>
 static Status rows_fwd(hipStream_t s, const float2* tw, const float* x, float pa, float pb, float pm, const StepDev* sp, float2* out, int P, int NC,
-                       const float* eps6, int out_ch, const int* slot_col) {
+                       const float* eps6, int out_ch, const int* slot_col, const LoopDev* pil) {
     const size_t pairs = (size_t)P * N / 2;             // a multiple of RW: no partial workgroup
     static LdsAttrOnce attr;      // dynamic LDS above 64 KB (the 512-point row passes: 8 exchange tiles + the [slot][9] line tile = 74 KB) is allowed per kernel, once
-    DPIR_HIP(attr.set(reinterpret_cast<const void*>(rfft4_rows_kernel<N>), 160 * 1024));
-    hipLaunchKernelGGL(rfft4_rows_kernel<N>, dim3((unsigned)(pairs / RW)), dim3(RTHREADS), lds4_rows(N, NC), s, x, pa, pb, pm, sp, out, NC, tw,
-                       RowsFuse{eps6, out_ch}, slot_col);
+    DPIR_HIP(attr.set(reinterpret_cast<const void*>(rfft4_rows_kernel<N, PI>), 160 * 1024));
+    hipLaunchKernelGGL((rfft4_rows_kernel<N, PI>), dim3((unsigned)(pairs / RW)), dim3(RTHREADS), lds4_rows(N, NC), s, x, pa, pb, pm, sp, out, NC, tw,
+                       RowsFuse{eps6, out_ch, pil}, slot_col);
     DPIR_HIP(hipGetLastError());
     return Status{};
 }
 Status launch_rfft4_rows(hipStream_t s, const float2* tw, int N, const float* x, float pa, float pb, float pm, const StepDev* sp, float2* out, int P, int NC,
-                         const float* eps6, int out_ch, const int* slot_col) {
+                         const float* eps6, int out_ch, const int* slot_col, const LoopDev* pil) {
     if (eps6 && !sp) return invalid("rfft4_rows: the fused x0 prologue reads its coefficients from the device step block");
-    if (N == 256) return rows_fwd<256>(s, tw, x, pa, pb, pm, sp, out, P, NC, eps6, out_ch, slot_col);
-    if (N == 512) return rows_fwd<512>(s, tw, x, pa, pb, pm, sp, out, P, NC, eps6, out_ch, slot_col);
+    if (pil && !sp) return invalid("rfft4_rows: the per-image form reads the device step block");
+    if (pil && N == 256) return rows_fwd<256, true>(s, tw, x, pa, pb, pm, sp, out, P, NC, eps6, out_ch, slot_col, pil);
+    if (pil && N == 512) return rows_fwd<512, true>(s, tw, x, pa, pb, pm, sp, out, P, NC, eps6, out_ch, slot_col, pil);
+    if (N == 256) return rows_fwd<256>(s, tw, x, pa, pb, pm, sp, out, P, NC, eps6, out_ch, slot_col, pil);
+    if (N == 512) return rows_fwd<512>(s, tw, x, pa, pb, pm, sp, out, P, NC, eps6, out_ch, slot_col, pil);
     return invalid("rfft4_rows: N must be 256 or 512");
 }
-template <int N>
+template <int N, bool PI = false>
 static Status rows_inv(hipStream_t s, const float2* tw, const float2* in, float* out, float scale, float oa, float ob, const float* blend, float g, int P,
                        int NC, RenoiseFuse rn, const int* col_slot) {
     const size_t pairs = (size_t)P * N / 2;
     static LdsAttrOnce attr;
-    DPIR_HIP(attr.set(reinterpret_cast<const void*>(irfft4_rows_kernel<N>), 160 * 1024));
-    hipLaunchKernelGGL(irfft4_rows_kernel<N>, dim3((unsigned)(pairs / RW)), dim3(RTHREADS), lds4_rows(N, N / 2 + 1), s, in, out, scale, oa, ob, blend, g, NC,
+    DPIR_HIP(attr.set(reinterpret_cast<const void*>(irfft4_rows_kernel<N, PI>), 160 * 1024));
+    hipLaunchKernelGGL((irfft4_rows_kernel<N, PI>), dim3((unsigned)(pairs / RW)), dim3(RTHREADS), lds4_rows(N, N / 2 + 1), s, in, out, scale, oa, ob, blend, g, NC,
                        tw, rn, col_slot);
     DPIR_HIP(hipGetLastError());
     return Status{};
 }
 Status launch_irfft4_rows(hipStream_t s, const float2* tw, int N, const float2* in, float* out, float scale, float oa, float ob, const float* blend, float g,
                           int P, int NC, const RenoiseFuse& rn, const int* col_slot) {
+    if (rn.per_image && !(rn.xt && rn.sp && rn.lp)) return invalid("irfft4_rows: the per-image form is the fused re-noise's");
+    if (rn.per_image && N == 256) return rows_inv<256, true>(s, tw, in, out, scale, oa, ob, blend, g, P, NC, rn, col_slot);
+    if (rn.per_image && N == 512) return rows_inv<512, true>(s, tw, in, out, scale, oa, ob, blend, g, P, NC, rn, col_slot);
     if (N == 256) return rows_inv<256>(s, tw, in, out, scale, oa, ob, blend, g, P, NC, rn, col_slot);
     if (N == 512) return rows_inv<512>(s, tw, in, out, scale, oa, ob, blend, g, P, NC, rn, col_slot);
     return invalid("irfft4_rows: N must be 256 or 512");
 }
-template <int N>
+template <int N, bool PI = false>
 static Status cols(hipStream_t s, const float2* tw, float2* buf, const SolveArgs& a_in, bool solve, int P, int NC) {
     const int groups = (NC + WAVES - 1) / WAVES;
     unsigned grid = (unsigned)(P * groups);
@@ -104,16 +110,19 @@ static Status cols(hipStream_t s, const float2* tw, float2* buf, const SolveArgs
         grid = 3u * (unsigned)(((size_t)(P / 3) * groups + 7) / 8 * 8);
     }
     if (!solve) hipLaunchKernelGGL((cfft4_cols_kernel<0, 1, N>), dim3(grid), dim3(THREADS4), lds4(N, false, 1), s, buf, a, NC, tw);
-    else if (a.sf == 1) hipLaunchKernelGGL((cfft4_cols_kernel<2, 1, N>), dim3(grid), dim3(THREADS4), lds4(N, false, 1), s, buf, a, NC, tw);
+    else if (a.sf == 1) hipLaunchKernelGGL((cfft4_cols_kernel<2, 1, N, PI>), dim3(grid), dim3(THREADS4), lds4(N, false, 1), s, buf, a, NC, tw);
     else {
         if ((a.sf != 2 && a.sf != 4) || !a.invW || !a.slot_col || NC % a.sf) return invalid("cfft4_cols: bad sf > 1 arguments");
-        if (a.sf == 2) hipLaunchKernelGGL((cfft4_cols_kernel<3, 2, N>), dim3(grid), dim3(THREADS4), lds4(N, true, 2), s, buf, a, NC, tw);
-        else hipLaunchKernelGGL((cfft4_cols_kernel<3, 4, N>), dim3(grid), dim3(THREADS4), lds4(N, true, 4), s, buf, a, NC, tw);
+        if (a.sf == 2) hipLaunchKernelGGL((cfft4_cols_kernel<3, 2, N, PI>), dim3(grid), dim3(THREADS4), lds4(N, true, 2), s, buf, a, NC, tw);
+        else hipLaunchKernelGGL((cfft4_cols_kernel<3, 4, N, PI>), dim3(grid), dim3(THREADS4), lds4(N, true, 4), s, buf, a, NC, tw);
     }
     DPIR_HIP(hipGetLastError());
     return Status{};
 }
 Status launch_cfft4_cols(hipStream_t s, const float2* tw, int N, float2* buf, const SolveArgs& a, bool solve, int P, int NC) {
+    if (a.pil && !(solve && a.sp)) return invalid("cfft4_cols: the per-image form is the solve's and reads the device step block");
+    if (a.pil && N == 256) return cols<256, true>(s, tw, buf, a, solve, P, NC);
+    if (a.pil && N == 512) return cols<512, true>(s, tw, buf, a, solve, P, NC);
     if (N == 256) return cols<256>(s, tw, buf, a, solve, P, NC);
     if (N == 512) return cols<512>(s, tw, buf, a, solve, P, NC);
     return invalid("cfft4_cols: N must be 256 or 512");

@@ -32,7 +32,9 @@ __device__ __forceinline__ void wsync() { wave_sync(); }
 // ------------------------------------------------------------------------------------------------ rows forward
 // grid: pairs / 8 workgroups x 512 threads; wave = one row pair.  NC = stored columns (slots) per plane; slot_col (sf > 1): slot -> column | mirror << 16, -1 padding.
 // job = 8 row pairs (one per wave) = 16 rows of one plane: job index `wg` = plane * 16 + m.  TWREG: the per-lane twiddles are already in `w`.
-template <int N, bool TWREG>
+// PI (all three bodies): the per-image instantiation of dpir_run_loop_per_image -- tau / k1 / k2 / the Philox image number of the plane's (element's)
+// image from the device loop block (fu.pil, a.pil, rn.lp); PI = false is the code as it was.
+template <int N, bool TWREG, bool PI = false>
 __device__ __forceinline__ void rows4_body(float2* sm4, size_t wg, const float* x, float pa, float pb, float pm, const StepDev* sp, float2* out, int NC,
                                            const float2* tw, WaveTwN<N> w, RowsFuse fu, const int* slot_col) {
     constexpr int R = N / 64, Q = N / 256, WL = wlds(N);               // Q float4 per lane and row
@@ -44,6 +46,7 @@ __device__ __forceinline__ void rows4_body(float2* sm4, size_t wg, const float* 
     const size_t plane = pair / (N / 2);
     const int r = pair_row((int)(pair - plane * (N / 2)));             // rows r and r + 64 of the plane
     const size_t ra = plane * N + r;
+    if (PI) pm = image_row(sp, fu.pil, plane / 3).x;
     // every global request of the wave first (rows, eps, then the per-lane twiddles): ONE memory round trip before the transform
     float4 qa[Q], qb[Q], ea[Q], eb[Q];
 #pragma unroll
@@ -127,7 +130,7 @@ __device__ __forceinline__ void rows4_body(float2* sm4, size_t wg, const float* 
 
 // ------------------------------------------------------------------------------------------------ rows inverse
 // job index `wg` = plane * 16 + m; wait(): called by all threads after the requests that do not depend on the column pass, before those that do
-template <int N, bool TWREG, class Wait>
+template <int N, bool TWREG, class Wait, bool PI = false>
 __device__ __forceinline__ void irows4_body(float2* sm4, size_t wg, const float2* in, float* out, float scale, float oa, float ob, const float* blend_base, float g,
                                             int NC, const float2* tw, WaveTwN<N> w, RenoiseFuse rn, const int* col_slot, Wait wait) {
     constexpr int R = N / 64, Q = N / 256, WL = wlds(N);
@@ -221,11 +224,13 @@ __device__ __forceinline__ void irows4_body(float2* sm4, size_t wg, const float2
                     z1[0] = t1.x; z1[1] = t1.y; z1[2] = t1.z; z1[3] = t1.w;
                 }
             } else {
-                const uint64_t img = (uint64_t)(rn.lp->image_offset + (long long)n);
+                const uint64_t img = (uint64_t)(PI ? rn.lp->imgidx[n] : rn.lp->image_offset + (long long)n);
                 philox_normal4(rn.lp->seed, 2 + 4 * (uint64_t)sd.i, img, e >> 2, z2);
                 if (rn.with_n1) philox_normal4(rn.lp->seed, 1 + 4 * (uint64_t)sd.i, img, e >> 2, z1);
             }
             const float xv[4] = {pre.x, pre.y, pre.z, pre.w}, av[4] = {q.x, q.y, q.z, q.w};
+            float k1 = sd.k1, k2 = sd.k2;
+            if (PI) { const float4 im = image_row(rn.sp, rn.lp, n); k1 = im.y; k2 = im.z; }
             float rv[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -233,8 +238,8 @@ __device__ __forceinline__ void irows4_body(float2* sm4, size_t wg, const float2
                 const float eps = (xv[u] - sd.sa_t * a) / sd.s1m_t;
                 float inner = sd.q * eps;
                 if (rn.with_n1) inner = inner + sd.es * z1[u];
-                float vv = sd.sa_p * a + sd.k1 * inner;
-                vv = vv + sd.k2 * z2[u];
+                float vv = sd.sa_p * a + k1 * inner;
+                vv = vv + k2 * z2[u];
                 rv[u] = vv;
             }
             *reinterpret_cast<float4*>(rn.xt + gi) = make_float4(rv[0], rv[1], rv[2], rv[3]);
@@ -253,7 +258,7 @@ __device__ __forceinline__ void irows4_body(float2* sm4, size_t wg, const float2
 // (A variant in which a workgroup WALKED several items with register prefetch of the next one measured slower, 29 vs 26 us per batch-16 apply; and
 // 16-byte lane loads -- the position order -- are not faster than 8-byte ones here: the pass is bound by its load -> transform -> store chain with
 // every wave of the launch in the same phase, profiles/r06.)
-template <int MODE, int SF, int N, class Wait>
+template <int MODE, int SF, int N, class Wait, bool PI = false>
 __device__ __forceinline__ void cols4_item_body(float2* lds, float2* fold, int plane, int item, int wave, float2* buf, const SolveArgs& a, int NC,
                                                 const WaveTwN<N>& w, Wait wait) {
     constexpr int R = N / 64;
@@ -285,7 +290,7 @@ __device__ __forceinline__ void cols4_item_body(float2* lds, float2* fold, int p
     }
     wave_fft<false>(v, w, lds, lane);
     if (MODE == 2) {
-        const float alpha = a.sp ? a.sp->tau : a.alpha;
+        const float alpha = PI ? image_row(a.sp, a.pil, plane / 3).x : (a.sp ? a.sp->tau : a.alpha);
         // the two quotients of the cancelling term keep the exact division of the reference's expression; the final (uniform) division by
         // alpha acts on the difference AFTER the cancellation, where one more rounding is not amplified: a multiplication by 1 / alpha
         const float inv_alpha = 1.0f / alpha;
@@ -303,7 +308,7 @@ __device__ __forceinline__ void cols4_item_body(float2* lds, float2* fold, int p
     }
     if (MODE == 3) {
         // slot s = sf q + b: alias b of fold group q.  Row aliases u + a Hs (Hs = N / sf, a multiple of 64) are registers of ONE lane.
-        const float alpha = a.sp ? a.sp->tau : a.alpha;
+        const float alpha = PI ? image_row(a.sp, a.pil, plane / 3).x : (a.sp ? a.sp->tau : a.alpha);
         const float inv_alpha = 1.0f / alpha;
         constexpr int Hs = N / SF, KH = R / SF;                         // KH folded values per lane
         const int QW = N / SF / 2 + 1;

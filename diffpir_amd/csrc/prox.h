@@ -54,13 +54,14 @@ Status prox_precalc(dpir_engine* e, const float* y, const float* k, int kh, int 
 Status prox_create(dpir_engine* e, const float* y, const float* k, int kh, int kw, int sf, int B, int H, int W, ProxState* st);
 // natural-order copy of FB (which 0), F2B (1) or FBFy (2) to the host
 Status prox_read(dpir_engine* e, const ProxState& st, int which, void* host_dst, size_t cap_bytes);
-// out = blend ? base + g*((ifft)*oa+ob - base) : (ifft)*oa+ob ; input pre-map v = (x*pa+pb)*alpha; sp != null: alpha = sp->tau
+// out = blend ? base + g*((ifft)*oa+ob - base) : (ifft)*oa+ob ; input pre-map v = (x*pa+pb)*alpha; sp != null: alpha = sp->tau;
+// pil != null (with sp; dpir_run_loop_per_image): alpha = tau of each plane's image from the device loop block, the per-image kernels
 Status prox_data_solution(dpir_engine* e, const ProxState& st, const float* x, float pa, float pb, float alpha, float* out, float oa, float ob,
-                          const float* blend_base, float g, const StepDev* sp = nullptr);
+                          const float* blend_base, float g, const StepDev* sp = nullptr, const LoopDev* pil = nullptr);
 // The restoration loop's data step on a half layout, fused into three launches: eps -> clamped x0 in the row-FFT prologue, spectral solve between the
 // column FFTs, re-noise (+ Philox) in the inverse row-FFT epilogue; x0 is never materialised.  *ran = false (nothing launched) when the step is not eligible.
 Status prox_fused_step(dpir_engine* e, const ProxState& st, const dpir_loop_desc& d, bool last, bool with_n1, float* x, const float* out6, float* x0,
-                       const StepDev* cur, const LoopDev* lp, bool* ran);
+                       const StepDev* cur, const LoopDev* lp, bool* ran, bool per_image = false);
 // measurement: n back-to-back applies between two events, eagerly or as one captured graph -> device microseconds per apply
 Status prox_apply_timed(dpir_engine* e, const ProxState& st, float* x0, float tau, float guidance, int n, bool use_graph, float* us_per_apply);
 

@@ -176,8 +176,8 @@ Status prox_ensure(dpir_engine* e, int sf, int B, int H, int W, ProxState* st, b
 // ------------------------------------------------------------------------------------------ the half-spectrum passes, whichever kernels run them
 static Status half_rows_fwd(hipStream_t s, const ProxState& st, const float2* tw, const float* x, float pa, float pb, float pm, const StepDev* sp, float2* out,
                             int P, RowsFuse fu) {
-    if (st.layout == ProxLayout::HalfCols) return launch_rfft4_rows(s, tw, st.W, x, pa, pb, pm, sp, out, P, st.WP, fu.eps6, fu.out_ch, st.slot_col);
-    return launch_rfft_rows(s, tw, x, pa, pb, pm, sp, out, P, st.W, fu.eps6, fu.out_ch, st.slot_col);
+    if (st.layout == ProxLayout::HalfCols) return launch_rfft4_rows(s, tw, st.W, x, pa, pb, pm, sp, out, P, st.WP, fu.eps6, fu.out_ch, st.slot_col, fu.pil);
+    return launch_rfft_rows(s, tw, x, pa, pb, pm, sp, out, P, st.W, fu.eps6, fu.out_ch, st.slot_col, fu.pil);
 }
 // solve == null: plain forward column transforms (pre_calculate)
 static Status half_cols(hipStream_t s, const ProxState& st, const float2* tw, float2* buf, const SolveArgs* solve, int P) {
@@ -309,17 +309,19 @@ static Status prox_passes(dpir_engine* e, const ProxState& st, const ProxPassArg
     hipStream_t s = e->stream;
     ProfScope ps(&e->prof, PC_FFT);
     const int P = st.B * 3;
-    const SolveArgs solve{st.FB, st.F2B, st.FBFy, a.alpha, st.sf, a.sp, st.invW, st.slot_col};
+    SolveArgs solve{st.FB, st.F2B, st.FBFy, a.alpha, st.sf, a.sp, st.invW, st.slot_col};
+    solve.pil = a.fu.pil;                   // both uses of tau (the row scale and the solve's alpha) take the same image's value
     DPIR_TRY(half_rows_fwd(s, st, tw, a.x, a.pa, a.pb, a.alpha, a.sp, hbuf, P, a.fu));
     DPIR_TRY(half_cols(s, st, tw, hbuf, &solve, P));
     return half_rows_inv(s, st, tw, hbuf, a.out, 1.0f / ((float)st.H * (float)st.W), a.oa, a.ob, a.blend_base, a.g, P, a.rn);
 }
 
 Status prox_data_solution(dpir_engine* e, const ProxState& st, const float* x, float pa, float pb, float alpha, float* out, float oa, float ob,
-                          const float* blend_base, float g, const StepDev* sp) {
+                          const float* blend_base, float g, const StepDev* sp, const LoopDev* pil) {
     if (!sp && !(alpha > 0.f)) return invalid("data_solution: alpha must be > 0");
+    if (pil && !sp) return invalid("data_solution: the per-image form reads the device step block");
     if (st.half())
-        return prox_passes(e, st, ProxPassArgs{x, pa, pb, alpha, sp, RowsFuse{}, out, oa, ob, (blend_base && g != 1.0f) ? blend_base : nullptr, g, RenoiseFuse{}});
+        return prox_passes(e, st, ProxPassArgs{x, pa, pb, alpha, sp, RowsFuse{nullptr, 0, pil}, out, oa, ob, (blend_base && g != 1.0f) ? blend_base : nullptr, g, RenoiseFuse{}});
     FftPlan ph, pw;
     DPIR_TRY(e->prox_cache.plan(st.H, &ph));
     DPIR_TRY(e->prox_cache.plan(st.W, &pw));
@@ -327,8 +329,9 @@ Status prox_data_solution(dpir_engine* e, const ProxState& st, const float* x, f
     DPIR_TRY(e->ws.getT("prox#buf", (size_t)st.B * 3 * st.H * st.W, &buf));
     hipStream_t s = e->stream;
     ProfScope ps(&e->prof, PC_FFT);
-    DPIR_TRY(launch_fft_rows_real3(s, pw, buf, x, pa, pb, alpha, st.B * 3, st.H, st.W, sp));
+    DPIR_TRY(launch_fft_rows_real3(s, pw, buf, x, pa, pb, alpha, st.B * 3, st.H, st.W, sp, pil));
     SolveArgs a{st.FB, st.F2B, st.FBFy, alpha, st.sf, sp};
+    a.pil = pil;
     DPIR_TRY(launch_fft_cols_solve(s, ph, buf, a, st.B, st.H, st.W));
     float scale = 1.0f / ((float)st.H * (float)st.W);
     DPIR_TRY(launch_ifft_rows_real(s, pw, buf, out, scale, oa, ob, blend_base, g, st.B * 3, st.H, st.W));
@@ -336,13 +339,13 @@ Status prox_data_solution(dpir_engine* e, const ProxState& st, const float* x, f
 }
 
 Status prox_fused_step(dpir_engine* e, const ProxState& st, const dpir_loop_desc& d, bool last, bool with_n1, float* x, const float* out6, float* x0,
-                       const StepDev* cur, const LoopDev* lp, bool* ran) {
+                       const StepDev* cur, const LoopDev* lp, bool* ran, bool per_image) {
     *ran = !last && d.generate_mode == 0 && !d.first_order && (d.task == DPIR_TASK_DEBLUR || d.task == DPIR_TASK_SR_BLUR) && st.half() && d.guidance == 1.0f;
     if (!*ran) return Status{};
     if (with_n1 && d.noise_n1_dev && !d.noise_n2_dev) return invalid("host n1 noise requires host n2 noise");
     const size_t total = (size_t)st.B * 3 * st.H * st.W;
-    const RenoiseFuse rn{x, cur, lp, d.noise_n1_dev, d.noise_n2_dev, d.noise_n2_dev ? total : 0, with_n1 ? 1 : 0};
-    DPIR_TRY(prox_passes(e, st, ProxPassArgs{x, 0.5f, 0.5f, 1.f, cur, RowsFuse{out6, e->net.desc.out_channels}, x0, 2.f, -1.f, nullptr, 1.f, rn}));
+    const RenoiseFuse rn{x, cur, lp, d.noise_n1_dev, d.noise_n2_dev, d.noise_n2_dev ? total : 0, with_n1 ? 1 : 0, per_image ? 1 : 0};
+    DPIR_TRY(prox_passes(e, st, ProxPassArgs{x, 0.5f, 0.5f, 1.f, cur, RowsFuse{out6, e->net.desc.out_channels, per_image ? lp : nullptr}, x0, 2.f, -1.f, nullptr, 1.f, rn}));
     DPIR_HIP(hipGetLastError());
     return Status{};
 }

@@ -337,7 +337,7 @@ def check_dps_sharding(engine, cfg, n_images: int, world: int):
 
 def restore_sharded(engine, cfg, y, k=None, mask=None, labels=None, *, rank: int, world: int, image_offset: int = 0, seed: int = 0,
                     use_graph: bool = True, noise_source: str = "device", host_noise=None, cache: dict = None,
-                    skip_dead_final_eval: bool = False, progress=None):
+                    skip_dead_final_eval: bool = False, progress=None, per_image=None):
     """One GLOBAL batch restored by `world` ranks: rank r runs images [lo, hi) of the batch on its own GPU (its own engine,
     its own replayed graph, no collective inside the loop) and ONE all-gather of the uint8 results ends the batch
     (SURVEY.md 8e).  y / k / mask / labels are the global batch (numpy, host); every rank slices its block.
@@ -345,12 +345,17 @@ def restore_sharded(engine, cfg, y, k=None, mask=None, labels=None, *, rank: int
     Device noise is keyed by the global image index (image_offset + lo + b), so the gathered result is independent of
     `world`.  Host noise (parity mode) must be pre-drawn for the GLOBAL batch: host_noise = (init, n1, n2[, nrp]) as returned
     by restore.draw_host_noise for the global shape; each rank uploads its image slice.
+    per_image: a restore.PerImage for the GLOBAL batch; each rank takes its rows [lo, hi) of every array (without image_index a row's noise key
+    stays image_offset + lo + b, as in a call without it).
     Returns (uint8 [n_images, H, W, 3] on every rank as an engine-owned DeviceArray, local fp32 DeviceArray)."""
     from . import restore
     if progress is not None:
         raise NotImplementedError("restore_sharded: a progressive strip (progress=) is not gathered across ranks; run restore.restore_batch "
                                   "on one GPU for save_progressive / log_process")
     n = y.shape[0]
+    if per_image is not None:
+        restore.check_per_image(cfg, per_image)
+        per_image.check(n)
     check_dps_sharding(engine, cfg, n, world)
     lo, hi = shard_range(n, rank, world)
     sl = slice(lo, hi)
@@ -359,7 +364,8 @@ def restore_sharded(engine, cfg, y, k=None, mask=None, labels=None, *, rank: int
     if hi > lo:
         kw = dict(k=None if k is None else np.ascontiguousarray(k[sl]), mask=None if mask is None else np.ascontiguousarray(mask[sl]),
                   labels=None if labels is None else np.asarray(labels)[sl], seed=seed, image_offset=image_offset + lo,
-                  use_graph=use_graph, out_u8=out_u8, _cache=cache, skip_dead_final_eval=skip_dead_final_eval)
+                  use_graph=use_graph, out_u8=out_u8, _cache=cache, skip_dead_final_eval=skip_dead_final_eval,
+                  per_image=None if per_image is None else per_image.rows(lo, hi))
         if noise_source == "host":
             cut = lambda a: None if a is None else (np.ascontiguousarray(a[sl]) if a.ndim == 4 else np.ascontiguousarray(a[:, sl]))     # noqa: E731
             # driver main_ddpir_inpainting: the dict of restore.draw_inpaint_host_noise for the global batch

@@ -78,6 +78,121 @@ def sweeps(config):
     return [(config.lambda_ * 1, config.zeta * 1)]
 
 
+def flatten_sweeps(n_points: int, n_images: int, batch_size: int):
+    """`engine_batch_sweeps: true`: the (sweep point, image) pairs of the whole test set in the order the sequential driver visits them (point by
+    point, main_ddpir.py:548-580; image by image inside a point), cut into batches of batch_size.  Returns a list of lists of (point, image)."""
+    if batch_size < 1:
+        raise ValueError("batch_size must be >= 1")
+    pairs = [(s, g) for s in range(n_points) for g in range(n_images)]
+    return [pairs[j:j + batch_size] for j in range(0, len(pairs), batch_size)]
+
+
+def regroup_sweeps(batches, values, n_points: int, n_images: int):
+    """The inverse of flatten_sweeps for per-pair results: values[b][j] belongs to pair batches[b][j]; returns [n_points][n_images], each point's
+    values in image order."""
+    out = [[None] * n_images for _ in range(n_points)]
+    for pairs, vals in zip(batches, values):
+        if len(pairs) != len(vals):
+            raise ValueError(f"a batch of {len(pairs)} pairs came back with {len(vals)} values")
+        for (s, g), v in zip(pairs, vals):
+            out[s][g] = v
+    if any(v is None for row in out for v in row):
+        raise ValueError("regroup_sweeps: some (point, image) pair has no value")
+    return out
+
+
+def image_runs(images):
+    """[(first image, count)] of the maximal runs of consecutive image numbers in `images` (distinct, in visiting order): each run is degraded by
+    one dgr.degrade call with image_offset = its first image, exactly as a batch of the sequential driver is."""
+    runs = []
+    for g in images:
+        if runs and runs[-1][0] + runs[-1][1] == g:
+            runs[-1][1] += 1
+        else:
+            runs.append([g, 1])
+    return [tuple(r) for r in runs]
+
+
+def check_batch_sweeps(config):
+    """What `engine_batch_sweeps: true` cannot do, refused before any work starts."""
+    if config.get("engine_noise", "device") != "device":
+        raise ValueError("engine_batch_sweeps needs engine_noise: device -- the reference's one global generator would have to be drawn for every "
+                         "sweep point up front (about 8 GB for the super-resolution sweep)")
+    if progress_options(config)[0]:
+        raise ValueError("engine_batch_sweeps with save_progressive / log_process: the strips' file names carry one lambda, a batch holds several")
+    restore.check_per_image(loop_config(config, *sweeps(config)[0]), restore.PerImage(lambda_=[], zeta=[]))
+
+
+def run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph, cache):
+    """The sweep loop of main() flattened into full batches (YAML `engine_batch_sweeps: true`): every batch holds batch_size (point, image) pairs
+    and runs as ONE restore_batch call with per-image (lambda, zeta) and the images' global numbers as noise keys.  Each distinct image of a batch
+    is degraded once, with the seed and image_offset the sequential driver uses, and its y / k / mask / ground-truth rows are gathered on the
+    device.  Logs and returns what the sequential loop does: one average PSNR per point, in the same order."""
+    n_img, bs = len(imgs), config.batch_size
+    H, W = imgs.shape[1], imgs.shape[2]
+    batches = flatten_sweeps(len(points), n_img, bs)
+    cfg = loop_config(config, *points[0])
+    values, t0 = [], time.time()
+
+    def gather(parts, rows):
+        """device rows: rows[j] = (part index, row inside it) -> one DeviceArray [len(rows), ...] (dpir_d2d per row), or None"""
+        if parts[0] is None:
+            return None
+        out = eng.empty((len(rows),) + parts[0].shape[1:], parts[0].dtype)
+        nb = out.nbytes // len(rows)
+        for j, (q, r) in enumerate(rows):
+            eng._check(eng.lib.dpir_d2d(eng.h, out.ptr + j * nb, parts[q].ptr + r * nb, nb))
+        return out
+
+    for pairs in batches:
+        lo, hi = ddist.shard_range(len(pairs), rank, world)
+        mine = pairs[lo:hi]
+        wanted = {g for _, g in mine}
+        u8_local = eng.empty((hi - lo, H, W, 3), np.uint8)
+        per_img = np.zeros((0, 2))
+        where, ys, ks, ms, gts = {}, [], [], [], []
+        for g0, cnt in image_runs(list(dict.fromkeys(g for _, g in pairs))):
+            k_all, mask_all = make_operators(config, cnt, g0, H, W)          # every rank draws every operator of the batch (seeded numpy)
+            if not wanted & set(range(g0, g0 + cnt)):
+                continue
+            y, ops = dgr.degrade(eng, config.task, imgs[g0:g0 + cnt], k=k_all, mask=mask_all, noise_level_img=config.noise_level_img, sf=config.sf,
+                                 sr_mode=config.sr_mode, seed=config.seed + 1, image_offset=g0)
+            for r in range(cnt):
+                where[g0 + r] = (len(ys), r)
+            ys.append(y); ks.append(ops.get("k")); ms.append(ops.get("mask")); gts.append(ops["gt"])
+        if mine:
+            rows = [where[g] for _, g in mine]
+            pi = restore.PerImage(lambda_=[points[s][0] for s, _ in mine], zeta=[points[s][1] for s, _ in mine], image_index=[g for _, g in mine])
+            out_f32 = restore.restore_batch(eng, cfg, gather(ys, rows), k=gather(ks, rows), mask=gather(ms, rows), noise_source="device",
+                                            seed=config.seed, use_graph=use_graph, out_u8=u8_local, _cache=cache,
+                                            skip_dead_final_eval=bool(config.get("engine_skip_dead_final_eval", False)), per_image=pi)
+            psnr_i, psnr_y_i = dgr.metrics(eng, out_f32, gather(gts, rows))
+            per_img = np.stack([psnr_i, psnr_y_i], 1).astype(np.float64)
+        ddist.all_gather_results(u8_local, len(pairs), rank, world, engine=eng)           # the one collective of the path
+        allm = ddist.all_gather_results(per_img.reshape(-1, 2), len(pairs), rank, world, engine=eng)
+        values.append([tuple(v) for v in allm])
+    dt = time.time() - t0
+    results = []
+    for (lambda_, zeta), per_point in zip(points, regroup_sweeps(batches, values, len(points), n_img)):
+        if rank == 0:
+            log.info("eta:%s, zeta:%s, lambda:%s, guidance_scale:%s", config.eta, zeta, lambda_, config.guidance_scale)
+        psnrs, psnrs_y = [], []
+        for i0 in range(0, n_img, bs):             # the sequential driver's batches of this point: the same averages, the same log lines
+            chunk = np.asarray(per_point[i0:i0 + bs], np.float64)
+            p, p_y = float(np.mean(chunk[:, 0])), float(np.mean(chunk[:, 1]))
+            psnrs.append(p * len(chunk))
+            psnrs_y.append(p_y * len(chunk))
+            if rank == 0:
+                log.info("batch%4d--> PSNR: %.4fdB", i0 // bs + 1, p)
+        if rank == 0:
+            log.info("-----------> Average PSNR(RGB) of (%s) scale factor: (%d), sigma: (%.3f): %.4f dB  [%.2f images/s on %d GPU(s)]",
+                     config.testset_name, config.sf, config.noise_level_model, sum(psnrs) / n_img, len(points) * n_img / dt, world)
+            log.info("-----------> Average PSNR(Y) of (%s) scale factor: (%d), sigma: (%.3f): %.4f dB",
+                     config.testset_name, config.sf, config.noise_level_model, sum(psnrs_y) / n_img)
+        results.append(sum(psnrs) / n_img)
+    return results
+
+
 def load_images(config, n_synth):
     """uint8 [N,H,W,3] (what util.imread_uint returns, main_ddpir.py:84) + names.  testsets/<testset_name>/*.png via PIL when
     present, else synthetic."""
@@ -271,6 +386,9 @@ def main(argv=None):
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(message)s")
     config = parse_config(args.opt)
+    batch_sweeps = bool(config.get("engine_batch_sweeps", False))
+    if batch_sweeps:
+        check_batch_sweeps(config)
     num_gpus = args.num_gpus or int(config.get("num_gpus", 1) or 1)
     if num_gpus > 1 and "WORLD_SIZE" not in os.environ:
         # one process per GPU: re-launch under torch.distributed.run (rendezvous on 127.0.0.1)
@@ -317,9 +435,11 @@ def main(argv=None):
     # batches had been computed, losing the run)
     for i0 in range(0, len(imgs), config.batch_size):
         ddist.check_dps_sharding(eng, loop_config(config, *sweeps(config)[0]), min(config.batch_size, len(imgs) - i0), world)
-    for si, (lambda_, zeta) in enumerate(sweeps(config)):
-        if args.max_sweeps and si >= args.max_sweeps:
-            break
+    points = sweeps(config)[:args.max_sweeps] if args.max_sweeps else sweeps(config)
+    if batch_sweeps:
+        results = run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph, cache)
+        points = []
+    for si, (lambda_, zeta) in enumerate(points):
         cfg = loop_config(config, lambda_, zeta)
         if rank == 0:
             log.info("eta:%s, zeta:%s, lambda:%s, guidance_scale:%s", config.eta, zeta, lambda_, config.guidance_scale)

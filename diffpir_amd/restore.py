@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from .engine import Engine, DeviceArray, _ptr, EngineError
-from .schedule import build_steps, find_nearest
+from .schedule import build_image_table, build_steps, find_nearest
 
 TASKS = {"deblur": 0, "sr_blur": 1, "inpaint": 2, "sr_cubic": 3}
 
@@ -123,6 +123,59 @@ class LoopConfig:
 
 DRIVERS = ("main_ddpir", "main_ddpir_deblur", "main_ddpir_inpainting")
 GENERATE_MODES = {"DiffPIR": 0, "repaint": 1, "vanilla": 2, "DPS_y0": 3, "DPS_yt": 4}
+
+
+@dataclass
+class PerImage:
+    """Per-image hyper-parameters of one restore_batch call: a batch may hold the same picture several times under different (lambda, zeta), or
+    pictures of different noise levels -- the sweep of main_ddpir.py:548-580 as rows of full batches.  lambda_, zeta, noise_level_img: None (the
+    LoopConfig's value for every image) or length-B sequences in LoopConfig's units; image_index: None (image_offset + b) or length-B ints, the
+    global image number that keys each row's device noise.  Row b equals what a uniform call at its own values computes for that image."""
+    lambda_: object = None
+    zeta: object = None
+    noise_level_img: object = None
+    image_index: object = None
+
+    def has_scalars(self) -> bool:
+        return self.lambda_ is not None or self.zeta is not None or self.noise_level_img is not None
+
+    def check(self, B: int):
+        for name in ("lambda_", "zeta", "noise_level_img", "image_index"):
+            v = getattr(self, name)
+            if v is not None and len(v) != B:
+                raise ValueError(f"PerImage.{name}: {len(v)} values for a batch of {B} images")
+
+    def rows(self, lo: int, hi: int) -> "PerImage":
+        """the rows [lo, hi) of a sharded batch"""
+        cut = lambda v: None if v is None else list(v)[lo:hi]
+        return PerImage(cut(self.lambda_), cut(self.zeta), cut(self.noise_level_img), cut(self.image_index))
+
+
+def check_per_image(cfg: "LoopConfig", per_image: PerImage):
+    """What has no per-image form, refused before the device is touched."""
+    if cfg.driver != "main_ddpir":
+        raise NotImplementedError(f"per_image: driver={cfg.driver!r} runs the standalone program's own loop, which has no per-image form")
+    if cfg.generate_mode in ("DPS_y0", "DPS_yt"):
+        raise NotImplementedError("per_image: the DPS modes have no per-image form")
+    if not cfg.sub_1_analytic:
+        raise NotImplementedError("per_image: sub_1_analytic=false normalises its step by one residual norm of the whole batch (main_ddpir.py:425-427)")
+    if cfg.skip_noise_model_t and per_image.noise_level_img is not None:
+        raise NotImplementedError("per_image: skip_noise_model_t with a per-image noise level -- noise_model_t (main_ddpir.py:192) would differ per image")
+
+
+def _image_table(cfg: "LoopConfig", per_image: PerImage, B: int):
+    """((dt, steps, arr), table) of schedule.build_image_table for this call: _steps' keywords with the three per-image sequences filled in."""
+    T = cfg.num_train_timesteps
+    _steps(cfg)                                    # the uniform path's own checks (skip_noise_model_t against iter_num)
+    t_start = None
+    if cfg.noise_init_img != "max" or cfg.skip_noise_model_t:
+        from .schedule import DriverTables
+        t_start = t_start_of(cfg, DriverTables.make(cfg.beta_start, cfg.beta_end, T).reduced)
+    every = lambda v, default: [default] * B if v is None else [float(x) for x in v]
+    sigma = [max(0.001, v) for v in every(per_image.noise_level_img, cfg.noise_level_img)]         # LoopConfig.sigma per image
+    return build_image_table(lambda_=every(per_image.lambda_, cfg.lambda_), zeta=every(per_image.zeta, cfg.zeta), sigma=sigma,
+                             iter_num=cfg.iter_num, eta=cfg.eta, skip_type=cfg.skip_type, T=T, beta_start=cfg.beta_start, beta_end=cfg.beta_end,
+                             t_start=t_start, generate_mode=cfg.generate_mode, model_output_type=cfg.model_output_type)
 
 
 @dataclass
@@ -300,11 +353,15 @@ def draw_host_noise(noise_fn: Callable, steps, shape, need_n1: bool, repaint: bo
 def restore_batch(engine: Engine, cfg: LoopConfig, y, k=None, mask=None, labels=None, noise_source="device",
                   noise_fn: Optional[Callable] = None, seed: int = 0, image_offset: int = 0, use_graph: bool = False,
                   skip_dead_final_eval: bool = False, out_f32=None, out_u8=None, return_u8: bool = False, _cache: dict = None,
-                  predrawn=None, progress: Optional[Progress] = None):
+                  predrawn=None, progress: Optional[Progress] = None, per_image: Optional[PerImage] = None):
     """y: [B,3,h,w] in [0,1]; k: [B,1,kh,kw]; mask: uint8 [B,3,H,W] -- device arrays (or numpy, uploaded).
     Returns a DeviceArray [B,3,H,W] = x_0 in [0,1] (un-clamped, main_ddpir.py:470), and the u8 NHWC
-    array as well when return_u8.  progress: a Progress request, filled with the progressive strip of this call (every driver and mode)."""
+    array as well when return_u8.  progress: a Progress request, filled with the progressive strip of this call (every driver and mode).
+    per_image: a PerImage -- lambda / zeta / noise level and the noise key per image (dpir_run_loop_per_image); the closed-form DiffPIR /
+    repaint / vanilla loop of driver main_ddpir only.  Host noise and progress work unchanged; the caller orders the rows."""
     cfg.check_supported()
+    if per_image is not None:
+        check_per_image(cfg, per_image)
     if cfg.driver == "main_ddpir_inpainting":
         return _restore_inpaint_resample(engine, cfg, y, mask, labels, noise_source, noise_fn, seed, image_offset, use_graph, skip_dead_final_eval,
                                          out_f32, out_u8, return_u8, _cache, predrawn, progress=progress)
@@ -318,7 +375,6 @@ def restore_batch(engine: Engine, cfg: LoopConfig, y, k=None, mask=None, labels=
             raise NotImplementedError("DPS modes take host noise through noise_fn (their draw order differs from the DiffPIR loop's) and no mask")
         return _restore_dps(engine, cfg, y, labels, noise_source, noise_fn, seed, image_offset, skip_dead_final_eval, out_f32, out_u8, return_u8,
                             progress=progress)
-    dt, steps, arr = _steps(cfg)
     keep = []
 
     def dev(a, dtype):
@@ -331,6 +387,16 @@ def restore_batch(engine: Engine, cfg: LoopConfig, y, k=None, mask=None, labels=
         return a
     y = dev(y, np.float32); k = dev(k, np.float32); mask = dev(mask, np.uint8)
     B, _, h, w = y.shape
+    table = index = None
+    if per_image is not None:
+        per_image.check(B)
+        if per_image.has_scalars():
+            (dt, steps, arr), tab = _image_table(cfg, per_image, B)
+            table = np.ascontiguousarray(tab, np.float32)
+        if per_image.image_index is not None:
+            index = np.ascontiguousarray(per_image.image_index, dtype=np.int64)
+    if table is None:
+        dt, steps, arr = _steps(cfg)
     H, W = h * cfg.sf, w * cfg.sf
     d = _lib.LoopDesc()
     d.task = cfg.engine_task()
@@ -375,7 +441,12 @@ def restore_batch(engine: Engine, cfg: LoopConfig, y, k=None, mask=None, labels=
     if out_u8 is None and return_u8:
         out_u8 = engine.empty((B, H, W, 3), np.uint8)
     armed = _arm(engine, progress, cfg, steps, B, H, W, mask is not None)
-    engine._check(engine.lib.dpir_run_loop(engine.h, C.byref(d), arr, len(steps), _ptr(out_f32), _ptr(out_u8)))
+    if table is None and index is None:
+        engine._check(engine.lib.dpir_run_loop(engine.h, C.byref(d), arr, len(steps), _ptr(out_f32), _ptr(out_u8)))
+    else:
+        engine._check(engine.lib.dpir_run_loop_per_image(
+            engine.h, C.byref(d), arr, len(steps), None if table is None else table.ctypes.data_as(C.POINTER(_lib.ImageStep)),
+            None if index is None else index.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(out_f32), _ptr(out_u8)))
     if armed:
         armed.finish()
     if _cache is not None:

@@ -189,6 +189,39 @@ def build_steps(*, iter_num: int, sigma: float, lambda_: float, zeta: float, eta
     return dt, steps, arr
 
 
+IMAGE_FIELDS = ("tau", "k1", "k2")          # what (lambda, zeta, sigma) reach of a step; every other field is shared by the batch
+
+
+def build_image_table(*, lambda_, zeta, sigma, **kw):
+    """Per-image (lambda, zeta, sigma) for one batch: lambda_, zeta and sigma are length-B sequences, every other keyword is build_steps' own and
+    holds for the whole call.  Returns ((dt, steps, arr) of image 0's triple, float32 [n_steps, B, 4] of (tau, k1, k2, 0)) -- the table of
+    dpir_run_loop_per_image.  build_steps is called once per distinct triple and its tau / k1 / k2 are copied: the numbers are the uniform
+    path's own, none of main_ddpir.py:277-286, 454-456 is restated here.  ValueError when any other field of a step differs between triples."""
+    lam, zet, sig = [float(v) for v in lambda_], [float(v) for v in zeta], [float(v) for v in sigma]
+    if not lam or not (len(lam) == len(zet) == len(sig)):
+        raise ValueError(f"lambda_, zeta and sigma must be sequences of one length B >= 1 (got {len(lam)}, {len(zet)}, {len(sig)})")
+    built = {}
+    for triple in zip(lam, zet, sig):
+        if triple not in built:
+            built[triple] = build_steps(lambda_=triple[0], zeta=triple[1], sigma=triple[2], **kw)
+    first = built[(lam[0], zet[0], sig[0])]
+    shared = [f for f, _ in _lib.Step._fields_ if f not in IMAGE_FIELDS]
+    for triple, (_, steps, arr) in built.items():
+        if len(steps) != len(first[1]):
+            raise ValueError(f"(lambda, zeta, sigma) = {triple}: {len(steps)} steps, image 0 has {len(first[1])}")
+        for i in range(len(steps)):
+            for f in shared:
+                if getattr(arr[i], f) != getattr(first[2][i], f):
+                    raise ValueError(f"step {i}: field {f!r} differs between (lambda, zeta, sigma) = {triple} and image 0's "
+                                     f"({getattr(arr[i], f)!r} != {getattr(first[2][i], f)!r}); only tau, k1 and k2 may depend on them")
+    table = np.zeros((len(first[1]), len(lam), 4), np.float32)
+    for b, triple in enumerate(zip(lam, zet, sig)):
+        arr = built[triple][2]
+        for i in range(table.shape[0]):
+            table[i, b, :3] = [getattr(arr[i], f) for f in IMAGE_FIELDS]      # the ctypes array holds the float32 values the engine reads
+    return first, table
+
+
 def build_inpaint_rows(*, iter_num: int, iter_num_U: int, sigma: float, lambda_: float, zeta: float, eta: float = 0.0,
                        skip_type: str = "quad", T: int = 1000, beta_start=0.0001, beta_end=0.02, t_start: int = None):
     """One row per sub-step (i, u) of the standalone inpainting program (main_ddpir_inpainting.py:200-300), model_out_type pred_xstart:

@@ -266,6 +266,28 @@ typedef struct dpir_loop_desc {
 int dpir_run_loop(dpir_engine* e, const dpir_loop_desc* d, const dpir_step* steps_host, int n_steps,
                   float* out_f32_dev, uint8_t* out_u8_dev);
 
+/* The three scalars of a step that depend on (lambda, zeta, sigma), for one image: rhos[t_i] (main_ddpir.py:277-286, 389) and the two zeta
+ * coefficients of the re-noise (main_ddpir.py:454-456), computed on the host like dpir_step's (diffpir_amd/schedule.py build_image_table). */
+typedef struct dpir_image_step { float tau, k1, k2, reserved; } dpir_image_step;
+
+/* dpir_run_loop with per-image scalars: image b at step i uses per_image_host[i*B + b]. {tau, k1, k2}
+ * in place of steps_host[i].{tau, k1, k2} (NULL: the step's own), and device Philox is keyed by
+ * image_index_host[b] in place of d->image_offset + b (NULL: that default).  Both NULL == dpir_run_loop.
+ * Replaces the outer sweep loop of main_ddpir.py:548-580 (one restoration per (lambda, zeta) point) by rows of one batch: every other field of a
+ * step, the timesteps and the denoiser are shared.  Row b computes what dpir_run_loop computes for that image under uniform scalars equal to its
+ * own (the same float32 operations in the same order).  Both tables are copied before the call returns.  DPIR_ERR_UNSUPPORTED before anything is
+ * enqueued: d->first_order with a per-image table (that data step normalises by ONE residual norm of the whole batch, main_ddpir.py:425-427).
+ * The gradient-mode loops and dpir_run_inpaint_loop have no per-image form. */
+int dpir_run_loop_per_image(dpir_engine* e, const dpir_loop_desc* d, const dpir_step* steps_host, int n_steps,
+                            const dpir_image_step* per_image_host, const int64_t* image_index_host,
+                            float* out_f32_dev, uint8_t* out_u8_dev);
+
+/* dpir_randn with an explicit image number per row: row b == dpir_randn(..., image_offset = image_index_host[b], B = 1)
+ * (torch.randn_like's perf-mode replacement, SURVEY.md 8a-R, for a batch whose rows are not consecutive images).  Synchronises the stream once
+ * (the image numbers are uploaded from the caller's array). */
+int dpir_randn_indexed(dpir_engine* e, float* out_dev, uint64_t seed, uint64_t stream_id,
+                       const int64_t* image_index_host, int B, int C, int H, int W);
+
 /* ---- inpainting with resampling (main_ddpir_inpainting.py:147-317, iter_num_U >= 1) ------- */
 /* One row per sub-step (i, u) of the standalone inpainting program, all computed on the host as that program does
  * (diffpir_amd/schedule.py build_inpaint_rows).  The first ten scalars are dpir_step's. */
