@@ -95,6 +95,13 @@ class Conv9Desc(C.Structure):
                 [(n, C.c_int32) for n in ("ran_out", "iters")] + [("ms_out", C.c_double)])
 
 
+class Conv11Desc(C.Structure):
+    """dpir_debug_conv11_desc (include/diffpir_debug.h): one layer of the 8 x 32 geometry for dpir_debug_conv11_layer."""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "Cin", "Cout", "H", "W", "res_mode", "route", "ksplit", "hop", "Cout2")] +
+                [(n, C.c_void_p) for n in ("x", "w", "bias", "res", "prm", "gamma2", "beta2", "film2", "w2", "bias2", "out", "stat_out", "out2")] +
+                [(n, C.c_int32) for n in ("ran_out", "iters")] + [("ms_out", C.c_double)])
+
+
 class ConvUpDesc(C.Structure):
     """dpir_debug_conv_up_desc (include/diffpir_debug.h): conv1 of an up-sampling ResBlock, or the two-layer hop, for dpir_debug_conv_up_layer."""
     _fields_ = ([(n, C.c_int32) for n in ("B", "Cin", "Cout", "Hs", "Ws", "hop", "force_hop", "Cout2", "route", "reserved")] +
@@ -232,6 +239,10 @@ def load_debug():
     d.dpir_debug_conv3_layer.restype = C.c_int
     d.dpir_debug_conv9_layer.argtypes = [C.c_void_p, C.POINTER(Conv9Desc)]
     d.dpir_debug_conv9_layer.restype = C.c_int
+    d.dpir_debug_conv11_layer.argtypes = [C.c_void_p, C.POINTER(Conv11Desc)]
+    d.dpir_debug_conv11_layer.restype = C.c_int
+    d.dpir_debug_conv11_counts.argtypes = [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    d.dpir_debug_conv11_counts.restype = None
     d.dpir_debug_conv_up_layer.argtypes = [C.c_void_p, C.POINTER(ConvUpDesc)]
     d.dpir_debug_conv_up_layer.restype = C.c_int
     d.dpir_debug_conv_up_counts.argtypes = [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]

@@ -3,6 +3,7 @@
 #include "engine.h"
 #include "conv6_params.h"
 #include "conv9.h"
+#include "conv11.h"
 #include "conv_up.h"
 #include "../../include/diffpir_debug.h"
 #include <string.h>
@@ -621,6 +622,146 @@ int dpir_debug_conv9_layer(dpir_engine* e, dpir_debug_conv9_desc* d) {
     return DPIR_OK;
 }
 
+// One layer of the 8 x 32 geometry on caller-supplied host operands through conv11 (csrc/conv11.hip), or the same planes through launch_conv6
+// with conv7 forced (route 7: the arm conv11 is timed against).  Planes: act_split (optionally with a table).  The timed repeats are the
+// convolution launch alone.
+int dpir_debug_conv11_layer(dpir_engine* e, dpir_debug_conv11_desc* d) {
+    if (!e || !d) return DPIR_ERR_INVALID;
+    d->ran_out = 0; d->ms_out = 0.0;
+    const int B = d->B, Cin = d->Cin, Cout = d->Cout, H = d->H, W = d->W;
+    if (!d->x || !d->w || !d->bias || (!d->hop && !d->out) || B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || d->res_mode < -1 || d->res_mode > 2 ||
+        (d->res_mode >= 0 && !d->res) || (d->route != 0 && d->route != 7) || (d->hop && d->route != 0) ||
+        (d->hop && (!d->gamma2 || !d->beta2 || !d->w2 || !d->bias2 || !d->out2 || d->Cout2 <= 0)))
+        return fail(e, invalid("conv11 layer: bad descriptor"));
+    if (d->hop && d->res_mode >= 0) return fail(e, invalid("conv11 layer: the hop's first layer takes no residual"));
+    if ((d->res_mode == 1 && ((H | W) & 1))) return fail(e, invalid("conv11 layer: a half-resolution residual needs an even output size"));
+    (void)hipSetDevice(e->device);
+    const size_t HW = (size_t)H * W, nx = (size_t)B * Cin * HW, no = (size_t)B * Cout * HW;
+    const size_t nres = d->res_mode == 1 ? no / 4 : (d->res_mode == 2 ? no * 4 : no);
+    const int chunks = (Cin + 15) / 16, C8 = 2 * chunks;
+    const size_t plane = (size_t)B * C8 * HW * 16;
+    Conv11Args a11;
+    a11.B = B; a11.Cin = Cin; a11.Cout = Cout; a11.H = H; a11.W = W;
+    a11.ksplit = d->ksplit; a11.precision = e->precision; a11.grad = e->grad_enabled;
+    if (d->route == 0) {        // refusals before anything is allocated: dummy non-null operands, the checks that decide come first
+        Conv11Args probe = a11;
+        if (probe.grad || probe.precision != 1 || probe.ksplit != 1 || !conv11_supported(Cin, Cout, H, W)) {
+            const Status st = launch_conv11(e->stream, probe);
+            if (!st.ok()) return fail(e, st);
+        }
+        if (d->hop && !conv11_emit_supported(Cout, H, W))
+            return fail(e, Status{DPIR_ERR_UNSUPPORTED, "conv11 layer: fused emission needs GroupNorm groups inside a wave's 64 channels and an image's tiles resident with room to spare"});
+    } else if (e->grad_enabled || e->precision != 1) {
+        return fail(e, Status{DPIR_ERR_UNSUPPORTED, "conv11 layer: the conv7 arm is timed on an f16x3 inference engine"});
+    }
+    const int slots = conv6_stat_slots(H, W);
+    const size_t nst = (size_t)B * Cout * slots;
+    float *dx = nullptr, *dbias = nullptr, *dout = nullptr, *dres = nullptr; float4* dprm = nullptr; float2* st = nullptr; char* s16 = nullptr;
+    API_TRY(e, e->ws.getT("c11#x", nx, &dx));
+    API_TRY(e, e->ws.getT("c11#b", (size_t)round_up(Cout, 64), &dbias));
+    API_TRY(e, e->ws.getT("c11#o", no, &dout));
+    API_TRY(e, e->ws.getT("c11#res", nres, &dres));
+    API_TRY(e, e->ws.getT("c11#prm", (size_t)B * Cin, &dprm));
+    API_TRY(e, e->ws.getT("c11#st", nst > 0 ? nst : 1, &st));
+    API_TRY(e, e->ws.getT("c11#s16", 2 * plane, &s16));
+    API_HIP(e, hipMemcpy(dx, d->x, nx * 4, hipMemcpyHostToDevice));
+    API_HIP(e, hipMemset(dbias, 0, (size_t)round_up(Cout, 64) * 4));
+    API_HIP(e, hipMemcpy(dbias, d->bias, (size_t)Cout * 4, hipMemcpyHostToDevice));
+    if (d->prm) API_HIP(e, hipMemcpy(dprm, d->prm, (size_t)B * Cin * 16, hipMemcpyHostToDevice));
+    if (d->res_mode >= 0) API_HIP(e, hipMemcpy(dres, d->res, nres * 4, hipMemcpyHostToDevice));
+    API_HIP(e, hipMemsetAsync(dout, 0xFF, no * 4, e->stream));
+    if (nst) API_HIP(e, hipMemsetAsync(st, 0xFF, nst * 8, e->stream));
+    API_HIP(e, hipMemsetAsync(s16, 0xFF, 2 * plane, e->stream));
+    API_TRY(e, launch_act_split(e->stream, CatSrc{dx, Cin, nullptr, 0}, d->prm ? dprm : nullptr, 0, B, H, W, s16, s16 + plane, e->range_ctr));
+    std::vector<uint16_t> w16v, w11v;
+    const float w16_scale = pack_weights_conv6(d->w, Cout, Cin, w16v);
+    void* wp = nullptr;
+    if (d->route == 0) {
+        pack_weights_conv11(d->w, Cout, Cin, w16_scale, w11v);
+        API_TRY(e, e->ws.get("c11#w11", w11v.size() * 2, &wp));
+        API_HIP(e, hipMemcpy(wp, w11v.data(), w11v.size() * 2, hipMemcpyHostToDevice));
+    } else {
+        API_TRY(e, e->ws.get("c11#w16", w16v.size() * 2, &wp));
+        API_HIP(e, hipMemcpy(wp, w16v.data(), w16v.size() * 2, hipMemcpyHostToDevice));
+    }
+    a11.xhi = s16; a11.xlo = s16 + plane; a11.w11 = wp; a11.w_scale = w16_scale; a11.bias = dbias; a11.out = dout;
+    if (d->res_mode >= 0) { a11.res = dres; a11.res_mode = d->res_mode; }
+    a11.stat = nst ? st : nullptr;
+    Conv6Args a6;
+    a6.xhi = s16; a6.xlo = s16 + plane; a6.w16 = wp; a6.w16_scale = w16_scale; a6.bias = dbias; a6.out = dout;
+    if (d->res_mode >= 0) { a6.res = dres; a6.res_mode = d->res_mode; }
+    a6.B = B; a6.Cin = Cin; a6.Cout = Cout; a6.H = H; a6.W = W; a6.stat = nst ? st : nullptr; a6.force_kernel = 7;
+    // second layer and the hop's arena (dpir_debug_conv_up_layer's)
+    const int Co2 = d->hop ? d->Cout2 : 0, C8b = 2 * ((Cout + 15) / 16);
+    const size_t plane2 = (size_t)B * C8b * HW * 16, no2 = (size_t)B * Co2 * HW;
+    const size_t arena_words = (size_t)B * 64 + ((size_t)B * ((Cout + 63) / 64) + 1) / 2;
+    char* s16b = nullptr; float *dg = nullptr, *db = nullptr, *df = nullptr, *dbias2 = nullptr, *dout2 = nullptr; long long* arena = nullptr; void* wp2 = nullptr;
+    Conv6Emit em;
+    Conv6Args c6;
+    if (d->hop) {
+        API_TRY(e, e->ws.getT("c11#s16b", 2 * plane2, &s16b));
+        API_TRY(e, e->ws.getT("c11#gamma2", (size_t)Cout, &dg));
+        API_TRY(e, e->ws.getT("c11#beta2", (size_t)Cout, &db));
+        API_TRY(e, e->ws.getT("c11#film2", (size_t)B * 2 * Cout, &df));
+        API_TRY(e, e->ws.getT("c11#b2", (size_t)round_up(Co2, 64), &dbias2));
+        API_TRY(e, e->ws.getT("c11#o2", no2, &dout2));
+        API_TRY(e, e->ws.getT("c11#arena", arena_words, &arena));
+        API_HIP(e, hipMemsetAsync(s16b, 0xFF, 2 * plane2, e->stream));
+        API_HIP(e, hipMemcpy(dg, d->gamma2, (size_t)Cout * 4, hipMemcpyHostToDevice));
+        API_HIP(e, hipMemcpy(db, d->beta2, (size_t)Cout * 4, hipMemcpyHostToDevice));
+        if (d->film2) API_HIP(e, hipMemcpy(df, d->film2, (size_t)B * 2 * Cout * 4, hipMemcpyHostToDevice));
+        API_HIP(e, hipMemset(dbias2, 0, (size_t)round_up(Co2, 64) * 4));
+        API_HIP(e, hipMemcpy(dbias2, d->bias2, (size_t)Co2 * 4, hipMemcpyHostToDevice));
+        API_HIP(e, hipMemsetAsync(dout2, 0xFF, no2 * 4, e->stream));
+        std::vector<uint16_t> w16b;
+        const float w2_scale = pack_weights_conv6(d->w2, Co2, Cout, w16b);
+        API_TRY(e, e->ws.get("c11#w16b", w16b.size() * 2, &wp2));
+        API_HIP(e, hipMemcpy(wp2, w16b.data(), w16b.size() * 2, hipMemcpyHostToDevice));
+        em.hi = s16b; em.lo = s16b + plane2; em.C8 = C8b; em.gamma = dg; em.beta = db;
+        em.film = d->film2 ? df : nullptr; em.film_stride = 2 * Cout; em.film_off = 0; em.frows = 2 * Cout; em.fstep = nullptr;
+        em.acc = arena; em.cnt = reinterpret_cast<unsigned*>(arena + (size_t)B * 64); em.range_ctr = e->range_ctr;
+        a11.out = nullptr; a11.stat = nullptr; a11.emit = &em;
+        c6.xhi = s16b; c6.xlo = s16b + plane2; c6.w16 = wp2; c6.w16_scale = w2_scale;
+        c6.bias = dbias2; c6.out = dout2; c6.B = B; c6.Cin = Cout; c6.Cout = Co2; c6.H = H; c6.W = W;
+    }
+    auto launch = [&]() -> Status {
+        if (d->route != 0) return launch_conv6(e->stream, a6);
+        if (!d->hop) return launch_conv11(e->stream, a11);
+        DPIR_HIP(hipMemsetAsync(arena, 0, arena_words * 8, e->stream));
+        DPIR_TRY(launch_conv11(e->stream, a11));
+        return launch_conv6(e->stream, c6);
+    };
+    API_TRY(e, launch());
+    if (d->iters > 0) {
+        hipEvent_t e0, e1;
+        API_HIP(e, hipEventCreate(&e0)); API_HIP(e, hipEventCreate(&e1));
+        API_HIP(e, hipEventRecord(e0, e->stream));
+        for (int i = 0; i < d->iters; ++i) API_TRY(e, launch());
+        API_HIP(e, hipEventRecord(e1, e->stream));
+        API_HIP(e, hipEventSynchronize(e1));
+        float ms = 0; API_HIP(e, hipEventElapsedTime(&ms, e0, e1));
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        d->ms_out = ms / d->iters;
+    }
+    API_HIP(e, hipStreamSynchronize(e->stream));
+    d->ran_out = d->route == 0 ? (d->hop ? 12 : 11) : 7;
+    if (d->hop) {
+        API_HIP(e, hipMemcpy(d->out2, dout2, no2 * 4, hipMemcpyDeviceToHost));
+        return DPIR_OK;
+    }
+    API_HIP(e, hipMemcpy(d->out, dout, no * 4, hipMemcpyDeviceToHost));
+    if (d->stat_out && nst) {        // epilogue slots: fp32 partial sums of 64 values, folded in fp64 (gn_prm's contract)
+        std::vector<float2> hs(nst);
+        API_HIP(e, hipMemcpy(hs.data(), st, nst * 8, hipMemcpyDeviceToHost));
+        for (size_t pl = 0; pl < (size_t)B * Cout; ++pl) {
+            double s1 = 0.0, s2 = 0.0;
+            for (int k = 0; k < slots; ++k) { s1 += (double)hs[pl * slots + k].x; s2 += (double)hs[pl * slots + k].y; }
+            d->stat_out[2 * pl] = s1; d->stat_out[2 * pl + 1] = s2;
+        }
+    }
+    return DPIR_OK;
+}
+
 // conv1 of an up-sampling ResBlock on caller-supplied host operands (include/diffpir_debug.h dpir_debug_conv_up_desc), as Fwd::resblock_up
 // (unet.hip) launches it -- route 0: act_split at the SOURCE resolution + conv_up (csrc/conv_up.hip) -- or as the forward ran it before --
 // route 1: act_split with the nearest-up source + launch_conv6.  hop: the first layer's epilogue writes the second layer's planes and the second
@@ -760,6 +901,7 @@ int dpir_debug_conv_up_layer(dpir_engine* e, dpir_debug_conv_up_desc* d) {
 }
 
 void dpir_debug_conv_up_counts(long long* plain, long long* hop) { conv_up_launch_counts(plain, hop); }
+void dpir_debug_conv11_counts(long long* plain, long long* hop) { conv11_launch_counts(plain, hop); }
 
 int dpir_debug_conv7_emit_supported(dpir_engine* e, int B, int Cout, int H, int W, int* capacity_out) {
     if (!e) return 0;

@@ -33,7 +33,8 @@ struct ConvW { float* w = nullptr; float* bias = nullptr; int cin = 0, cout = 0,
                float* wT = nullptr; int coutpT = 0;             // grad mode: the dgrad operand [coutP16][taps flipped][cinP64] (unet_bwd.hip)
                void* w8 = nullptr; float w8_scale = 1.f;        // 3x3 with cout <= 16 and cin % 32 == 0: conv8 layout (fused GroupNorm/SiLU/split prologue)
                void* w16T = nullptr; float w16T_scale = 1.f;    // grad mode in the f16 precisions: the same operand in conv6 / conv5 split layout
-               void* wup = nullptr; float wup_scale = 1.f; };   // conv1 of an up-sampling ResBlock, f16 precisions: the phase pack (conv_up.hip), besides w16
+               void* wup = nullptr; float wup_scale = 1.f;      // conv1 of an up-sampling ResBlock, f16 precisions: the phase pack (conv_up.hip), besides w16
+               void* w11 = nullptr; };                          // f16x3, 3x3 with cin % 32 == 0 and cout % 128 == 0: conv11 layout (same halves and scale as w16)
 struct GnW { float* gamma = nullptr; float* beta = nullptr; int c = 0; };
 struct ResW {
     std::string name;

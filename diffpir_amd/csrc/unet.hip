@@ -9,6 +9,7 @@
 #include "engine.h"
 #include "conv6_params.h"
 #include "conv9.h"
+#include "conv11.h"
 #include "conv_up.h"
 #include <unordered_map>
 #include <cstdint>
@@ -127,6 +128,16 @@ Status load_conv(dpir_engine* e, const WeightMap& wm, const std::string& p, int 
             e->net.allocs.push_back(p8);
             DPIR_HIP(hipMemcpy(p8, w8.data(), w8.size() * 2, hipMemcpyHostToDevice));
             out->w8 = p8;
+        }
+        if (e->precision == 1 && ks == 3 && !one_d && conv11_supported(cin, cout, 8, 32)) {
+            // the same f16 halves in the lane order of the 16x16x32 MFMA (conv11.hip), besides the conv6 pack (split-K launches, small shapes, gradient mode)
+            std::vector<uint16_t> w11;
+            pack_weights_conv11(w, cout, cin, out->w16_scale, w11);
+            void* p11 = nullptr;
+            if (hipMalloc(&p11, w11.size() * 2) != hipSuccess) return Status{DPIR_ERR_NOMEM, "hipMalloc for the conv11 weights failed"};
+            e->net.allocs.push_back(p11);
+            DPIR_HIP(hipMemcpy(p11, w11.data(), w11.size() * 2, hipMemcpyHostToDevice));
+            out->w11 = p11;
         }
         if (up_pack && ks == 3 && !one_d && cin % 16 == 0 && cout % 32 == 0) {
             // conv1 behind a nearest-x2 up-sampling: the four 2x2 phase filters (conv_up.hip), besides the 3x3 pack (gradient mode, small shapes)
@@ -405,6 +416,18 @@ struct Fwd {
                (long long)B * (cw.cout / 32) >= min_wg;
     }
 
+    // conv11 (csrc/conv11.hip: conv7's 8 x 32 tile with the 16x16x32 MFMA, x0.93 of conv7's time per layer, profiles/conv11/README.md) takes a 3x3
+    // layer of the f16x3 precision when its pack is loaded, the forward records no tape, the tiles lie inside the image and launch_conv6
+    // would have run the launch whole-K (its rule: 256 workgroups; the hop: conv7_emit_supported's 384, checked by h1_fusable) -- and, for
+    // the hop, when an image's tiles fit into half of conv11's own resident workgroups.  DPIR_CONV11=0 restores launch_conv6's dispatch.
+    bool conv11_route(const ConvW& cw, int Ho, int Wo, bool hop) const {
+        static const bool on = !(getenv("DPIR_CONV11") && atoi(getenv("DPIR_CONV11")) == 0);
+        static const int split_below = getenv("DPIR_SPLIT_BELOW") ? atoi(getenv("DPIR_SPLIT_BELOW")) : 256;
+        if (!on || grad || e->precision != 1 || !cw.w11 || cw.ks != 3 || !conv11_supported(cw.cin, cw.cout, Ho, Wo)) return false;
+        const long long wgs = (long long)(Wo / 32) * (Ho / 8) * B * (cw.cout / 128);
+        return hop ? wgs >= 384 && conv11_emit_supported(cw.cout, Ho, Wo) : wgs >= split_below;
+    }
+
     Status conv6_on_planes(const ConvW& cw, char* s16, size_t plane, const float* res, int res_mode, float* out, int Ho, int Wo,
                            const Conv6Emit* emit = nullptr) {
         const bool x1 = e->precision == 2;
@@ -436,6 +459,16 @@ struct Fwd {
             a9.stat_plane = emit ? nullptr : sp; a9.x1 = x1; a9.emit = emit;
             DPIR_TRY(launch_conv9(s, a9));
             if (sp && !emit) fused[out] = FusedStat{nullptr, 0, sp};
+            else fused.erase(out);
+            return Status{};
+        }
+        if (conv11_route(cw, Ho, Wo, emit != nullptr)) {
+            Conv11Args a11;
+            a11.xhi = s16; a11.xlo = s16 + plane; a11.w11 = cw.w11; a11.w_scale = cw.w16_scale; a11.bias = cw.bias; a11.out = out;
+            a11.res = res; a11.res_mode = res_mode; a11.B = B; a11.Cin = cw.cin; a11.Cout = cw.cout; a11.H = Ho; a11.W = Wo;
+            a11.stat = emit ? nullptr : st; a11.precision = e->precision; a11.grad = grad; a11.emit = emit;
+            DPIR_TRY(launch_conv11(s, a11));
+            if (st && !emit) fused[out] = FusedStat{st, slots, nullptr};
             else fused.erase(out);
             return Status{};
         }

@@ -74,6 +74,25 @@ typedef struct dpir_debug_conv9_desc {
     double ms_out;
 } dpir_debug_conv9_desc;
 int dpir_debug_conv9_layer(dpir_engine* e, dpir_debug_conv9_desc* d);
+/* One 3x3 layer of the 8 x 32 geometry on host operands through conv11 (csrc/conv11.hip: conv7's tile with the 16x16x32 MFMA), without the
+ * forward's workgroup threshold.  x, prm, res / res_mode, out, stat_out (the epilogue's slots, folded here) as dpir_debug_conv9_desc.
+ *   route 0: conv11; route 7: the same planes through launch_conv6 with conv7 forced (the arm conv11 is timed against).
+ *   ksplit: the split-K factor the caller would have used; conv11 refuses anything but 1.
+ *   hop 1 (route 0): the first layer's epilogue writes the second layer's planes -- GroupNorm32(gamma2, beta2), optional FiLM rows film2[B][2 Cout],
+ *     SiLU -- and the second layer (w2 [Cout2][Cout][3][3], bias2) runs through launch_conv6: out2[B][Cout2][H][W].
+ * A refusal (Cin, Cout, tile shape, split-K, gradient-mode engine, f32 / f16x1 precision, a hop whose groups straddle waves) is a non-zero return
+ * code with dpir_last_error's text; ran_out = 11 when conv11 ran, 12 for its hop, 7 for conv7.  iters > 0: the convolution launch alone (planes
+ * already built; hop: both launches, the hop's arena cleared in between) is repeated back to back that many times, ms_out = average of one repeat. */
+typedef struct dpir_debug_conv11_desc {
+    int32_t B, Cin, Cout, H, W, res_mode, route, ksplit, hop, Cout2;
+    const float *x, *w, *bias, *res, *prm, *gamma2, *beta2, *film2, *w2, *bias2;
+    float* out; double* stat_out; float* out2;
+    int32_t ran_out, iters;
+    double ms_out;
+} dpir_debug_conv11_desc;
+int dpir_debug_conv11_layer(dpir_engine* e, dpir_debug_conv11_desc* d);
+/* conv11 launches of this process so far: plain epilogue, fused hop (the probe's and the forward's; captured graph replays do not count). */
+void dpir_debug_conv11_counts(long long* plain, long long* hop);
 /* conv1 of an up-sampling ResBlock (3x3 on the nearest-x2 up-sampled x) on host operands.  x[B][Cin][Hs][Ws] is at the SOURCE resolution, out
  * [B][Cout][2 Hs][2 Ws]; prm: optional table [B][Cin][4] {mean, scale, shift, SiLU flag} applied by act_split at the source resolution.
  *   route 0: conv_up (csrc/conv_up.hip: four 2x2 phase convolutions of the source image); route 1: the up-sampled planes + launch_conv6.
