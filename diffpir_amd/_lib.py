@@ -109,6 +109,55 @@ class ConvUpDesc(C.Structure):
                 [(n, C.c_int32) for n in ("ran_out", "iters")] + [("ms_out", C.c_double)])
 
 
+class RouteRec(C.Structure):
+    """dpir_debug_route_rec (include/diffpir_debug.h): one convolution launch of the last forward, for dpir_debug_route_log."""
+    _fields_ = ([("layer", C.c_char * 80)] + [(n, C.c_int32) for n in ("kernel", "ks", "ksplit", "hop", "stat_kind", "reserved")] +
+                [("workgroups", C.c_longlong)])
+
+
+class ConvKnobs(C.Structure):
+    """dpir_debug_conv_knobs: the A/B switches of the 3x3 dispatch (csrc/conv_plan.h ConvKnobs)."""
+    _fields_ = [(n, C.c_int32) for n in ("conv8", "conv9", "conv9_min_wg", "conv11", "conv_up", "split_below", "split_target", "fuse_small",
+                                         "fuse_h1", "emit_skip")]
+
+
+CONV3_QUERY_FIELDS = ("B", "Cin", "Cout", "H", "W", "precision", "grad", "w16", "w8", "w11", "conv8_source", "defer", "hop", "has_res", "stats",
+                      "force_kernel")
+
+
+class Conv3Query(C.Structure):
+    """dpir_debug_conv3_query: one 3x3 layer as the planner sees it, for dpir_debug_conv3_plan."""
+    _fields_ = [(n, C.c_int32) for n in CONV3_QUERY_FIELDS] + [("slab_floats", C.c_longlong)]
+
+
+class ConvPlan(C.Structure):
+    """dpir_debug_conv_plan: the planner's answer for one layer."""
+    _fields_ = ([(n, C.c_int32) for n in ("kernel", "hop", "geo", "ksplit", "chunks_per_split", "stat_kind", "stat_slots", "refused")] +
+                [("workgroups", C.c_longlong)])
+
+
+class ResblockQuery(C.Structure):
+    """dpir_debug_resblock_query, for dpir_debug_resblock_plan."""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "Cin", "Cout", "H", "W", "mode", "concat", "precision", "grad", "hop_allowed")] +
+                [("arena_words_left", C.c_longlong), ("slab_floats", C.c_longlong)])
+
+
+class ResblockPlan(C.Structure):
+    """dpir_debug_resblock_plan_out."""
+    _fields_ = [(n, C.c_int32) for n in ("up", "skip_emit", "hop", "arena_counters")] + [("conv1", ConvPlan), ("conv2", ConvPlan)]
+
+
+def route_log(engine):
+    """The convolution launches of the engine's last eager forward: a list of dicts (dpir_debug_route_log)."""
+    dbg = load_debug()
+    n = C.c_int(0)
+    assert dbg.dpir_debug_route_log(engine.h, None, 0, C.byref(n)) == 0
+    recs = (RouteRec * max(n.value, 1))()
+    assert dbg.dpir_debug_route_log(engine.h, recs, n.value, C.byref(n)) == 0
+    return [dict(layer=r.layer.decode(), kernel=r.kernel, ks=r.ks, ksplit=r.ksplit, hop=r.hop, stat_kind=r.stat_kind, workgroups=r.workgroups)
+            for r in recs[:n.value]]
+
+
 class AttentionDesc(C.Structure):
     """dpir_debug_attention_desc (include/diffpir_debug.h): the attention core, forward and backward, for dpir_debug_attention."""
     _fields_ = ([(n, C.c_int32) for n in ("B", "C", "T", "head_ch")] + [(n, C.c_void_p) for n in ("qkv", "dAtt", "out", "dqkv")] +
@@ -241,12 +290,16 @@ def load_debug():
     d.dpir_debug_conv9_layer.restype = C.c_int
     d.dpir_debug_conv11_layer.argtypes = [C.c_void_p, C.POINTER(Conv11Desc)]
     d.dpir_debug_conv11_layer.restype = C.c_int
-    d.dpir_debug_conv11_counts.argtypes = [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
-    d.dpir_debug_conv11_counts.restype = None
     d.dpir_debug_conv_up_layer.argtypes = [C.c_void_p, C.POINTER(ConvUpDesc)]
     d.dpir_debug_conv_up_layer.restype = C.c_int
-    d.dpir_debug_conv_up_counts.argtypes = [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
-    d.dpir_debug_conv_up_counts.restype = None
+    d.dpir_debug_route_log.argtypes = [C.c_void_p, C.POINTER(RouteRec), C.c_int, C.POINTER(C.c_int)]
+    d.dpir_debug_route_log.restype = C.c_int
+    d.dpir_debug_conv_knobs_default.argtypes = [C.POINTER(ConvKnobs)]
+    d.dpir_debug_conv_knobs_default.restype = None
+    d.dpir_debug_conv3_plan.argtypes = [C.c_void_p, C.c_int, C.POINTER(ConvKnobs)] + [C.c_int] * 3 + [C.c_void_p]
+    d.dpir_debug_conv3_plan.restype = C.c_int
+    d.dpir_debug_resblock_plan.argtypes = [C.POINTER(ResblockQuery), C.POINTER(ConvKnobs)] + [C.c_int] * 3 + [C.POINTER(ResblockPlan)]
+    d.dpir_debug_resblock_plan.restype = C.c_int
     d.dpir_debug_attention.argtypes = [C.c_void_p, C.POINTER(AttentionDesc)]
     d.dpir_debug_attention.restype = C.c_int
     d.dpir_debug_groupnorm.argtypes = [C.c_void_p, C.POINTER(GroupNormDesc)]

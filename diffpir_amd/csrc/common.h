@@ -10,6 +10,7 @@
 #include <mutex>
 
 #include "../../include/diffpir_engine.h"
+#include "conv_plan.h"
 
 namespace dpir {
 
@@ -170,17 +171,17 @@ struct Conv6Args {
     bool x1 = false;               // single-product mode (f16x1): hi planes / hi weight halves only
     // optional device scalar folded into the output scale (dgrad, unet_bwd.hip): it multiplies the convolution sum; bias and res are added unscaled
     const float* out_scale_dev = nullptr;
-    int force_kernel = 0;          // tests only: 6 = conv6 even where conv7 applies, 7 = conv7 or an error; 0 = launch_conv6 decides
+    int force_kernel = 0;          // tests only: CK_CONV6 = conv6 even where conv7 applies, CK_CONV7 = conv7 or an error; 0 = the planner decides
     const struct Conv6Emit* emit = nullptr;    // conv6_params.h: fused emission of the NEXT convolution's operand planes instead of `out`
 };
-// true when a launch with these arguments runs whole-K on the 8 x 32 geometry with every tile inside the image (what Conv6Emit needs)
+// views of the planner (conv_plan.h) on this device: conv7's hop is possible / geometry(H, W) tiles the image / its statistics slots
 bool conv7_emit_supported(int B, int Cout, int H, int W);
 bool conv6_supported(int H, int W);
 int conv6_stat_slots(int H, int W);
-// pend_out != null: a split-K launch leaves its slabs uncombined and describes them in *pend_out (stat kind 3); the caller must
-// have them finished (gn_act_small or launch_conv6_resolve) before the slab buffer is reused.  kernel_out (tests): 6 / 7 = the kernel
-// that ran
-Status launch_conv6(hipStream_t s, const Conv6Args& a, int* stat_kind_out = nullptr, PendingConv* pend_out = nullptr, int* kernel_out = nullptr);
+// plan_out: the plan that was executed (kernel, split-K factor, statistics kind).  pend_out != null: a split-K launch leaves its slabs
+// uncombined and describes them in *pend_out (ST_PENDING); the caller must have them finished (gn_act_small or launch_conv6_resolve)
+// before the slab buffer is reused.
+Status launch_conv6(hipStream_t s, const Conv6Args& a, Conv3Plan* plan_out = nullptr, PendingConv* pend_out = nullptr);
 Status launch_conv6_resolve(hipStream_t s, const PendingConv& p);
 float pack_weights_conv6(const float* w_oihw, int cout, int cin, std::vector<uint16_t>& out);
 // conv5.hip: 1x1 convolution, f16x3 with the operand split done in-kernel from the fp32 NCHW (virtual concat) input
@@ -197,7 +198,6 @@ struct Conv5Args {
     const float* out_scale_dev = nullptr;      // optional device scalar folded into the output scale (dgrad); bias and res are added unscaled
     int force_tile = 0;                        // tests only: 1 = the 128 x 256 tile, 2 = the 64 x 128 tile, whatever the workgroup count; 0 = launch_conv5 decides
 };
-constexpr int kConv5EmitMaxC = 384;            // channels of the GroupNorm table the plane-emitting variant stages in LDS
 bool conv5_supported(int B, int Cout, int H, int W, bool has_prm = false);
 // true when launch_conv5 runs this launch on the small (64 co x 128 px) tile: shapes the large tile leaves most of the chip idle on,
 // including some conv5_supported refuses (the 8 x 8 layers at the benched batches)

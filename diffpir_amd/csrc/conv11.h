@@ -19,12 +19,11 @@ struct Conv11Args {
     const Conv6Emit* emit = nullptr;
 };
 
-// Cin % 32 == 0, Cout % 128 == 0, W % 32 == 0, H % 8 == 0
+// conv11_shape_ok / conv11_hop_ok (conv_plan.h) on this device: Cin % 32 == 0, Cout % 128 == 0, W % 32 == 0, H % 8 == 0; which layers take
+// this kernel is the planner's decision
 bool conv11_supported(int Cin, int Cout, int H, int W);
-int conv11_emit_capacity();        // resident workgroups of the emitting kernel on this device (CUs x occupancy)
 bool conv11_emit_supported(int Cout, int H, int W);
 Status launch_conv11(hipStream_t s, const Conv11Args& a);
-void conv11_launch_counts(long long* plain, long long* hop);      // launches of this process so far (captured graph replays do not count)
 // Host: OIHW fp32 -> one 1 KiB record per (pair step, co-block, wave co-half, M-tile, hi | lo) in A-fragment lane order of the 16x16x32
 // instruction; `scale` is the power of two pack_weights_conv6 chose for the same layer (every f16 half equals that pack's).
 void pack_weights_conv11(const float* w_oihw, int cout, int cin, float scale, std::vector<uint16_t>& out);

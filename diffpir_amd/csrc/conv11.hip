@@ -19,7 +19,7 @@
 // Measured back to back against conv7 on one box, random planes, B = 16 (profiles/conv11/README.md): x0.92-0.94 of conv7's time on every
 // routed shape of the FFHQ forward (128 -> 128 @256^2 762 -> 714 us, 256 -> 128 @256^2 1376 -> 1281, 256 -> 256 @128^2 706 -> 657); forward,
 // DPIR_CONV11=1/0 interleaved in one call: 16.92 vs 17.71 ms.  f16x3 only; f16x1, split-K launches, the 16 x 16 and 8 x 8 geometries, partial
-// co-blocks and gradient mode stay on launch_conv6 (Fwd::conv11_route, unet.hip).
+// co-blocks and gradient mode stay on launch_conv6 (plan_conv3, conv_plan.cpp).
 #include "common.h"
 #include "elem.h"
 #include "lds_dma.h"
@@ -529,37 +529,9 @@ __global__ __launch_bounds__(256, 2) void conv11_mfma_kernel(Conv6K p) {
 #endif
 }
 
-bool conv11_supported(int Cin, int Cout, int H, int W) {
-    return Cin > 0 && Cin % 32 == 0 && Cout > 0 && Cout % 128 == 0 && W > 0 && W % 32 == 0 && H > 0 && H % 8 == 0;
-}
-
-// Workgroups of the EMIT kernel the device holds at once (CUs x resident workgroups per CU by the occupancy API, capped by the launch bound
-// of two): conv7_emit_capacity for this kernel's own symbol.
-int conv11_emit_capacity() {
-    static std::atomic<int> caps[16];      // per device ordinal (0 = not asked yet; stored + 1)
-    int dev = 0, cus = 0, occ = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    std::atomic<int>* slot = (dev >= 0 && dev < 16) ? &caps[dev] : nullptr;
-    if (slot && slot->load() > 0) return slot->load() - 1;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, conv11_mfma_kernel<true>, 256, c11::LDS) != hipSuccess || occ < 1) occ = 1;
-    if (occ > 2) occ = 2;
-    if (slot) slot->store(cus * occ + 1);
-    return cus * occ;
-}
-
-// the waiting set -- the tiles of one (image, co-block), consecutive ids -- takes at most half of the resident workgroups (conv7's rule), and
-// a GroupNorm group (Cout / 32 channels) lies inside the 64 channels of one wave
-bool conv11_emit_supported(int Cout, int H, int W) {
-    if (Cout <= 0 || Cout % 128 || W <= 0 || W % 32 || H <= 0 || H % 8 || 64 % (Cout / 32) != 0) return false;
-    return (W / 32) * (H / 8) <= conv11_emit_capacity() / 2;
-}
-
-static std::atomic<long long> g_launches11[2];    // plain, hop (tests read them to see which route a forward took)
-void conv11_launch_counts(long long* plain, long long* hop) {
-    if (plain) *plain = g_launches11[0].load();
-    if (hop) *hop = g_launches11[1].load();
-}
+bool conv11_supported(int Cin, int Cout, int H, int W) { return conv11_shape_ok(Cin, Cout, H, W); }
+KernelRef conv11_emit_kernel() { return KernelRef{reinterpret_cast<const void*>(conv11_mfma_kernel<true>), c11::LDS}; }
+bool conv11_emit_supported(int Cout, int H, int W) { return conv11_hop_ok(Cout, H, W, device_caps().conv11); }
 
 Status launch_conv11(hipStream_t s, const Conv11Args& a) {
     if (a.grad) return Status{DPIR_ERR_UNSUPPORTED, "conv11: a gradient-mode forward keeps launch_conv6's route"};
@@ -603,7 +575,6 @@ Status launch_conv11(hipStream_t s, const Conv11Args& a) {
         hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(256), c11::LDS, s, k);
     }
     DPIR_HIP(hipGetLastError());
-    g_launches11[a.emit ? 1 : 0].fetch_add(1);
     return Status{};
 }
 

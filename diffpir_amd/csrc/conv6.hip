@@ -518,29 +518,32 @@ __global__ __launch_bounds__(256) void conv6_reduce_kernel(const float* partial,
 
 const float* conv_zero_page();
 
-static int conv6_geo(int H, int W) {
-    if ((W & 3) || W < 8 || H < 8) return -1;
-    return W >= 32 ? 0 : (W >= 16 ? 1 : 2);
-}
-bool conv6_supported(int H, int W) { return conv6_geo(H, W) >= 0; }
-// Conv6Emit: whole K (>= 384 workgroups, launch_conv6's rule), 8 x 32 tiles inside the image, full 128-channel blocks, and at most 256
-// workgroups per (image, co-block) -- the set that waits for one another, consecutive in dispatch order -- so that it is resident
-// together with room to spare (the chip holds 512)
-bool conv7_emit_supported(int B, int Cout, int H, int W) {
-    if (conv6_geo(H, W) != 0 || (W & 31) || (H & 7) || (Cout & 127)) return false;
-    // the emission folds per-group sums inside one wave: channels per group (Cout / 32) must divide the 64 channels a wave owns, i.e. Cout in
-    // {128, 256, 512, 1024, 2048}; 384 / 640 / 768 / 896 (channel_mult x3, x5, x6, x7) have groups that straddle waves -> unfused path
-    if (64 % (Cout / 32) != 0) return false;
-    const int tiles = (W / 32) * (H / 8);
-    return tiles <= conv7_emit_capacity() / 2 && tiles * (Cout / 128) * B >= 384;
-}
+bool conv6_supported(int H, int W) { return geometry(H, W).ok(); }
+int conv6_stat_slots(int H, int W) { return geometry(H, W).stat_slots; }
+bool conv7_emit_supported(int B, int Cout, int H, int W) { return conv7_hop_ok(B, Cout, H, W, device_caps().conv7); }
 
-// statistics slots per (image, channel) plane written by the epilogue when no split-K is used
-int conv6_stat_slots(int H, int W) {
-    const int g = conv6_geo(H, W);
-    if (g < 0) return 0;
-    const int tw = g == 0 ? 32 : (g == 1 ? 16 : 8), th = g == 0 ? 8 : (g == 1 ? 16 : 8);
-    return ((W + tw - 1) / tw) * ((H + th - 1) / th) * ((tw * th) / 64);
+// Workgroups of a kernel the device holds at once: CUs x resident workgroups per CU (occupancy API, capped by the launch bound of two the
+// emitting kernels are built with).  A fused hop's waiting set must fit with room to spare (at most HALF of this, conv_plan.cpp), instead of
+// the constants 256 / 512 of an MI355X being assumed.
+static int resident_workgroups(const KernelRef& k, int dev) {
+    int cus = 0, occ = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k.fn, 256, k.lds) != hipSuccess || occ < 1) occ = 1;
+    return cus * (occ > 2 ? 2 : occ);
+}
+DeviceCaps device_caps() {
+    static std::once_flag flags[16];        // per device ordinal: engines on different devices share this process
+    static DeviceCaps caps[16];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return DeviceCaps{};
+    auto fill = [dev](DeviceCaps& c) {
+        c.conv7 = resident_workgroups(conv7_emit_kernel(), dev);
+        c.conv11 = resident_workgroups(conv11_emit_kernel(), dev);
+        c.conv_up = resident_workgroups(conv_up_emit_kernel(), dev);
+    };
+    if (dev < 0 || dev >= 16) { DeviceCaps c; fill(c); return c; }
+    std::call_once(flags[dev], fill, caps[dev]);
+    return caps[dev];
 }
 
 template <int GEO, int R, bool X1>
@@ -557,7 +560,6 @@ static Status launch6(hipStream_t s, Conv6K k, int blocks) {
     return Status{};
 }
 
-// stat_kind_out: 0 none, 1 epilogue slots (a.stat filled, conv6_stat_slots entries per plane), 2 per-plane fp64 records (a.stat_plane)
 Status launch_conv6_resolve(hipStream_t s, const PendingConv& p) {
     const int planes = p.B * p.Cout;
     hipLaunchKernelGGL(conv6_reduce_kernel, dim3((unsigned)((planes + 3) / 4)), dim3(256), 0, s, p.partial, p.ksplit, p.bias, p.res, p.res_mode, p.out,
@@ -566,83 +568,43 @@ Status launch_conv6_resolve(hipStream_t s, const PendingConv& p) {
     return Status{};
 }
 
-Status launch_conv6(hipStream_t s, const Conv6Args& a, int* stat_kind_out, PendingConv* pend_out, int* kernel_out) {
-    if (stat_kind_out) *stat_kind_out = 0;
+// Executes what plan_conv67 (conv_plan.cpp) says for these arguments: tiling, split-K factor, conv6 or conv7, statistics.
+Status launch_conv6(hipStream_t s, const Conv6Args& a, Conv3Plan* plan_out, PendingConv* pend_out) {
     if (pend_out) *pend_out = PendingConv{};
-    const int geo = conv6_geo(a.H, a.W);
-    if (geo < 0) return Status{DPIR_ERR_UNSUPPORTED, "conv6: shape not tiled"};
+    Conv3Query q;
+    q.B = a.B; q.Cin = a.Cin; q.Cout = a.Cout; q.H = a.H; q.W = a.W; q.w16 = true;
+    q.slab = a.partial != nullptr; q.slab_floats = a.partial_capacity; q.defer = pend_out != nullptr;
+    q.hop = a.emit != nullptr; q.has_res = a.res != nullptr; q.out_scale_dev = a.out_scale_dev != nullptr;
+    q.stat_slots = a.stat != nullptr; q.stat_plane = a.stat_plane != nullptr; q.force_kernel = a.force_kernel;
+    const Conv3Plan p = plan_conv67(q, ConvKnobs::from_env(), a.emit ? device_caps() : DeviceCaps{});
+    if (plan_out) *plan_out = p;
+    if (p.refusal) return p.geo < 0 ? Status{DPIR_ERR_UNSUPPORTED, p.refusal} : invalid(p.refusal);
+    const Conv3Geometry g = geometry(a.H, a.W);
     Conv6K k;
     k.xhi = reinterpret_cast<const char*>(a.xhi); k.xlo = reinterpret_cast<const char*>(a.xlo);
     k.w16 = reinterpret_cast<const char*>(a.w16); k.bias = a.bias; k.out = a.out; k.res = a.res; k.res_mode = a.res_mode;
     k.B = a.B; k.Cout = a.Cout; k.H = a.H; k.W = a.W;
     k.n_chunks_total = (a.Cin + 15) / 16;
     k.C8 = 2 * k.n_chunks_total;          // act.hip pads the blocked tensor to whole 16-channel chunks
-    k.partial = a.partial; k.ksplit = 1; k.chunks_per_split = 0;
+    k.ksplit = p.ksplit; k.chunks_per_split = p.chunks_per_split;
+    k.partial = p.ksplit > 1 ? a.partial : nullptr;
     k.out_scale = 1.0f / a.w16_scale;
     k.out_scale_dev = a.out_scale_dev;
     k.zeros = conv_zero_page();
     if (!k.zeros) return Status{DPIR_ERR_NOMEM, "conv6: cannot allocate the zero page"};
-    const int tw = geo == 0 ? 32 : (geo == 1 ? 16 : 8), th = geo == 0 ? 8 : (geo == 1 ? 16 : 8), ti = geo == 2 ? 4 : 1;
-    k.tiles_x = (a.W + tw - 1) / tw;
-    k.tiles_y = (a.H + th - 1) / th;
-    const int n_ptiles = k.tiles_x * k.tiles_y * ((a.B + ti - 1) / ti);
+    k.tiles_x = g.tiles_x; k.tiles_y = g.tiles_y;
     k.n_co_blocks = (a.Cout + 127) / 128;
-    const int chunks = k.n_chunks_total;
-    const int blocks = n_ptiles * k.n_co_blocks;
-    // split-K when the launch cannot give every CU ONE workgroup (low-resolution layers); deterministic slabs.  Every slice writes a full fp32
-    // slab, so splitting trades co-resident workgroups for slab traffic.  Rounds 2-4 split below 384 workgroups up to ~512 ("two per CU");
-    // measured in round 5 (profiles/r05/split_rule_layer_roofline_and_forward_ab.log, five settings interleaved in one call): splitting only
-    // below 256 up to ~256 is faster on every affected shape -- 512 -> 512 @ 32^2 215 -> 185 us, 256 -> 256 @ 32^2 65 -> 60, 512 -> 512 @ 16^2
-    // 64 -> 58.5, 1024 -> 512 @ 16^2 108 -> 99 -- and 18.88 -> 18.73 ms per forward; larger targets (768, 1024) lose 0.7 ms.  The two constants stay
-    // read-once environment knobs for A/B runs (tools/layer_roofline.py, tools/forward_time.py).
-    static const int split_below = getenv("DPIR_SPLIT_BELOW") ? atoi(getenv("DPIR_SPLIT_BELOW")) : 256;
-    static const int split_target = getenv("DPIR_SPLIT_TARGET") ? atoi(getenv("DPIR_SPLIT_TARGET")) : 256;
-    int S = 1;
-    if (k.partial && blocks < split_below) {
-        S = (split_target + blocks - 1) / blocks;
-        if (S > chunks / 2) S = chunks / 2;
-        if (S > 16) S = 16;
-        if (S < 1) S = 1;
-        if ((size_t)S * k.B * k.Cout * k.H * k.W > a.partial_capacity) S = 1;
-    }
-    k.chunks_per_split = (chunks + S - 1) / S;
-    S = (chunks + k.chunks_per_split - 1) / k.chunks_per_split;      // no empty slice: every workgroup owns at least one chunk
-    k.ksplit = S;
-    if (S == 1) k.partial = nullptr;
-    k.stat = nullptr; k.stat_slots = 0;
-    if (a.emit) {
-        if (S != 1 || !conv7_emit_supported(a.B, a.Cout, a.H, a.W) || a.res || a.out_scale_dev) return invalid("conv6: this launch cannot emit the next convolution's planes");
-        k.em = *a.emit;
-        DPIR_TRY(launch_conv7(s, k, blocks, a.x1));
-        DPIR_HIP(hipGetLastError());
-        return Status{};
-    }
-    if (a.stat && S == 1) {
-        k.stat = a.stat; k.stat_slots = conv6_stat_slots(a.H, a.W);
-        if (stat_kind_out) *stat_kind_out = 1;
-    }
-    // conv7 (csrc/conv7.hip: same results bit for bit) is the 3x3 kernel; conv6 keeps the two launch classes of the 8 x 32 geometry it
-    // is measurably faster at (profiles/r04/conv7x_check.log): split-K launches (x1.07) and a last co-block with at most 64 live
-    // channels (x1.05) -- unless the whole launch has at most 32 output channels (the 128 -> 6 output convolution), which conv7's
-    // NARROW variant spreads over all four waves.  force_kernel (tests): 6 = conv6 (geometry 0 only), 7 = conv7.
-    const bool idle_half = (a.Cout & 127) != 0 && (a.Cout & 127) <= 64 && a.Cout > 32;
-    const bool use6 = a.force_kernel == 6 || (a.force_kernel != 7 && geo == 0 && (S > 1 || idle_half));
-    if (kernel_out) *kernel_out = use6 ? 6 : 7;
-    if (use6 && geo != 0) return invalid("conv6 is built for the 8 x 32 geometry only (conv7 has the 16 x 16 and 8 x 8 ones)");
-    if (!use6) DPIR_TRY(launch_conv7(s, k, blocks * S, a.x1));
-    else if (a.x1) DPIR_TRY((launch6<0, 4, true>(s, k, blocks * S)));
-    else DPIR_TRY((launch6<0, 4, false>(s, k, blocks * S)));
-    if (S > 1) {
+    k.stat = p.stat_kind == ST_SLOTS ? a.stat : nullptr; k.stat_slots = p.stat_slots;
+    if (p.hop) k.em = *a.emit;
+    if (p.kernel != CK_CONV6) DPIR_TRY(launch_conv7(s, k, (int)p.workgroups, a.x1));
+    else if (a.x1) DPIR_TRY((launch6<0, 4, true>(s, k, (int)p.workgroups)));
+    else DPIR_TRY((launch6<0, 4, false>(s, k, (int)p.workgroups)));
+    if (p.ksplit > 1) {
         PendingConv pc;
-        pc.partial = k.partial; pc.ksplit = S; pc.bias = k.bias; pc.res = k.res; pc.res_mode = k.res_mode; pc.out = k.out;
+        pc.partial = k.partial; pc.ksplit = p.ksplit; pc.bias = k.bias; pc.res = k.res; pc.res_mode = k.res_mode; pc.out = k.out;
         pc.B = k.B; pc.Cout = k.Cout; pc.H = k.H; pc.W = k.W; pc.stat_plane = a.stat_plane;
-        if (pend_out) {
-            *pend_out = pc;
-            if (stat_kind_out) *stat_kind_out = 3;
-        } else {
-            DPIR_TRY(launch_conv6_resolve(s, pc));
-            if (a.stat_plane && stat_kind_out) *stat_kind_out = 2;
-        }
+        if (pend_out) *pend_out = pc;
+        else DPIR_TRY(launch_conv6_resolve(s, pc));
     }
     DPIR_HIP(hipGetLastError());
     return Status{};

@@ -40,6 +40,13 @@ struct Conv6K {
 // conv7.hip: every case of launch_conv6 (all three geometries, split-K slabs, f16x1, dgrad scale) with the workgroup tile cut as
 // 64 co x 128 px per wave; blocks = pixel tiles x co-blocks x ksplit
 Status launch_conv7(hipStream_t s, const Conv6K& k, int blocks, bool x1);
-int conv7_emit_capacity();     // resident EMIT workgroups on this device (CUs x occupancy)
+
+// The three kernels whose fused hop waits across workgroups (conv7.hip, conv11.hip, conv_up.hip), and how many workgroups of each this device
+// holds at once (conv6.hip; asked once per device)
+struct KernelRef { const void* fn; size_t lds; };
+KernelRef conv7_emit_kernel();
+KernelRef conv11_emit_kernel();
+KernelRef conv_up_emit_kernel();
+DeviceCaps device_caps();
 
 }  // namespace dpir

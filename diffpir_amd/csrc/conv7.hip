@@ -556,35 +556,22 @@ static Status launch7(hipStream_t s, const Conv6K& k, int blocks) {
     return Status{};
 }
 
-// Workgroups of the EMIT kernel the device holds at once: CUs x resident workgroups per CU (occupancy API, capped by the kernel's launch
-// bound of two).  The fused hop's waiting set -- the workgroups of one (image, co-block) -- must fit with room to spare
-// (conv7_emit_supported: at most HALF of this), instead of the constants 256 / 512 of an MI355X being assumed.
-int conv7_emit_capacity() {
-    static std::atomic<int> caps[16];      // per device ordinal (0 = not asked yet; stored + 1): engines on different devices share this process
-    int dev = 0, cus = 0, occ = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    std::atomic<int>* slot = (dev >= 0 && dev < 16) ? &caps[dev] : nullptr;
-    if (slot && slot->load() > 0) return slot->load() - 1;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+KernelRef conv7_emit_kernel() {
     using G = Geo7<0>;
     constexpr int PATCH = G::TI * ((1 << G::LTH) + 2) * ((1 << G::LTW) + 2);
-    constexpr size_t LDS = (size_t)4 * ((2 * PATCH + 63) / 64) * 1024;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, conv7_mfma_kernel<0, false, false, true>, 256, LDS) != hipSuccess || occ < 1) occ = 1;
-    if (occ > 2) occ = 2;
-    if (slot) slot->store(cus * occ + 1);
-    return cus * occ;
+    return KernelRef{reinterpret_cast<const void*>(conv7_mfma_kernel<0, false, false, true>), (size_t)4 * ((2 * PATCH + 63) / 64) * 1024};
 }
 
-// k as launch_conv6 fills it (geometry from H, W as conv6_geo); blocks = pixel tiles x co-blocks x ksplit
+// k as launch_conv6 fills it (the tiling of geometry(H, W)); blocks = pixel tiles x co-blocks x ksplit
 Status launch_conv7(hipStream_t s, const Conv6K& k, int blocks, bool x1) {
-    if ((k.W & 3) || k.W < 8 || k.H < 8) return invalid("conv7: shape not tiled");
-    const int geo = k.W >= 32 ? 0 : (k.W >= 16 ? 1 : 2);
+    const int geo = geometry(k.H, k.W).geo;
+    if (geo < 0) return invalid("conv7: shape not tiled");
     if (k.em.hi) {
         if (geo != 0 || k.ksplit != 1 || (k.Cout & 127) || (k.W & 31) || (k.H & 7) || !k.em.acc || !k.em.cnt || !k.em.range_ctr || (!x1 && !k.em.lo))
             return invalid("conv7: fused emission needs the 8 x 32 geometry, whole K, full 128-channel blocks and tiles inside the image");
         return x1 ? launch7<0, true, false, true>(s, k, blocks) : launch7<0, false, false, true>(s, k, blocks);
     }
-    if (geo == 0 && k.Cout <= 32) return x1 ? launch7<0, true, true>(s, k, blocks) : launch7<0, false, true>(s, k, blocks);
+    if (conv7_narrow(geo, k.Cout)) return x1 ? launch7<0, true, true>(s, k, blocks) : launch7<0, false, true>(s, k, blocks);
     if (x1) {
         if (geo == 0) return launch7<0, true>(s, k, blocks);
         if (geo == 1) return launch7<1, true>(s, k, blocks);

@@ -44,7 +44,7 @@ constexpr int C8_ITEMS = C8_KG * C8_PATCH;                 // (group, position) 
 constexpr int C8_THREADS = 512;                            // 8 waves: one tile row (2 pixel tiles of 16) each
 constexpr int C8_NIT = (C8_ITEMS + C8_THREADS - 1) / C8_THREADS;   // per thread
 constexpr int C8_WFR = 18 * 64;                            // weight entries (half8) per K step
-constexpr int C8_MAXC = 256;
+static_assert(C8_TW == 32 && C8_TH == 8, "conv8_shape_ok (conv_plan.cpp) states this tile");
 
 __device__ __forceinline__ float silu8(float v) {          // act.hip's silu_a
     float e = __builtin_amdgcn_exp2f(v * -1.4426950408889634f);
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(C8_THREADS, 2) void conv8_fused_kernel(Conv8K p) {
     __shared__ half8 s_hi[C8_ITEMS];
     __shared__ half8 s_lo[X1 ? 1 : C8_ITEMS];
     __shared__ half8 s_w[C8_WFR];
-    __shared__ float4 s_prm[C8_MAXC];
+    __shared__ float4 s_prm[kConv8MaxC];
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -216,10 +216,7 @@ __global__ __launch_bounds__(C8_THREADS, 2) void conv8_fused_kernel(Conv8K p) {
 #endif
 }
 
-bool conv8_supported(int B, int C, int Cout, int H, int W) {
-    return B > 0 && Cout >= 1 && Cout <= 16 && C % 32 == 0 && C >= 32 && C <= C8_MAXC && H % C8_TH == 0 && W % C8_TW == 0 &&
-           (size_t)C * H * W < ((size_t)1 << 30);      // one image's bytes fit the 32-bit range of a buffer descriptor
-}
+bool conv8_supported(int B, int C, int Cout, int H, int W) { return conv8_shape_ok(B, C, Cout, H, W); }
 
 Status launch_conv8(hipStream_t s, const Conv8Args& a) {
     if (!conv8_supported(a.B, a.C, a.Cout, a.H, a.W)) return invalid("conv8: shape not supported");

@@ -25,10 +25,8 @@ struct Conv9K {
     Conv6Emit em;
 };
 
-// Workgroups (B x Cout / 32) from which Fwd (unet.hip) prefers conv9 to launch_conv6's split-K route
-constexpr int kConv9MinWg = 128;
-
-// H = W = 8, Cin % 16 == 0, Cout % 32 == 0; emit: Cout / 32 divides 32 (GroupNorm groups never straddle a 32-channel tile)
+// conv9_refusal (conv_plan.h): H = W = 8, Cin % 16 == 0, Cout % 32 == 0; emit: GroupNorm groups never straddle a 32-channel tile.  When a layer
+// takes this kernel (kConv9MinWg workgroups) is the planner's decision.
 bool conv9_supported(int B, int Cin, int Cout, int H, int W, bool emit);
 Status launch_conv9(hipStream_t s, const Conv9Args& a);
 

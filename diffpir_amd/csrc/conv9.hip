@@ -313,17 +313,6 @@ static Status launch9(hipStream_t s, const Conv9K& k, int blocks) {
     return Status{};
 }
 
-static const char* conv9_refusal(int B, int Cin, int Cout, int H, int W, bool emit) {
-    if (B <= 0 || Cin <= 0 || Cout <= 0) return "conv9: empty launch";
-    if (H != W) return "conv9: whole-image tiles need a square image";
-    if (H != 8) return "conv9: the whole-image tile is built for 8 x 8 layers only";
-    if (Cin % 16) return "conv9: the input channels must be a multiple of 16";
-    if (Cout % 32) return "conv9: the output channels must be a multiple of 32";
-    if (emit && 32 % (Cout / 32) != 0) return "conv9: fused emission needs GroupNorm groups that do not straddle a 32-channel tile";
-    if ((size_t)B * (Cin / 8) * H * W * 16 >= ((size_t)1 << 32)) return "conv9: split activation plane exceeds the 4 GiB buffer-descriptor range";
-    return nullptr;
-}
-
 bool conv9_supported(int B, int Cin, int Cout, int H, int W, bool emit) { return conv9_refusal(B, Cin, Cout, H, W, emit) == nullptr; }
 
 Status launch_conv9(hipStream_t s, const Conv9Args& a) {

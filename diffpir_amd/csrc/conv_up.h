@@ -14,18 +14,14 @@ struct ConvUpArgs {
     float2* stat = nullptr;            // optional [B][Cout][conv_up_stat_slots(Hs, Ws)] fp32 partial sums of 64 stored values each (conv6's epilogue record)
     bool x1 = false;                   // single-product mode (f16x1): hi planes / hi weight halves only
     const Conv6Emit* emit = nullptr;   // fused hop: the next convolution's planes at 2 Hs x 2 Ws instead of `out`; cnt holds B x Cout / 64 counters
-    int min_wg_hop = 0;                // the hop is refused below this many workgroups (Fwd: 384, launch_conv6's whole-K rule; tests: 0)
+    int min_wg_hop = 0;                // the hop is refused below this many workgroups (Fwd: kHopMinWg; tests: 0)
 };
 
-// Workgroups of one launch: source tiles (8 x 32) x 64-channel blocks x 2 row parities x images
-long long conv_up_workgroups(int B, int Cout, int Hs, int Ws);
-// null when the launch is supported, else the refusal text
+// conv_up_refusal (conv_plan.h) on this device: null when the launch is supported, else the refusal text
 const char* conv_up_supported(int B, int Cin, int Cout, int Hs, int Ws, bool emit, int min_wg_hop = 0);
 int conv_up_stat_slots(int Hs, int Ws);          // == conv6_stat_slots(2 Hs, 2 Ws)
-int conv_up_emit_capacity();                     // resident workgroups of the hop kernel on this device (CUs x occupancy)
 // OIHW fp32 3x3 -> phase pack; returns the power-of-two scale (max |combined weight| * scale in [512, 1024))
 float pack_weights_conv_up(const float* w_oihw, int cout, int cin, std::vector<uint16_t>& out);
 Status launch_conv_up(hipStream_t s, const ConvUpArgs& a);
-void conv_up_launch_counts(long long* plain, long long* hop);    // launches of this process so far (captured graph replays do not count)
 
 }  // namespace dpir

@@ -478,51 +478,10 @@ static Status launch_up(hipStream_t s, const Conv6K& k, int blocks) {
     return Status{};
 }
 
-// conv7_emit_capacity's rule for this kernel: CUs x resident workgroups per CU (occupancy API, capped by the launch bound of two)
-int conv_up_emit_capacity() {
-    static std::atomic<int> caps[16];      // per device ordinal (0 = not asked yet; stored + 1)
-    int dev = 0, cus = 0, occ = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    std::atomic<int>* slot = (dev >= 0 && dev < 16) ? &caps[dev] : nullptr;
-    if (slot && slot->load() > 0) return slot->load() - 1;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, conv_up_kernel<false, true>, 256, kConvUpLds) != hipSuccess || occ < 1) occ = 1;
-    if (occ > 2) occ = 2;
-    if (slot) slot->store(cus * occ + 1);
-    return cus * occ;
-}
-
-long long conv_up_workgroups(int B, int Cout, int Hs, int Ws) {
-    return (long long)B * (Ws / 32) * (Hs / 8) * ((Cout + 63) / 64) * 2;
-}
-
-int conv_up_stat_slots(int Hs, int Ws) { return (Ws / 32) * (Hs / 8) * 16; }
-
+KernelRef conv_up_emit_kernel() { return KernelRef{reinterpret_cast<const void*>(conv_up_kernel<false, true>), kConvUpLds}; }
+int conv_up_stat_slots(int Hs, int Ws) { return geometry(2 * Hs, 2 * Ws).stat_slots; }
 const char* conv_up_supported(int B, int Cin, int Cout, int Hs, int Ws, bool emit, int min_wg_hop) {
-    if (B <= 0 || Cin <= 0 || Cout <= 0 || Hs <= 0 || Ws <= 0) return "conv_up: bad shape";
-    if (Ws & 31) return "conv_up: the source width must be a multiple of 32";
-    if (Hs & 7) return "conv_up: the source height must be a multiple of 8";
-    if (Cin & 15) return "conv_up: the input channels must be a multiple of 16";
-    if (Cout & 31) return "conv_up: the output channels must be a multiple of 32";
-    const size_t HW = (size_t)Hs * Ws;
-    if ((size_t)B * (Cin / 8) * HW * 16 >= ((size_t)1 << 32) || (size_t)Cout * HW * 16 >= ((size_t)1 << 32) ||
-        conv_up_workgroups(B, Cout, Hs, Ws) >= ((long long)1 << 31))
-        return "conv_up: operand planes or one image's output exceed the 4 GiB buffer-descriptor range";
-    if (emit) {
-        // the emission folds per-group sums inside one wave: channels per group (Cout / 32) must divide the 32 channels a wave owns
-        if ((Cout & 63) || 32 % (Cout / 32) != 0) return "conv_up: GroupNorm groups of the hop must not straddle a wave's 32 channels (Cout 128, 256, 512 or 1024)";
-        const int wait_set = 2 * (Ws / 32) * (Hs / 8);
-        if (wait_set > conv_up_emit_capacity() / 2) return "conv_up: the hop's wait set exceeds half of the resident workgroups";
-        if (conv_up_workgroups(B, Cout, Hs, Ws) < min_wg_hop) return "conv_up: too few workgroups for the hop";
-        if ((size_t)B * (Cout / 8) * HW * 4 * 16 >= ((size_t)1 << 32)) return "conv_up: the emitted planes exceed the 4 GiB range";
-    }
-    return nullptr;
-}
-
-static std::atomic<long long> g_launches[2];      // plain, hop (tests read them to see which route a forward took)
-void conv_up_launch_counts(long long* plain, long long* hop) {
-    if (plain) *plain = g_launches[0].load();
-    if (hop) *hop = g_launches[1].load();
+    return conv_up_refusal(B, Cin, Cout, Hs, Ws, emit, min_wg_hop, emit ? device_caps().conv_up : 0);
 }
 
 Status launch_conv_up(hipStream_t s, const ConvUpArgs& a) {
@@ -550,7 +509,6 @@ Status launch_conv_up(hipStream_t s, const ConvUpArgs& a) {
         DPIR_TRY((a.x1 ? launch_up<true, false>(s, k, blocks) : launch_up<false, false>(s, k, blocks)));
     }
     DPIR_HIP(hipGetLastError());
-    ++g_launches[a.emit ? 1 : 0];
     return Status{};
 }
 

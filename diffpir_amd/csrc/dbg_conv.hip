@@ -40,6 +40,83 @@ __global__ void dbg_bitdiff_kernel(const float* a, const float* b, size_t n, uns
     if (cnt) { atomicAdd(&out[0], cnt); atomicMax(&out[1], (unsigned long long)mx); }
 }
 
+// `launch` repeated `iters` times back to back on the stream: *ms_out = average time of one repeat (untouched when iters <= 0)
+template <class F>
+static Status time_repeats(hipStream_t s, int iters, F&& launch, double* ms_out) {
+    if (iters <= 0) return Status{};
+    hipEvent_t e0, e1;
+    DPIR_HIP(hipEventCreate(&e0)); DPIR_HIP(hipEventCreate(&e1));
+    DPIR_HIP(hipEventRecord(e0, s));
+    for (int i = 0; i < iters; ++i) DPIR_TRY(launch());
+    DPIR_HIP(hipEventRecord(e1, s));
+    DPIR_HIP(hipEventSynchronize(e1));
+    float ms = 0; DPIR_HIP(hipEventElapsedTime(&ms, e0, e1));
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    *ms_out = ms / iters;
+    return Status{};
+}
+
+// epilogue slots [planes][slots] (fp32 partial sums of at most 256 values) folded in fp64 (gn_prm's contract) into stat_out[planes][2]
+static Status fold_slots(const float2* st, size_t planes, int slots, double* stat_out) {
+    std::vector<float2> hs(planes * slots);
+    DPIR_HIP(hipMemcpy(hs.data(), st, hs.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t pl = 0; pl < planes; ++pl) {
+        double s1 = 0.0, s2 = 0.0;
+        for (int k = 0; k < slots; ++k) { s1 += (double)hs[pl * slots + k].x; s2 += (double)hs[pl * slots + k].y; }
+        stat_out[2 * pl] = s1; stat_out[2 * pl + 1] = s2;
+    }
+    return Status{};
+}
+
+// The second layer of a two-layer hop probe (fields gamma2, beta2, film2, w2, bias2, Cout2 of the descriptors): its poisoned planes and output,
+// GroupNorm affine, FiLM rows, bias and conv6-layout weights on the device, and the Conv6Emit the first layer's epilogue is given.
+// counters > 0: an arena with the accumulators and that many arrival counters per image (to be zeroed before every launch of the first layer).
+struct HopStage {
+    char* s16b = nullptr; size_t plane2 = 0, no2 = 0, arena_words = 0;
+    float *dbias2 = nullptr, *dout2 = nullptr; void* wp2 = nullptr; float w2_scale = 1.f; long long* arena = nullptr;
+    Conv6Emit em;
+};
+template <class Desc>
+static Status hop_stage(dpir_engine* e, const std::string& tag, const Desc* d, int B, int Cout, size_t HW, bool x1, int counters, HopStage* h) {
+    const int Co2 = d->Cout2, C8b = 2 * ((Cout + 15) / 16);
+    h->plane2 = (size_t)B * C8b * HW * 16; h->no2 = (size_t)B * Co2 * HW;
+    float *dg = nullptr, *db = nullptr, *df = nullptr;
+    DPIR_TRY(e->ws.getT(tag + "#s16b", 2 * h->plane2, &h->s16b));
+    DPIR_TRY(e->ws.getT(tag + "#gamma2", (size_t)Cout, &dg));
+    DPIR_TRY(e->ws.getT(tag + "#beta2", (size_t)Cout, &db));
+    DPIR_TRY(e->ws.getT(tag + "#film2", (size_t)B * 2 * Cout, &df));
+    DPIR_TRY(e->ws.getT(tag + "#b2", (size_t)round_up(Co2, 64), &h->dbias2));
+    DPIR_TRY(e->ws.getT(tag + "#o2", h->no2, &h->dout2));
+    DPIR_HIP(hipMemsetAsync(h->s16b, 0xFF, 2 * h->plane2, e->stream));
+    DPIR_HIP(hipMemcpy(dg, d->gamma2, (size_t)Cout * 4, hipMemcpyHostToDevice));
+    DPIR_HIP(hipMemcpy(db, d->beta2, (size_t)Cout * 4, hipMemcpyHostToDevice));
+    if (d->film2) DPIR_HIP(hipMemcpy(df, d->film2, (size_t)B * 2 * Cout * 4, hipMemcpyHostToDevice));
+    DPIR_HIP(hipMemset(h->dbias2, 0, (size_t)round_up(Co2, 64) * 4));
+    DPIR_HIP(hipMemcpy(h->dbias2, d->bias2, (size_t)Co2 * 4, hipMemcpyHostToDevice));
+    DPIR_HIP(hipMemsetAsync(h->dout2, 0xFF, h->no2 * 4, e->stream));
+    std::vector<uint16_t> w16b;
+    h->w2_scale = pack_weights_conv6(d->w2, Co2, Cout, w16b);
+    DPIR_TRY(e->ws.get(tag + "#w16b", w16b.size() * 2, &h->wp2));
+    DPIR_HIP(hipMemcpy(h->wp2, w16b.data(), w16b.size() * 2, hipMemcpyHostToDevice));
+    Conv6Emit& em = h->em;
+    em.hi = h->s16b; em.lo = x1 ? nullptr : h->s16b + h->plane2; em.C8 = C8b; em.gamma = dg; em.beta = db;
+    em.film = d->film2 ? df : nullptr; em.film_stride = 2 * Cout; em.film_off = 0; em.frows = 2 * Cout; em.fstep = nullptr;
+    em.range_ctr = e->range_ctr;
+    if (counters > 0) {
+        h->arena_words = (size_t)B * 64 + ((size_t)B * counters + 1) / 2;
+        DPIR_TRY(e->ws.getT(tag + "#arena", h->arena_words, &h->arena));
+        em.acc = h->arena; em.cnt = reinterpret_cast<unsigned*>(h->arena + (size_t)B * 64);
+    }
+    return Status{};
+}
+// the second layer through launch_conv6
+static Conv6Args second_conv6(const HopStage& h, int B, int Cin, int Cout, int H, int W, bool x1) {
+    Conv6Args c6;
+    c6.x1 = x1; c6.xhi = h.s16b; c6.xlo = h.s16b + h.plane2; c6.w16 = h.wp2; c6.w16_scale = h.w2_scale;
+    c6.bias = h.dbias2; c6.out = h.dout2; c6.B = B; c6.Cin = Cin; c6.Cout = Cout; c6.H = H; c6.W = W;
+    return c6;
+}
+
 extern "C" {
 // Times one convolution shape in isolation (synthetic operands already on the device).  mode bits: 0 = exact-fp32 kernels,
 // 1 = f16x3 (conv6 for 3x3 incl. its act_split pre-pass, conv5 for 1x1), 2 = f16x3 without the pre-pass (planes prepared once).
@@ -101,15 +178,7 @@ int dpir_debug_conv_bench(dpir_engine* e, int B, int Cin, int Cout, int H, int W
         return launch_conv(e->stream, a);
     };
     API_TRY(e, run_once());
-    hipEvent_t e0, e1;
-    API_HIP(e, hipEventCreate(&e0)); API_HIP(e, hipEventCreate(&e1));
-    API_HIP(e, hipEventRecord(e0, e->stream));
-    for (int i = 0; i < iters; ++i) API_TRY(e, run_once());
-    API_HIP(e, hipEventRecord(e1, e->stream));
-    API_HIP(e, hipEventSynchronize(e1));
-    float ms = 0; API_HIP(e, hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    *ms_out = ms / iters;
+    API_TRY(e, time_repeats(e->stream, iters, run_once, ms_out));
     return DPIR_OK;
 }
 
@@ -163,30 +232,22 @@ int dpir_debug_conv7_check(dpir_engine* e, int B, int Cin, int Cout, int H, int 
     if (scaled) a6.out_scale_dev = scale;
     a6.out = o6; a6.stat = st6; a6.force_kernel = 6;
     if (split) { a6.partial = p6; a6.partial_capacity = pcap; }
-    // the parameter block launch_conv6 would build, for conv7 (same tiling and the same split rule)
+    // the parameter block launch_conv6 builds, for conv7: the same plan with the other kernel forced
+    Conv3Query q;
+    q.B = B; q.Cin = Cin; q.Cout = Cout; q.H = H; q.W = W; q.w16 = true; q.slab = split != 0; q.slab_floats = pcap; q.defer = true;
+    q.has_res = res_mode >= 0; q.out_scale_dev = scaled != 0; q.stat_slots = true; q.force_kernel = CK_CONV7;
+    const Conv3Plan plan7 = plan_conv67(q, ConvKnobs::from_env(), DeviceCaps{});
+    if (plan7.refusal) return fail(e, invalid(plan7.refusal));
+    const Conv3Geometry g = geometry(H, W);
+    const int S = plan7.ksplit, blocks = (int)(plan7.workgroups / S);
     Conv6K k;
     k.xhi = reinterpret_cast<const char*>(a6.xhi); k.xlo = reinterpret_cast<const char*>(a6.xlo);
     k.w16 = reinterpret_cast<const char*>(wp); k.bias = bias; k.out = o7; k.res = a6.res; k.res_mode = a6.res_mode;
     k.B = B; k.Cout = Cout; k.H = H; k.W = W; k.n_chunks_total = chunks; k.C8 = C8;
     k.out_scale = 1.0f / w16_scale; k.out_scale_dev = a6.out_scale_dev; k.zeros = nullptr;
-    const int geo = W >= 32 ? 0 : (W >= 16 ? 1 : 2);
-    const int tw = geo == 0 ? 32 : (geo == 1 ? 16 : 8), th = geo == 0 ? 8 : (geo == 1 ? 16 : 8), ti = geo == 2 ? 4 : 1;
-    k.tiles_x = (W + tw - 1) / tw; k.tiles_y = (H + th - 1) / th;
-    const int n_ptiles = k.tiles_x * k.tiles_y * ((B + ti - 1) / ti);
-    k.n_co_blocks = (Cout + 127) / 128;
-    const int blocks = n_ptiles * k.n_co_blocks;
-    int S = 1;
-    if (split && blocks < 384) {
-        S = (512 + blocks - 1) / blocks;
-        if (S > chunks / 2) S = chunks / 2;
-        if (S > 16) S = 16;
-        if (S < 1) S = 1;
-        if ((size_t)S * no > pcap) S = 1;
-    }
-    k.chunks_per_split = (chunks + S - 1) / S;
-    S = (chunks + k.chunks_per_split - 1) / k.chunks_per_split;
-    k.ksplit = S; k.partial = S > 1 ? p7 : nullptr;
-    k.stat = S == 1 ? st7 : nullptr; k.stat_slots = S == 1 ? slots : 0;
+    k.tiles_x = g.tiles_x; k.tiles_y = g.tiles_y; k.n_co_blocks = (Cout + 127) / 128;
+    k.chunks_per_split = plan7.chunks_per_split; k.ksplit = S; k.partial = S > 1 ? p7 : nullptr;
+    k.stat = S == 1 ? st7 : nullptr; k.stat_slots = plan7.stat_slots;
     *ksplit_out = S;
     API_HIP(e, hipMemsetAsync(o6, 0xFF, no * 4, e->stream));
     API_HIP(e, hipMemsetAsync(o7, 0x7F, no * 4, e->stream));
@@ -194,10 +255,10 @@ int dpir_debug_conv7_check(dpir_engine* e, int B, int Cin, int Cout, int H, int 
     API_HIP(e, hipMemsetAsync(st7, 0x7F, nst * 8, e->stream));
     if (split) { API_HIP(e, hipMemsetAsync(p6, 0xFF, (size_t)S * no * 4, e->stream)); API_HIP(e, hipMemsetAsync(p7, 0x7F, (size_t)S * no * 4, e->stream)); }
     API_HIP(e, hipMemsetAsync(cmp, 0, 16, e->stream));
-    int k6 = 0;
+    Conv3Plan plan6;
     PendingConv pend;
-    API_TRY(e, launch_conv6(e->stream, a6, &k6, &pend));
-    if ((S > 1) != (k6 == 3) || (S > 1 && pend.ksplit != S)) return fail(e, Status{DPIR_ERR_INVALID, "conv7 check: the split rule of launch_conv6 changed"});
+    API_TRY(e, launch_conv6(e->stream, a6, &plan6, &pend));
+    if (plan6.kernel != CK_CONV6 || plan6.ksplit != S) return fail(e, Status{DPIR_ERR_INVALID, "conv7 check: forcing the kernel changed the plan"});
     API_TRY(e, launch_conv7(e->stream, k, blocks * S, x1 != 0));
     API_HIP(e, hipGetLastError());
     if (S > 1) {
@@ -214,9 +275,9 @@ int dpir_debug_conv7_check(dpir_engine* e, int B, int Cin, int Cout, int H, int 
     *maxdiff_out = __builtin_bit_cast(float, mb);
     hipEvent_t e0, e1, e2;
     API_HIP(e, hipEventCreate(&e0)); API_HIP(e, hipEventCreate(&e1)); API_HIP(e, hipEventCreate(&e2));
-    for (int i = 0; i < 3; ++i) { API_TRY(e, launch_conv6(e->stream, a6, &k6, &pend)); API_TRY(e, launch_conv7(e->stream, k, blocks * S, x1 != 0)); }
+    for (int i = 0; i < 3; ++i) { API_TRY(e, launch_conv6(e->stream, a6, &plan6, &pend)); API_TRY(e, launch_conv7(e->stream, k, blocks * S, x1 != 0)); }
     API_HIP(e, hipEventRecord(e0, e->stream));
-    for (int i = 0; i < iters; ++i) API_TRY(e, launch_conv6(e->stream, a6, &k6, &pend));
+    for (int i = 0; i < iters; ++i) API_TRY(e, launch_conv6(e->stream, a6, &plan6, &pend));
     API_HIP(e, hipEventRecord(e1, e->stream));
     for (int i = 0; i < iters; ++i) API_TRY(e, launch_conv7(e->stream, k, blocks * S, x1 != 0));
     API_HIP(e, hipEventRecord(e2, e->stream));
@@ -291,8 +352,9 @@ int dpir_debug_conv5_layer(dpir_engine* e, int B, int ca, int cb, int Cout, int 
 }
 
 // One 3x3 layer on caller-supplied host operands (include/diffpir_debug.h dpir_debug_conv3_desc): the prologue the forward would run
-// (none / act_split or the fp32 kernel's own table prologue / gn_act_small), then launch_conv6, launch_conv8 or launch_conv as Fwd::conv
-// and Fwd::gn_conv (unet.hip) call them.  Which kernel ran, the split-K factor and the statistics kind are read back from the launchers.
+// (none / act_split or the fp32 kernel's own table prologue / gn_act_small), then the kernel plan_conv3 (conv_plan.h) names with conv9 and
+// conv11 switched off (they have probes of their own) and conv8 by request only.  Which kernel ran, the split-K factor and the statistics
+// kind are the plan launch_conv6 executed.
 int dpir_debug_conv3_layer(dpir_engine* e, dpir_debug_conv3_desc* d) {
     if (!e || !d) return DPIR_ERR_INVALID;
     d->path_out = -1; d->ksplit_out = 0; d->stat_kind_out = 0;
@@ -334,8 +396,13 @@ int dpir_debug_conv3_layer(dpir_engine* e, dpir_debug_conv3_desc* d) {
     const int res_mode = d->res_mode >= 0 ? d->res_mode : 0;
     const CatSrc src{dxa, ca, cb ? dxb : nullptr, cb};
     const bool x1 = e->precision == 2;
-    const bool f16path = e->precision != 0 && conv6_supported(H, W);
     const size_t pcap = (size_t)16 * no;                       // room for 16 slabs
+    ConvKnobs knobs = ConvKnobs::from_env();
+    knobs.conv8 = knobs.conv9 = knobs.conv11 = false;
+    Conv3Query q;
+    q.B = B; q.Cin = C; q.Cout = Cout; q.H = H; q.W = W; q.precision = e->precision; q.w16 = e->precision != 0;
+    q.slab = d->split != 0; q.slab_floats = pcap; q.defer = d->defer != 0; q.has_res = res != nullptr; q.out_scale_dev = d->scaled != 0;
+    const bool f16path = plan_conv3(q, knobs, DeviceCaps{}).kernel != CK_FP32;
     float* partial = nullptr;
     if (d->split) {
         API_TRY(e, e->ws.getT("c3#partial", pcap, &partial));
@@ -436,24 +503,22 @@ int dpir_debug_conv3_layer(dpir_engine* e, dpir_debug_conv3_desc* d) {
         API_HIP(e, hipMemset(sp, 0xFF, (size_t)B * Cout * 16));
     }
     a6.stat = st; a6.stat_plane = sp;
-    int kind = 0, kernel = 0;
+    Conv3Plan ran;
     PendingConv pc;
-    API_TRY(e, launch_conv6(e->stream, a6, &kind, d->defer ? &pc : nullptr, &kernel));
-    d->path_out = kernel; d->stat_kind_out = kind;
-    d->ksplit_out = kind == 3 ? pc.ksplit : 1;
-    if (d->split && !d->defer) {     // the resolved launch keeps its factor to itself: the same launch again with the combine left pending
+    API_TRY(e, launch_conv6(e->stream, a6, &ran, d->defer ? &pc : nullptr));
+    const int kind = ran.stat_kind;
+    d->path_out = ran.kernel == CK_CONV6 ? 6 : 7; d->stat_kind_out = kind; d->ksplit_out = ran.ksplit;
+    if (d->split && !d->defer) {     // the same launch again with the combine left pending and finished by launch_conv6_resolve
         PendingConv probe;
         Conv6Args b6 = a6;
         float* o2 = nullptr;
         API_TRY(e, e->ws.getT("c3#o_again", no, &o2));
         b6.out = o2;
-        int k2 = 0;
         API_HIP(e, hipStreamSynchronize(e->stream));
         std::vector<float> first(no);
         API_HIP(e, hipMemcpy(first.data(), dout, no * 4, hipMemcpyDeviceToHost));
-        API_TRY(e, launch_conv6(e->stream, b6, &k2, &probe));
-        d->ksplit_out = k2 == 3 ? probe.ksplit : 1;
-        if (k2 == 3) API_TRY(e, launch_conv6_resolve(e->stream, probe));
+        API_TRY(e, launch_conv6(e->stream, b6, nullptr, &probe));
+        if (probe.partial) API_TRY(e, launch_conv6_resolve(e->stream, probe));
         API_HIP(e, hipStreamSynchronize(e->stream));
         // both launches ran the same slabs in the same order: the output of the first one is what is returned, the second must equal it
         std::vector<float> again(no);
@@ -461,7 +526,7 @@ int dpir_debug_conv3_layer(dpir_engine* e, dpir_debug_conv3_desc* d) {
         if (memcmp(first.data(), again.data(), no * 4) != 0) return fail(e, Status{DPIR_ERR_STATE, "conv3 layer: two identical split-K launches disagree"});
     }
     if (d->defer) {
-        if (kind != 3) return fail(e, invalid("conv3 layer: defer was asked for but launch_conv6 did not split this launch"));
+        if (kind != ST_PENDING) return fail(e, invalid("conv3 layer: defer was asked for but launch_conv6 did not split this launch"));
         // Fwd::gn_conv after a split-K conv1: the fused prologue of the next layer combines the slabs (and stores the finished tensor)
         const int Cn = Cout, Co2 = d->Cout2;
         if (Cn % 16 || !gn_act_small_supported(Cn, H, W, 0)) return fail(e, Status{DPIR_ERR_UNSUPPORTED, "conv3 layer: gn_act_small refuses the second stage"});
@@ -499,14 +564,8 @@ int dpir_debug_conv3_layer(dpir_engine* e, dpir_debug_conv3_desc* d) {
     API_HIP(e, hipStreamSynchronize(e->stream));
     API_HIP(e, hipMemcpy(d->out, dout, no * 4, hipMemcpyDeviceToHost));
     if (d->stat_out && (kind == 1 || kind == 2)) {
-        if (kind == 1) {        // epilogue slots: fp32 partial sums of at most 256 values, folded in fp64 (gn_prm's contract)
-            std::vector<float2> hs(nst);
-            API_HIP(e, hipMemcpy(hs.data(), st, nst * 8, hipMemcpyDeviceToHost));
-            for (size_t pl = 0; pl < (size_t)B * Cout; ++pl) {
-                double s1 = 0.0, s2 = 0.0;
-                for (int k = 0; k < slots; ++k) { s1 += (double)hs[pl * slots + k].x; s2 += (double)hs[pl * slots + k].y; }
-                d->stat_out[2 * pl] = s1; d->stat_out[2 * pl + 1] = s2;
-            }
+        if (kind == 1) {
+            API_TRY(e, fold_slots(st, (size_t)B * Cout, slots, d->stat_out));
         } else {
             API_HIP(e, hipMemcpy(d->stat_out, sp, (size_t)B * Cout * 16, hipMemcpyDeviceToHost));
         }
@@ -562,63 +621,27 @@ int dpir_debug_conv9_layer(dpir_engine* e, dpir_debug_conv9_desc* d) {
     if (d->res_mode >= 0) { a9.res = dres; a9.res_mode = d->res_mode; }
     a9.B = B; a9.Cin = Cin; a9.Cout = Cout; a9.H = H; a9.W = W; a9.stat_plane = sp; a9.x1 = x1;
     d->ms_out = 0.0;
-    auto timed = [&](auto&& launch) -> int {       // iters > 0: the launch again, back to back, averaged
-        if (d->iters <= 0) return DPIR_OK;
-        hipEvent_t e0, e1;
-        API_HIP(e, hipEventCreate(&e0)); API_HIP(e, hipEventCreate(&e1));
-        API_HIP(e, hipEventRecord(e0, e->stream));
-        for (int i = 0; i < d->iters; ++i) API_TRY(e, launch());
-        API_HIP(e, hipEventRecord(e1, e->stream));
-        API_HIP(e, hipEventSynchronize(e1));
-        float ms = 0; API_HIP(e, hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        d->ms_out = ms / d->iters;
-        return DPIR_OK;
-    };
     if (!d->hop) {
         API_TRY(e, launch_conv9(e->stream, a9));
-        if (int rc = timed([&]() { return launch_conv9(e->stream, a9); })) return rc;
+        API_TRY(e, time_repeats(e->stream, d->iters, [&]() { return launch_conv9(e->stream, a9); }, &d->ms_out));
         API_HIP(e, hipStreamSynchronize(e->stream));
         d->ran_out = 1;
         API_HIP(e, hipMemcpy(d->out, dout, no * 4, hipMemcpyDeviceToHost));
         if (d->stat_out) API_HIP(e, hipMemcpy(d->stat_out, sp, (size_t)B * Cout * 16, hipMemcpyDeviceToHost));
         return DPIR_OK;
     }
-    const int Co2 = d->Cout2, C8b = 2 * ((Cout + 15) / 16);
-    const size_t plane2 = (size_t)B * C8b * HW * 16, no2 = (size_t)B * Co2 * HW;
-    char* s16b = nullptr; float *dg = nullptr, *db = nullptr, *df = nullptr, *dbias2 = nullptr, *dout2 = nullptr;
-    API_TRY(e, e->ws.getT("c9#s16b", 2 * plane2, &s16b));
-    API_TRY(e, e->ws.getT("c9#gamma2", (size_t)Cout, &dg));
-    API_TRY(e, e->ws.getT("c9#beta2", (size_t)Cout, &db));
-    API_TRY(e, e->ws.getT("c9#film2", (size_t)B * 2 * Cout, &df));
-    API_TRY(e, e->ws.getT("c9#b2", (size_t)round_up(Co2, 64), &dbias2));
-    API_TRY(e, e->ws.getT("c9#o2", no2, &dout2));
-    API_HIP(e, hipMemsetAsync(s16b, 0xFF, 2 * plane2, e->stream));
-    API_HIP(e, hipMemcpy(dg, d->gamma2, (size_t)Cout * 4, hipMemcpyHostToDevice));
-    API_HIP(e, hipMemcpy(db, d->beta2, (size_t)Cout * 4, hipMemcpyHostToDevice));
-    if (d->film2) API_HIP(e, hipMemcpy(df, d->film2, (size_t)B * 2 * Cout * 4, hipMemcpyHostToDevice));
-    API_HIP(e, hipMemset(dbias2, 0, (size_t)round_up(Co2, 64) * 4));
-    API_HIP(e, hipMemcpy(dbias2, d->bias2, (size_t)Co2 * 4, hipMemcpyHostToDevice));
-    API_HIP(e, hipMemsetAsync(dout2, 0xFF, no2 * 4, e->stream));
-    std::vector<uint16_t> w16b;
-    const float w16b_scale = pack_weights_conv6(d->w2, Co2, Cout, w16b);
-    void* wp2 = nullptr;
-    API_TRY(e, e->ws.get("c9#w16b", w16b.size() * 2, &wp2));
-    API_HIP(e, hipMemcpy(wp2, w16b.data(), w16b.size() * 2, hipMemcpyHostToDevice));
-    Conv6Emit em;
-    em.hi = s16b; em.lo = x1 ? nullptr : s16b + plane2; em.C8 = C8b; em.gamma = dg; em.beta = db;
-    em.film = d->film2 ? df : nullptr; em.film_stride = 2 * Cout; em.film_off = 0; em.frows = 2 * Cout; em.fstep = nullptr;
-    em.range_ctr = e->range_ctr;
-    a9.out = nullptr; a9.stat_plane = nullptr; a9.emit = &em;
+    HopStage h;
+    API_TRY(e, hop_stage(e, "c9", d, B, Cout, HW, x1, 0, &h));
+    a9.out = nullptr; a9.stat_plane = nullptr; a9.emit = &h.em;
     API_TRY(e, launch_conv9(e->stream, a9));
     Conv9Args b9;
-    b9.xhi = s16b; b9.xlo = s16b + plane2; b9.w16 = wp2; b9.w16_scale = w16b_scale; b9.bias = dbias2; b9.out = dout2;
-    b9.B = B; b9.Cin = Cout; b9.Cout = Co2; b9.H = H; b9.W = W; b9.x1 = x1;
+    b9.xhi = h.s16b; b9.xlo = h.s16b + h.plane2; b9.w16 = h.wp2; b9.w16_scale = h.w2_scale; b9.bias = h.dbias2; b9.out = h.dout2;
+    b9.B = B; b9.Cin = Cout; b9.Cout = d->Cout2; b9.H = H; b9.W = W; b9.x1 = x1;
     API_TRY(e, launch_conv9(e->stream, b9));
-    if (int rc = timed([&]() -> Status { DPIR_TRY(launch_conv9(e->stream, a9)); return launch_conv9(e->stream, b9); })) return rc;
+    API_TRY(e, time_repeats(e->stream, d->iters, [&]() -> Status { DPIR_TRY(launch_conv9(e->stream, a9)); return launch_conv9(e->stream, b9); }, &d->ms_out));
     API_HIP(e, hipStreamSynchronize(e->stream));
     d->ran_out = 1;
-    API_HIP(e, hipMemcpy(d->out2, dout2, no2 * 4, hipMemcpyDeviceToHost));
+    API_HIP(e, hipMemcpy(d->out2, h.dout2, h.no2 * 4, hipMemcpyDeviceToHost));
     return DPIR_OK;
 }
 
@@ -691,74 +714,30 @@ int dpir_debug_conv11_layer(dpir_engine* e, dpir_debug_conv11_desc* d) {
     a6.xhi = s16; a6.xlo = s16 + plane; a6.w16 = wp; a6.w16_scale = w16_scale; a6.bias = dbias; a6.out = dout;
     if (d->res_mode >= 0) { a6.res = dres; a6.res_mode = d->res_mode; }
     a6.B = B; a6.Cin = Cin; a6.Cout = Cout; a6.H = H; a6.W = W; a6.stat = nst ? st : nullptr; a6.force_kernel = 7;
-    // second layer and the hop's arena (dpir_debug_conv_up_layer's)
-    const int Co2 = d->hop ? d->Cout2 : 0, C8b = 2 * ((Cout + 15) / 16);
-    const size_t plane2 = (size_t)B * C8b * HW * 16, no2 = (size_t)B * Co2 * HW;
-    const size_t arena_words = (size_t)B * 64 + ((size_t)B * ((Cout + 63) / 64) + 1) / 2;
-    char* s16b = nullptr; float *dg = nullptr, *db = nullptr, *df = nullptr, *dbias2 = nullptr, *dout2 = nullptr; long long* arena = nullptr; void* wp2 = nullptr;
-    Conv6Emit em;
+    HopStage h;
     Conv6Args c6;
     if (d->hop) {
-        API_TRY(e, e->ws.getT("c11#s16b", 2 * plane2, &s16b));
-        API_TRY(e, e->ws.getT("c11#gamma2", (size_t)Cout, &dg));
-        API_TRY(e, e->ws.getT("c11#beta2", (size_t)Cout, &db));
-        API_TRY(e, e->ws.getT("c11#film2", (size_t)B * 2 * Cout, &df));
-        API_TRY(e, e->ws.getT("c11#b2", (size_t)round_up(Co2, 64), &dbias2));
-        API_TRY(e, e->ws.getT("c11#o2", no2, &dout2));
-        API_TRY(e, e->ws.getT("c11#arena", arena_words, &arena));
-        API_HIP(e, hipMemsetAsync(s16b, 0xFF, 2 * plane2, e->stream));
-        API_HIP(e, hipMemcpy(dg, d->gamma2, (size_t)Cout * 4, hipMemcpyHostToDevice));
-        API_HIP(e, hipMemcpy(db, d->beta2, (size_t)Cout * 4, hipMemcpyHostToDevice));
-        if (d->film2) API_HIP(e, hipMemcpy(df, d->film2, (size_t)B * 2 * Cout * 4, hipMemcpyHostToDevice));
-        API_HIP(e, hipMemset(dbias2, 0, (size_t)round_up(Co2, 64) * 4));
-        API_HIP(e, hipMemcpy(dbias2, d->bias2, (size_t)Co2 * 4, hipMemcpyHostToDevice));
-        API_HIP(e, hipMemsetAsync(dout2, 0xFF, no2 * 4, e->stream));
-        std::vector<uint16_t> w16b;
-        const float w2_scale = pack_weights_conv6(d->w2, Co2, Cout, w16b);
-        API_TRY(e, e->ws.get("c11#w16b", w16b.size() * 2, &wp2));
-        API_HIP(e, hipMemcpy(wp2, w16b.data(), w16b.size() * 2, hipMemcpyHostToDevice));
-        em.hi = s16b; em.lo = s16b + plane2; em.C8 = C8b; em.gamma = dg; em.beta = db;
-        em.film = d->film2 ? df : nullptr; em.film_stride = 2 * Cout; em.film_off = 0; em.frows = 2 * Cout; em.fstep = nullptr;
-        em.acc = arena; em.cnt = reinterpret_cast<unsigned*>(arena + (size_t)B * 64); em.range_ctr = e->range_ctr;
-        a11.out = nullptr; a11.stat = nullptr; a11.emit = &em;
-        c6.xhi = s16b; c6.xlo = s16b + plane2; c6.w16 = wp2; c6.w16_scale = w2_scale;
-        c6.bias = dbias2; c6.out = dout2; c6.B = B; c6.Cin = Cout; c6.Cout = Co2; c6.H = H; c6.W = W;
+        API_TRY(e, hop_stage(e, "c11", d, B, Cout, HW, false, (Cout + 63) / 64, &h));
+        a11.out = nullptr; a11.stat = nullptr; a11.emit = &h.em;
+        c6 = second_conv6(h, B, Cout, d->Cout2, H, W, false);
     }
     auto launch = [&]() -> Status {
         if (d->route != 0) return launch_conv6(e->stream, a6);
         if (!d->hop) return launch_conv11(e->stream, a11);
-        DPIR_HIP(hipMemsetAsync(arena, 0, arena_words * 8, e->stream));
+        DPIR_HIP(hipMemsetAsync(h.arena, 0, h.arena_words * 8, e->stream));
         DPIR_TRY(launch_conv11(e->stream, a11));
         return launch_conv6(e->stream, c6);
     };
     API_TRY(e, launch());
-    if (d->iters > 0) {
-        hipEvent_t e0, e1;
-        API_HIP(e, hipEventCreate(&e0)); API_HIP(e, hipEventCreate(&e1));
-        API_HIP(e, hipEventRecord(e0, e->stream));
-        for (int i = 0; i < d->iters; ++i) API_TRY(e, launch());
-        API_HIP(e, hipEventRecord(e1, e->stream));
-        API_HIP(e, hipEventSynchronize(e1));
-        float ms = 0; API_HIP(e, hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        d->ms_out = ms / d->iters;
-    }
+    API_TRY(e, time_repeats(e->stream, d->iters, launch, &d->ms_out));
     API_HIP(e, hipStreamSynchronize(e->stream));
     d->ran_out = d->route == 0 ? (d->hop ? 12 : 11) : 7;
     if (d->hop) {
-        API_HIP(e, hipMemcpy(d->out2, dout2, no2 * 4, hipMemcpyDeviceToHost));
+        API_HIP(e, hipMemcpy(d->out2, h.dout2, h.no2 * 4, hipMemcpyDeviceToHost));
         return DPIR_OK;
     }
     API_HIP(e, hipMemcpy(d->out, dout, no * 4, hipMemcpyDeviceToHost));
-    if (d->stat_out && nst) {        // epilogue slots: fp32 partial sums of 64 values, folded in fp64 (gn_prm's contract)
-        std::vector<float2> hs(nst);
-        API_HIP(e, hipMemcpy(hs.data(), st, nst * 8, hipMemcpyDeviceToHost));
-        for (size_t pl = 0; pl < (size_t)B * Cout; ++pl) {
-            double s1 = 0.0, s2 = 0.0;
-            for (int k = 0; k < slots; ++k) { s1 += (double)hs[pl * slots + k].x; s2 += (double)hs[pl * slots + k].y; }
-            d->stat_out[2 * pl] = s1; d->stat_out[2 * pl + 1] = s2;
-        }
-    }
+    if (d->stat_out && nst) API_TRY(e, fold_slots(st, (size_t)B * Cout, slots, d->stat_out));
     return DPIR_OK;
 }
 
@@ -776,7 +755,7 @@ int dpir_debug_conv_up_layer(dpir_engine* e, dpir_debug_conv_up_desc* d) {
     if (e->grad_enabled) return fail(e, Status{DPIR_ERR_UNSUPPORTED, "conv_up layer: a gradient-mode engine keeps launch_conv6's route"});
     if (e->precision == 0) return fail(e, Status{DPIR_ERR_UNSUPPORTED, "conv_up layer: the f32 precision keeps the fp32 kernel"});
     if (d->res) return fail(e, invalid("conv_up: conv1 of an up-sampling ResBlock takes no residual"));
-    const int min_wg = d->force_hop ? 0 : 384;
+    const int min_wg = d->force_hop ? 0 : kHopMinWg;
     if (d->route == 0) {
         if (const char* why = conv_up_supported(B, Cin, Cout, Hs, Ws, d->hop != 0, min_wg)) return fail(e, Status{DPIR_ERR_UNSUPPORTED, why});
     } else if (Cin % 16 || !conv6_supported(2 * Hs, 2 * Ws) || (d->hop && !conv7_emit_supported(B, Cout, 2 * Hs, 2 * Ws))) {
@@ -811,102 +790,116 @@ int dpir_debug_conv_up_layer(dpir_engine* e, dpir_debug_conv_up_desc* d) {
     API_HIP(e, hipMemcpy(wp, wv.data(), wv.size() * 2, hipMemcpyHostToDevice));
     const CatSrc src{dx, Cin, nullptr, 0};
     const float4* prm = d->prm ? dprm : nullptr;
-    // second layer and the hop's arena
-    const int Co2 = d->hop ? d->Cout2 : 0, C8b = 2 * ((Cout + 15) / 16);
-    const size_t plane2 = (size_t)B * C8b * HW * 16, no2 = (size_t)B * Co2 * HW;
-    char* s16b = nullptr; float *dg = nullptr, *db = nullptr, *df = nullptr, *dbias2 = nullptr, *dout2 = nullptr; long long* arena = nullptr; void* wp2 = nullptr;
-    const size_t arena_words = (size_t)B * 64 + ((size_t)B * ((Cout + 63) / 64) + 1) / 2;
-    Conv6Emit em;
-    float w2_scale = 1.f;
-    if (d->hop) {
-        API_TRY(e, e->ws.getT("cu#s16b", 2 * plane2, &s16b));
-        API_TRY(e, e->ws.getT("cu#gamma2", (size_t)Cout, &dg));
-        API_TRY(e, e->ws.getT("cu#beta2", (size_t)Cout, &db));
-        API_TRY(e, e->ws.getT("cu#film2", (size_t)B * 2 * Cout, &df));
-        API_TRY(e, e->ws.getT("cu#b2", (size_t)round_up(Co2, 64), &dbias2));
-        API_TRY(e, e->ws.getT("cu#o2", no2, &dout2));
-        API_TRY(e, e->ws.getT("cu#arena", arena_words, &arena));
-        API_HIP(e, hipMemsetAsync(s16b, 0xFF, 2 * plane2, e->stream));
-        API_HIP(e, hipMemcpy(dg, d->gamma2, (size_t)Cout * 4, hipMemcpyHostToDevice));
-        API_HIP(e, hipMemcpy(db, d->beta2, (size_t)Cout * 4, hipMemcpyHostToDevice));
-        if (d->film2) API_HIP(e, hipMemcpy(df, d->film2, (size_t)B * 2 * Cout * 4, hipMemcpyHostToDevice));
-        API_HIP(e, hipMemset(dbias2, 0, (size_t)round_up(Co2, 64) * 4));
-        API_HIP(e, hipMemcpy(dbias2, d->bias2, (size_t)Co2 * 4, hipMemcpyHostToDevice));
-        API_HIP(e, hipMemsetAsync(dout2, 0xFF, no2 * 4, e->stream));
-        std::vector<uint16_t> w16b;
-        w2_scale = pack_weights_conv6(d->w2, Co2, Cout, w16b);
-        API_TRY(e, e->ws.get("cu#w16b", w16b.size() * 2, &wp2));
-        API_HIP(e, hipMemcpy(wp2, w16b.data(), w16b.size() * 2, hipMemcpyHostToDevice));
-        em.hi = s16b; em.lo = x1 ? nullptr : s16b + plane2; em.C8 = C8b; em.gamma = dg; em.beta = db;
-        em.film = d->film2 ? df : nullptr; em.film_stride = 2 * Cout; em.film_off = 0; em.frows = 2 * Cout; em.fstep = nullptr;
-        em.acc = arena; em.cnt = reinterpret_cast<unsigned*>(arena + (size_t)B * 64); em.range_ctr = e->range_ctr;
-    }
-    int kernel1 = 0;
+    HopStage h;
+    if (d->hop) API_TRY(e, hop_stage(e, "cu", d, B, Cout, HW, x1, (Cout + 63) / 64, &h));
     auto once = [&]() -> Status {
-        if (d->hop) DPIR_HIP(hipMemsetAsync(arena, 0, arena_words * 8, e->stream));
+        if (d->hop) DPIR_HIP(hipMemsetAsync(h.arena, 0, h.arena_words * 8, e->stream));
         if (d->route == 0) {
             DPIR_TRY(launch_act_split(e->stream, src, prm, 0, B, Hs, Ws, s16, x1 ? nullptr : s16 + plane_s, e->range_ctr));
             ConvUpArgs a;
             a.xhi = s16; a.xlo = s16 + plane_s; a.wup = wp; a.wup_scale = w_scale; a.bias = dbias; a.out = d->hop ? nullptr : dout;
             a.B = B; a.Cin = Cin; a.Cout = Cout; a.Hs = Hs; a.Ws = Ws; a.stat = d->hop ? nullptr : st; a.x1 = x1;
-            a.emit = d->hop ? &em : nullptr; a.min_wg_hop = min_wg;
+            a.emit = d->hop ? &h.em : nullptr; a.min_wg_hop = min_wg;
             DPIR_TRY(launch_conv_up(e->stream, a));
         } else {
             DPIR_TRY(launch_act_split(e->stream, src, prm, 1, B, H, W, s16, x1 ? nullptr : s16 + plane, e->range_ctr));
             Conv6Args a6;
             a6.x1 = x1; a6.xhi = s16; a6.xlo = s16 + plane; a6.w16 = wp; a6.w16_scale = w_scale; a6.bias = dbias; a6.out = d->hop ? nullptr : dout;
             a6.B = B; a6.Cin = Cin; a6.Cout = Cout; a6.H = H; a6.W = W; a6.stat = d->hop ? nullptr : st;
-            a6.emit = d->hop ? &em : nullptr;
-            int kind = 0;
-            DPIR_TRY(launch_conv6(e->stream, a6, &kind, nullptr, &kernel1));
-            if (!d->hop && kind != 1) return invalid("conv_up layer: launch_conv6 produced no epilogue statistics here");
+            a6.emit = d->hop ? &h.em : nullptr;
+            Conv3Plan ran;
+            DPIR_TRY(launch_conv6(e->stream, a6, &ran));
+            if (!d->hop && ran.stat_kind != ST_SLOTS) return invalid("conv_up layer: launch_conv6 produced no epilogue statistics here");
         }
-        if (d->hop) {
-            Conv6Args c6;
-            c6.x1 = x1; c6.xhi = s16b; c6.xlo = s16b + plane2; c6.w16 = wp2; c6.w16_scale = w2_scale;
-            c6.bias = dbias2; c6.out = dout2; c6.B = B; c6.Cin = Cout; c6.Cout = Co2; c6.H = H; c6.W = W;
-            DPIR_TRY(launch_conv6(e->stream, c6));
-        }
+        if (d->hop) DPIR_TRY(launch_conv6(e->stream, second_conv6(h, B, Cout, d->Cout2, H, W, x1)));
         return Status{};
     };
     API_TRY(e, once());
-    if (d->iters > 0) {       // the whole route again, back to back, averaged
-        hipEvent_t e0, e1;
-        API_HIP(e, hipEventCreate(&e0)); API_HIP(e, hipEventCreate(&e1));
-        API_HIP(e, hipEventRecord(e0, e->stream));
-        for (int i = 0; i < d->iters; ++i) API_TRY(e, once());
-        API_HIP(e, hipEventRecord(e1, e->stream));
-        API_HIP(e, hipEventSynchronize(e1));
-        float ms = 0; API_HIP(e, hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        d->ms_out = ms / d->iters;
-    }
+    API_TRY(e, time_repeats(e->stream, d->iters, once, &d->ms_out));       // the whole route again, back to back, averaged
     API_HIP(e, hipStreamSynchronize(e->stream));
     d->ran_out = d->route == 0 ? (d->hop ? 2 : 1) : 7;
     if (d->hop) {
-        API_HIP(e, hipMemcpy(d->out2, dout2, no2 * 4, hipMemcpyDeviceToHost));
+        API_HIP(e, hipMemcpy(d->out2, h.dout2, h.no2 * 4, hipMemcpyDeviceToHost));
         return DPIR_OK;
     }
     API_HIP(e, hipMemcpy(d->out, dout, no * 4, hipMemcpyDeviceToHost));
-    if (d->stat_out) {          // epilogue slots: fp32 partial sums of 64 values, folded in fp64 (gn_prm's contract)
-        std::vector<float2> hs(nst);
-        API_HIP(e, hipMemcpy(hs.data(), st, nst * 8, hipMemcpyDeviceToHost));
-        for (size_t pl = 0; pl < (size_t)B * Cout; ++pl) {
-            double s1 = 0.0, s2 = 0.0;
-            for (int k = 0; k < slots; ++k) { s1 += (double)hs[pl * slots + k].x; s2 += (double)hs[pl * slots + k].y; }
-            d->stat_out[2 * pl] = s1; d->stat_out[2 * pl + 1] = s2;
-        }
+    if (d->stat_out) API_TRY(e, fold_slots(st, (size_t)B * Cout, slots, d->stat_out));
+    return DPIR_OK;
+}
+
+// The convolution launches of the engine's last forward with taps on (engine.h RouteRec): up to `cap` records into `recs`, the number there
+// are into *n_out.
+int dpir_debug_route_log(dpir_engine* e, dpir_debug_route_rec* recs, int cap, int* n_out) {
+    if (!e || !n_out || (cap > 0 && !recs)) return DPIR_ERR_INVALID;
+    *n_out = (int)e->route_log.size();
+    for (int i = 0; i < *n_out && i < cap; ++i) {
+        const RouteRec& r = e->route_log[i];
+        snprintf(recs[i].layer, sizeof recs[i].layer, "%s", r.layer.c_str());
+        recs[i].kernel = r.kernel; recs[i].ks = r.ks; recs[i].ksplit = r.ksplit; recs[i].hop = r.hop; recs[i].stat_kind = r.stat_kind;
+        recs[i].workgroups = r.workgroups;
     }
     return DPIR_OK;
 }
 
-void dpir_debug_conv_up_counts(long long* plain, long long* hop) { conv_up_launch_counts(plain, hop); }
-void dpir_debug_conv11_counts(long long* plain, long long* hop) { conv11_launch_counts(plain, hop); }
+// The planner (csrc/conv_plan.h) without an engine or a GPU: capacities are arguments, knobs == null means the built-in defaults (not the
+// environment).
+static ConvKnobs knobs_of(const dpir_debug_conv_knobs* k) {
+    ConvKnobs o;
+    if (!k) return o;
+    o.conv8 = k->conv8 != 0; o.conv9 = k->conv9 != 0; o.conv9_min_wg = k->conv9_min_wg; o.conv11 = k->conv11 != 0; o.conv_up = k->conv_up != 0;
+    o.split_below = k->split_below; o.split_target = k->split_target; o.fuse_small = k->fuse_small != 0; o.fuse_h1 = k->fuse_h1 != 0;
+    o.emit_skip = k->emit_skip;
+    return o;
+}
+static dpir_debug_conv_plan plan_out(const Conv3Plan& p) {
+    dpir_debug_conv_plan o;
+    o.kernel = p.kernel; o.hop = p.hop; o.geo = p.geo; o.ksplit = p.ksplit; o.chunks_per_split = p.chunks_per_split;
+    o.stat_kind = p.stat_kind; o.stat_slots = p.stat_slots; o.refused = p.refusal != nullptr; o.workgroups = p.workgroups;
+    return o;
+}
+void dpir_debug_conv_knobs_default(dpir_debug_conv_knobs* k) {
+    const ConvKnobs d;
+    *k = dpir_debug_conv_knobs{d.conv8, d.conv9, d.conv9_min_wg, d.conv11, d.conv_up, d.split_below, d.split_target, d.fuse_small, d.fuse_h1, d.emit_skip};
+}
+int dpir_debug_conv3_plan(const dpir_debug_conv3_query* qs, int n, const dpir_debug_conv_knobs* knobs, int cap7, int cap11, int cap_up, dpir_debug_conv_plan* out) {
+    if (!qs || !out || n < 0) return DPIR_ERR_INVALID;
+    const ConvKnobs k = knobs_of(knobs);
+    const DeviceCaps caps{cap7, cap11, cap_up};
+    for (int i = 0; i < n; ++i) {
+        const dpir_debug_conv3_query& d = qs[i];
+        Conv3Query q;
+        q.B = d.B; q.Cin = d.Cin; q.Cout = d.Cout; q.H = d.H; q.W = d.W; q.precision = d.precision; q.grad = d.grad != 0;
+        q.w16 = d.w16 != 0; q.w8 = d.w8 != 0; q.w11 = d.w11 != 0; q.conv8_source = d.conv8_source != 0;
+        q.slab = d.slab_floats > 0; q.slab_floats = (size_t)d.slab_floats; q.defer = d.defer != 0; q.hop = d.hop != 0; q.has_res = d.has_res != 0;
+        q.stat_slots = q.stat_plane = d.stats != 0; q.force_kernel = d.force_kernel;
+        out[i] = plan_out(plan_conv3(q, k, caps));
+    }
+    return DPIR_OK;
+}
+int dpir_debug_resblock_plan(const dpir_debug_resblock_query* d, const dpir_debug_conv_knobs* knobs, int cap7, int cap11, int cap_up, dpir_debug_resblock_plan_out* out) {
+    if (!d || !out) return DPIR_ERR_INVALID;
+    ResblockQuery q;
+    q.B = d->B; q.Cin = d->Cin; q.Cout = d->Cout; q.H = d->H; q.W = d->W; q.mode = d->mode; q.concat = d->concat != 0; q.has_skip = d->Cin != d->Cout;
+    q.gn1_c = d->Cin; q.gn2_c = d->Cout; q.precision = d->precision; q.grad = d->grad != 0;
+    q.hop_allowed = d->hop_allowed != 0; q.arena_words_left = (size_t)d->arena_words_left;
+    // the packs load_conv (unet.hip) makes for this precision and mode
+    const bool f16 = d->precision != 0;
+    q.conv1_w16 = q.conv2_w16 = f16; q.skip_w16 = f16 && q.has_skip;
+    q.conv1_w11 = d->precision == 1 && conv11_supported(d->Cin, d->Cout, 8, 32); q.conv2_w11 = d->precision == 1 && conv11_supported(d->Cout, d->Cout, 8, 32);
+    q.conv1_wup = f16 && d->mode == 1 && d->Cin % 16 == 0 && d->Cout % 32 == 0;
+    const int Ho = d->mode == 1 ? d->H * 2 : (d->mode == 2 ? d->H / 2 : d->H), Wo = d->mode == 1 ? d->W * 2 : (d->mode == 2 ? d->W / 2 : d->W);
+    q.small_prologue = gn_act_small_supported(d->Cin, d->H, d->W, 0); q.conv5_ok = conv5_supported(d->B, d->Cout, Ho, Wo);
+    q.slab = d->slab_floats > 0; q.slab_floats = (size_t)d->slab_floats;
+    const ResblockPlan rp = plan_resblock(q, knobs_of(knobs), DeviceCaps{cap7, cap11, cap_up});
+    out->up = rp.up; out->skip_emit = rp.skip_emit; out->hop = rp.hop; out->arena_counters = rp.arena_counters;
+    out->conv1 = plan_out(rp.conv1); out->conv2 = plan_out(rp.conv2);
+    return DPIR_OK;
+}
 
 int dpir_debug_conv7_emit_supported(dpir_engine* e, int B, int Cout, int H, int W, int* capacity_out) {
     if (!e) return 0;
     (void)hipSetDevice(e->device);
-    if (capacity_out) *capacity_out = conv7_emit_capacity();
+    if (capacity_out) *capacity_out = device_caps().conv7;
     return conv7_emit_supported(B, Cout, H, W) ? 1 : 0;
 }
 

@@ -64,6 +64,10 @@ struct UNet {
 };
 
 struct TapInfo { const float* p; size_t numel; };
+// One convolution launch of the last forward, recorded while taps are collected (dpir_debug_route_log reads it back): ConvKernel, HopKind and
+// StatKind of conv_plan.h.  A split-K launch is ST_PENDING until Fwd::resolve finishes it (then ST_PLANE / ST_NONE, followed by a CK_RESOLVE
+// record); the ones still pending at the end were combined by the next layer's fused prologue.
+struct RouteRec { std::string layer; int kernel, ks, ksplit, hop, stat_kind; long long workgroups; };
 
 // What the last forward left behind for the input-gradient pass (grad mode only; unet_bwd.hip walks it in reverse)
 struct TapeRes { int idx; CatSrc in; int inH, inW, Ho, Wo; float* h1; float* sk; float* out; float4* prm1; float2* st1; float4* prm2; float2* st2; };
@@ -93,6 +97,7 @@ struct dpir_engine {
     dpir::UNet net;
     dpir::Workspace ws;          // UNet activations + loop state
     std::map<std::string, dpir::TapInfo> taps;
+    std::vector<dpir::RouteRec> route_log;
     dpir::ProxCache prox_cache;                  // twiddle tables and slot maps of the FFT prox (prox.hip)
     std::map<std::pair<int, int>, dpir::ResizerTab> resizers;   // (in_len, sf)
     std::vector<void*> user_allocs;

@@ -66,6 +66,14 @@ Status upload(dpir_engine* e, const float* host, size_t n, float** dev) {
     *dev = reinterpret_cast<float*>(p);
     return Status{};
 }
+Status upload16(dpir_engine* e, const std::vector<uint16_t>& pack, const char* what, void** dev) {
+    void* p = nullptr;
+    if (hipMalloc(&p, pack.size() * 2) != hipSuccess) return Status{DPIR_ERR_NOMEM, std::string("hipMalloc for ") + what + " failed"};
+    e->net.allocs.push_back(p);
+    DPIR_HIP(hipMemcpy(p, pack.data(), pack.size() * 2, hipMemcpyHostToDevice));
+    *dev = p;
+    return Status{};
+}
 
 // OIHW (or OI1 for conv1d) -> [CinP][taps][CoutP], zero padded: CinP % 16 == 0, CoutP % 64 == 0 (conv2.hip's LDS-DMA
 // copies whole K chunks and 64-channel column blocks without bounds checks)
@@ -105,49 +113,29 @@ Status load_conv(dpir_engine* e, const WeightMap& wm, const std::string& p, int 
                         wt[((size_t)ci * cout + co) * taps + t] = w[((size_t)co * cin + ci) * taps + (taps - 1 - t)];
             std::vector<uint16_t> w16t;
             out->w16T_scale = ks == 3 ? pack_weights_conv6(wt.data(), cin, cout, w16t) : pack_weights_f16x3_1x1(wt.data(), cin, cout, w16t);
-            void* pp = nullptr;
-            if (hipMalloc(&pp, w16t.size() * 2) != hipSuccess) return Status{DPIR_ERR_NOMEM, "hipMalloc for the split dgrad weights failed"};
-            e->net.allocs.push_back(pp);
-            DPIR_HIP(hipMemcpy(pp, w16t.data(), w16t.size() * 2, hipMemcpyHostToDevice));
-            out->w16T = pp;
+            DPIR_TRY(upload16(e, w16t, "the split dgrad weights", &out->w16T));
         }
     }
     if (e->precision >= 1 && (ks == 3 || ks == 1)) {
         std::vector<uint16_t> w16;
         out->w16_scale = ks == 3 ? pack_weights_conv6(w, cout, cin, w16) : pack_weights_f16x3_1x1(w, cout, cin, w16);
-        void* p = nullptr;
-        if (hipMalloc(&p, w16.size() * 2) != hipSuccess) return Status{DPIR_ERR_NOMEM, "hipMalloc for split weights failed"};
-        e->net.allocs.push_back(p);
-        DPIR_HIP(hipMemcpy(p, w16.data(), w16.size() * 2, hipMemcpyHostToDevice));
-        out->w16 = p;
+        DPIR_TRY(upload16(e, w16, "split weights", &out->w16));
         if (ks == 3 && !one_d && cout <= 16 && cin % 32 == 0) {
             std::vector<uint16_t> w8;
             out->w8_scale = pack_weights_conv8(w, cout, cin, w8);
-            void* p8 = nullptr;
-            if (hipMalloc(&p8, w8.size() * 2) != hipSuccess) return Status{DPIR_ERR_NOMEM, "hipMalloc for the conv8 weights failed"};
-            e->net.allocs.push_back(p8);
-            DPIR_HIP(hipMemcpy(p8, w8.data(), w8.size() * 2, hipMemcpyHostToDevice));
-            out->w8 = p8;
+            DPIR_TRY(upload16(e, w8, "the conv8 weights", &out->w8));
         }
         if (e->precision == 1 && ks == 3 && !one_d && conv11_supported(cin, cout, 8, 32)) {
             // the same f16 halves in the lane order of the 16x16x32 MFMA (conv11.hip), besides the conv6 pack (split-K launches, small shapes, gradient mode)
             std::vector<uint16_t> w11;
             pack_weights_conv11(w, cout, cin, out->w16_scale, w11);
-            void* p11 = nullptr;
-            if (hipMalloc(&p11, w11.size() * 2) != hipSuccess) return Status{DPIR_ERR_NOMEM, "hipMalloc for the conv11 weights failed"};
-            e->net.allocs.push_back(p11);
-            DPIR_HIP(hipMemcpy(p11, w11.data(), w11.size() * 2, hipMemcpyHostToDevice));
-            out->w11 = p11;
+            DPIR_TRY(upload16(e, w11, "the conv11 weights", &out->w11));
         }
         if (up_pack && ks == 3 && !one_d && cin % 16 == 0 && cout % 32 == 0) {
             // conv1 behind a nearest-x2 up-sampling: the four 2x2 phase filters (conv_up.hip), besides the 3x3 pack (gradient mode, small shapes)
             std::vector<uint16_t> wu;
             out->wup_scale = pack_weights_conv_up(w, cout, cin, wu);
-            void* pu = nullptr;
-            if (hipMalloc(&pu, wu.size() * 2) != hipSuccess) return Status{DPIR_ERR_NOMEM, "hipMalloc for the phase weights failed"};
-            e->net.allocs.push_back(pu);
-            DPIR_HIP(hipMemcpy(pu, wu.data(), wu.size() * 2, hipMemcpyHostToDevice));
-            out->wup = pu;
+            DPIR_TRY(upload16(e, wu, "the phase weights", &out->wup));
         }
     }
     return Status{};
@@ -336,6 +324,10 @@ struct Fwd {
     const StepDev* fstep;  // device-resident current step (row selector of the hoisted table) or null
     float* partial;        // split-K slab shared by all convolutions of the forward
     size_t partial_cap;
+    // Which kernel a 3x3 layer runs on and which hop a ResBlock takes is the planner's decision (conv_plan.h): Fwd describes the layer and
+    // the engine's state, and executes the plan.
+    const ConvKnobs& knobs = ConvKnobs::from_env();
+    DeviceCaps caps;
     // GroupNorm statistics already produced by the epilogue of the convolution that wrote a tensor (keyed by its address)
     struct FusedStat { const float2* slots; int nslots; const double2* part; };   // epilogue slots, or per-plane fp64 records (split-K combine)
     std::unordered_map<const float*, FusedStat> fused;
@@ -344,10 +336,16 @@ struct Fwd {
     // reuses the slab buffer.
     PendingConv pending;
     bool grad = false;    // grad mode: GroupNorm tables kept (also by the fused prologues), tape recorded
-    bool fuse_small;
-    int emit_skip;        // conv5 emits conv1's operand planes in ResBlocks with a 1x1 skip projection: 0 never, 1 when the projection has
-                          // ONE 128-channel output block (each input row is then read exactly once; with two blocks only one of them emits and
-                          // the other re-reads -- measured slower on the ImageNet-256 topology, profiles/r03), 2 always
+    bool x1() const { return e->precision == 2; }      // f16x1: single-product mode, hi halves only
+
+    // route log (engine.h RouteRec): the layer the next launches belong to, and the record of the pending convolution
+    std::string layer;
+    int pending_rec = -1;
+    void log(int kernel, int ks, const Conv3Plan& p, int hop) {
+        if (!e->collect_taps) return;
+        if (p.stat_kind == ST_PENDING) pending_rec = (int)e->route_log.size();
+        e->route_log.push_back(RouteRec{layer, kernel, ks, p.ksplit, hop, p.stat_kind, p.workgroups});
+    }
 
     Status resolve() {
         if (!pending.partial) return Status{};
@@ -355,47 +353,69 @@ struct Fwd {
         DPIR_TRY(launch_conv6_resolve(s, pending));
         if (pending.stat_plane) fused[pending.out] = FusedStat{nullptr, 0, pending.stat_plane};
         else fused.erase(pending.out);
-        pending = PendingConv{};
+        if (e->collect_taps && pending_rec >= 0) {
+            RouteRec r = e->route_log[pending_rec];
+            e->route_log[pending_rec].stat_kind = pending.stat_plane ? ST_PLANE : ST_NONE;
+            r.kernel = CK_RESOLVE; r.hop = HOP_NONE; r.stat_kind = e->route_log[pending_rec].stat_kind; r.workgroups = ((long long)pending.B * pending.Cout + 3) / 4;
+            e->route_log.push_back(r);
+        }
+        pending = PendingConv{}; pending_rec = -1;
         return Status{};
     }
     bool is_pending(const float* p) const { return pending.partial && p && p == pending.out; }
 
-    // GroupNorm (+FiLM) + SiLU + 3x3 convolution.  Low-resolution layers on the f16 path take the fused prologue; everything
+    Conv3Query query(const ConvW& cw, int Cin, int Ho, int Wo, bool hop, bool has_res) const {
+        Conv3Query q;
+        q.B = B; q.Cin = Cin; q.Cout = cw.cout; q.H = Ho; q.W = Wo; q.precision = e->precision; q.grad = grad;
+        q.w16 = cw.ks == 3 && cw.w16; q.w8 = cw.ks == 3 && cw.w8; q.w11 = cw.ks == 3 && cw.w11;
+        q.hop = hop; q.has_res = has_res;
+        q.slab = !hop; q.slab_floats = hop ? 0 : partial_cap; q.defer = knobs.fuse_small;      // a hop runs whole K or not at all
+        return q;
+    }
+
+    // The fused low-resolution prologue (gn_act_small): [combine of the pending split-K convolution +] GroupNorm statistics + affine / FiLM fold +
+    // SiLU + resample + f16 split of `in` into the planes s16
+    Status small_prologue(const GnW& g, const std::string& tag, int film_off, const Act& in, int mode, const float* res, char* s16, size_t plane,
+                          float4** prm_out = nullptr, float2** stats_out = nullptr) {
+        if (pending.partial && !is_pending(in.a)) DPIR_TRY(resolve());
+        if (is_pending(res)) return invalid("gn_conv: residual is an unfinished convolution");
+        GnActArgs ga;
+        ga.src = CatSrc{in.a, in.ca, in.b, in.cb};
+        ga.pend = pending;
+        ga.gamma = g.gamma; ga.beta = g.beta;
+        ga.film = film_off >= 0 ? film : nullptr; ga.film_stride = film_stride; ga.film_off = film_off < 0 ? 0 : film_off;
+        ga.fstep = fstep; ga.frows = film_rows;
+        ga.silu = true; ga.mode = mode; ga.B = B; ga.Hs = in.H; ga.Ws = in.W;
+        ga.hi = s16; ga.lo = x1() ? nullptr : s16 + plane; ga.range_ctr = e->range_ctr;
+        if (grad) {     // the backward pass reads the same tables gn_prm_kernel would have written
+            DPIR_TRY(ws.getT(tag + "#prm", (size_t)B * in.C(), &ga.prm_out));
+            DPIR_TRY(ws.getT(tag + "#gst", (size_t)B * 32, &ga.stats_out));
+            if (prm_out) *prm_out = ga.prm_out;
+            if (stats_out) *stats_out = ga.stats_out;
+        }
+        {
+            ProfScope ps(&e->prof, PC_ELEM);
+            DPIR_TRY(launch_gn_act_small(s, ga));
+        }
+        if (pending.partial) { fused.erase(pending.out); pending = PendingConv{}; pending_rec = -1; }   // finished (and stored) by the fused prologue
+        return Status{};
+    }
+
+    // GroupNorm (+FiLM) + SiLU + 3x3 convolution.  Low-resolution layers on the f16 kernels take the fused prologue; everything
     // else the separate statistics / gn_prm / act_split (or fp32 in-kernel prologue) route.
     Status gn_conv(const GnW& g, const std::string& tag, int film_off, const ConvW& cw, const Act& in, int mode,
                    const float* res, int res_mode, float* out, int Ho, int Wo, float4** prm_out = nullptr, float2** stats_out = nullptr,
                    const Conv6Emit* emit = nullptr) {
         const int C = in.C();
-        const bool f16path = cw.w16 && cw.ks == 3 && conv6_supported(Ho, Wo);
-        if (fuse_small && f16path && C == g.c && C % 16 == 0 && gn_act_small_supported(C, in.H, in.W, mode)) {
-            const bool x1 = e->precision == 2;
+        const bool planes = cw.ks == 3 && plan_conv3(query(cw, C, Ho, Wo, emit != nullptr, res != nullptr), knobs, caps).kernel != CK_FP32;
+        if (knobs.fuse_small && planes && C == g.c && C % 16 == 0 && gn_act_small_supported(C, in.H, in.W, mode)) {
             int eh = mode == 1 ? Ho / 2 : (mode == 2 ? Ho * 2 : Ho), ew = mode == 1 ? Wo / 2 : (mode == 2 ? Wo * 2 : Wo);
             if (eh != in.H || ew != in.W) return invalid("conv: source resolution does not match mode");
-            if (pending.partial && !is_pending(in.a)) DPIR_TRY(resolve());
-            if (is_pending(res)) return invalid("gn_conv: residual is an unfinished convolution");
             const int C8 = 2 * ((C + 15) / 16);
             const size_t plane = (size_t)B * C8 * Ho * Wo * 16;
             char* s16 = nullptr;
             DPIR_TRY(ws.getT("act#s16", 2 * plane, &s16));
-            GnActArgs ga;
-            ga.src = CatSrc{in.a, in.ca, in.b, in.cb};
-            ga.pend = pending;
-            ga.gamma = g.gamma; ga.beta = g.beta;
-            ga.film = film_off >= 0 ? film : nullptr; ga.film_stride = film_stride; ga.film_off = film_off < 0 ? 0 : film_off;
-            ga.fstep = fstep; ga.frows = film_rows;
-            ga.silu = true; ga.mode = mode; ga.B = B; ga.Hs = in.H; ga.Ws = in.W;
-            ga.hi = s16; ga.lo = x1 ? nullptr : s16 + plane; ga.range_ctr = e->range_ctr;
-            if (grad) {     // the backward pass reads the same tables gn_prm_kernel would have written
-                DPIR_TRY(ws.getT(tag + "#prm", (size_t)B * C, &ga.prm_out));
-                DPIR_TRY(ws.getT(tag + "#gst", (size_t)B * 32, &ga.stats_out));
-                if (prm_out) *prm_out = ga.prm_out;
-                if (stats_out) *stats_out = ga.stats_out;
-            }
-            {
-                ProfScope ps(&e->prof, PC_ELEM);
-                DPIR_TRY(launch_gn_act_small(s, ga));
-            }
-            if (pending.partial) { fused.erase(pending.out); pending = PendingConv{}; }   // finished (and stored) by the fused prologue
+            DPIR_TRY(small_prologue(g, tag, film_off, in, mode, res, s16, plane, prm_out, stats_out));
             return conv6_on_planes(cw, s16, plane, res, res_mode, out, Ho, Wo, emit);
         }
         DPIR_TRY(resolve());
@@ -405,105 +425,82 @@ struct Fwd {
         return conv(cw, in, mode, prm, res, res_mode, out, Ho, Wo, emit);
     }
 
-    // conv9 (csrc/conv9.hip) takes a 3x3 layer when the shape fits its whole-image tile, the forward is not recording a tape, the
-    // precision is one of the f16 modes and the launch has enough workgroups (B x Cout / 32) to fill the device: below the threshold the
-    // split-K route of launch_conv6, tuned for small batches, stays.  DPIR_CONV9=0 restores launch_conv6's dispatch everywhere,
-    // DPIR_CONV9_MIN_WG overrides the threshold (profiles/conv9/README.md has the per-layer table it comes from).
-    bool conv9_route(const ConvW& cw, int Ho, int Wo, bool hop) const {
-        static const bool on = !(getenv("DPIR_CONV9") && atoi(getenv("DPIR_CONV9")) == 0);
-        static const int min_wg = getenv("DPIR_CONV9_MIN_WG") ? atoi(getenv("DPIR_CONV9_MIN_WG")) : kConv9MinWg;
-        return on && !grad && e->precision != 0 && cw.w16 && cw.ks == 3 && conv9_supported(B, cw.cin, cw.cout, Ho, Wo, hop) &&
-               (long long)B * (cw.cout / 32) >= min_wg;
-    }
-
-    // conv11 (csrc/conv11.hip: conv7's 8 x 32 tile with the 16x16x32 MFMA, x0.93 of conv7's time per layer, profiles/conv11/README.md) takes a 3x3
-    // layer of the f16x3 precision when its pack is loaded, the forward records no tape, the tiles lie inside the image and launch_conv6
-    // would have run the launch whole-K (its rule: 256 workgroups; the hop: conv7_emit_supported's 384, checked by h1_fusable) -- and, for
-    // the hop, when an image's tiles fit into half of conv11's own resident workgroups.  DPIR_CONV11=0 restores launch_conv6's dispatch.
-    bool conv11_route(const ConvW& cw, int Ho, int Wo, bool hop) const {
-        static const bool on = !(getenv("DPIR_CONV11") && atoi(getenv("DPIR_CONV11")) == 0);
-        static const int split_below = getenv("DPIR_SPLIT_BELOW") ? atoi(getenv("DPIR_SPLIT_BELOW")) : 256;
-        if (!on || grad || e->precision != 1 || !cw.w11 || cw.ks != 3 || !conv11_supported(cw.cin, cw.cout, Ho, Wo)) return false;
-        const long long wgs = (long long)(Wo / 32) * (Ho / 8) * B * (cw.cout / 128);
-        return hop ? wgs >= 384 && conv11_emit_supported(cw.cout, Ho, Wo) : wgs >= split_below;
-    }
-
+    // One 3x3 layer of the f16 precisions on prepared operand planes: conv9, conv11 or launch_conv6 (conv6 / conv7), as planned
     Status conv6_on_planes(const ConvW& cw, char* s16, size_t plane, const float* res, int res_mode, float* out, int Ho, int Wo,
                            const Conv6Emit* emit = nullptr) {
-        const bool x1 = e->precision == 2;
-        Conv6Args a6;
-        a6.x1 = x1;
-        a6.xhi = s16; a6.xlo = s16 + plane; a6.w16 = cw.w16; a6.w16_scale = cw.w16_scale;
-        a6.bias = cw.bias; a6.out = out; a6.res = res; a6.res_mode = res_mode;
-        a6.B = B; a6.Cin = cw.cin; a6.Cout = cw.cout; a6.H = Ho; a6.W = Wo;
-        a6.partial = partial; a6.partial_capacity = partial_cap;
-        const int slots = conv6_stat_slots(Ho, Wo);
+        const int slots = geometry(Ho, Wo).stat_slots;
         float2* st = nullptr; double2* sp = nullptr;
         if (slots > 0 && cw.cout % 32 == 0) {
             const std::string key = std::to_string(reinterpret_cast<uintptr_t>(out));
             DPIR_TRY(ws.getT("st#" + key, (size_t)B * cw.cout * slots, &st));
             DPIR_TRY(ws.getT("sp#" + key, (size_t)B * cw.cout, &sp));
         }
-        a6.stat = st; a6.stat_plane = sp;
-        a6.emit = emit;
-        if (emit) { a6.stat = nullptr; a6.stat_plane = nullptr; a6.partial = nullptr; a6.partial_capacity = 0; }
-        int kind = 0;
-        PendingConv pc;
+        if (emit) { st = nullptr; sp = nullptr; }
+        Conv3Query q = query(cw, cw.cin, Ho, Wo, emit != nullptr, res != nullptr);
+        q.w8 = false;       // the planes exist already
+        q.stat_slots = st != nullptr; q.stat_plane = sp != nullptr;
+        Conv3Plan p = plan_conv3(q, knobs, caps);
+        if (p.refusal) return invalid(p.refusal);
         ProfScope ps(&e->prof, PC_CONV3);
-        // 8 x 8: one workgroup per (image, 32 output channels), whole K -- no slabs, nothing pending.  A hop (emit) reaches this shape only
-        // from resblock's conv9 branch: conv7's own emission needs the 8 x 32 geometry.
-        if (conv9_route(cw, Ho, Wo, emit != nullptr)) {
+        if (p.kernel == CK_CONV9) {
             Conv9Args a9;
             a9.xhi = s16; a9.xlo = s16 + plane; a9.w16 = cw.w16; a9.w16_scale = cw.w16_scale; a9.bias = cw.bias; a9.out = out;
             a9.res = res; a9.res_mode = res_mode; a9.B = B; a9.Cin = cw.cin; a9.Cout = cw.cout; a9.H = Ho; a9.W = Wo;
-            a9.stat_plane = emit ? nullptr : sp; a9.x1 = x1; a9.emit = emit;
+            a9.stat_plane = sp; a9.x1 = x1(); a9.emit = emit;
             DPIR_TRY(launch_conv9(s, a9));
-            if (sp && !emit) fused[out] = FusedStat{nullptr, 0, sp};
-            else fused.erase(out);
-            return Status{};
-        }
-        if (conv11_route(cw, Ho, Wo, emit != nullptr)) {
+        } else if (p.kernel == CK_CONV11) {
             Conv11Args a11;
             a11.xhi = s16; a11.xlo = s16 + plane; a11.w11 = cw.w11; a11.w_scale = cw.w16_scale; a11.bias = cw.bias; a11.out = out;
             a11.res = res; a11.res_mode = res_mode; a11.B = B; a11.Cin = cw.cin; a11.Cout = cw.cout; a11.H = Ho; a11.W = Wo;
-            a11.stat = emit ? nullptr : st; a11.precision = e->precision; a11.grad = grad; a11.emit = emit;
+            a11.stat = st; a11.precision = e->precision; a11.grad = grad; a11.emit = emit;
             DPIR_TRY(launch_conv11(s, a11));
-            if (st && !emit) fused[out] = FusedStat{st, slots, nullptr};
-            else fused.erase(out);
-            return Status{};
+        } else {
+            Conv6Args a6;
+            a6.x1 = x1();
+            a6.xhi = s16; a6.xlo = s16 + plane; a6.w16 = cw.w16; a6.w16_scale = cw.w16_scale;
+            a6.bias = cw.bias; a6.out = out; a6.res = res; a6.res_mode = res_mode;
+            a6.B = B; a6.Cin = cw.cin; a6.Cout = cw.cout; a6.H = Ho; a6.W = Wo;
+            if (q.slab) { a6.partial = partial; a6.partial_capacity = partial_cap; }
+            a6.stat = st; a6.stat_plane = sp; a6.emit = emit;
+            PendingConv pc;
+            DPIR_TRY(launch_conv6(s, a6, &p, q.defer ? &pc : nullptr));
+            if (p.stat_kind == ST_PENDING) pending = pc;
         }
-        DPIR_TRY(launch_conv6(s, a6, &kind, fuse_small ? &pc : nullptr));
-        if (kind == 1) fused[out] = FusedStat{st, slots, nullptr};
-        else if (kind == 2) fused[out] = FusedStat{nullptr, 0, sp};
+        if (p.stat_kind == ST_SLOTS) fused[out] = FusedStat{st, p.stat_slots, nullptr};
+        else if (p.stat_kind == ST_PLANE) fused[out] = FusedStat{nullptr, 0, sp};
         else fused.erase(out);
-        if (kind == 3) pending = pc;
+        log(p.kernel, 3, p, !p.hop ? HOP_NONE : (p.kernel == CK_CONV9 ? HOP_CONV9 : HOP_ARENA));
         return Status{};
     }
 
     Status conv(const ConvW& cw, const Act& in, int mode, const float4* prm, const float* res, int res_mode, float* out, int Ho, int Wo,
                 const Conv6Emit* emit = nullptr) {
-        const bool x1 = e->precision == 2;        // f16x1: single-product mode, hi halves only
         // an unfinished split-K output is finished before anything but the fused prologue reads it (or reuses the slab buffer)
         const bool use5 = cw.w16 && cw.ks == 1 && mode == 0 && (!res || res_mode == 0) && !(prm && in.C() % 16) &&
                           (conv5_supported(B, cw.cout, Ho, Wo, prm != nullptr) ||
                            conv5_small_supported(B, in.ca, in.b ? in.cb : 0, cw.cout, Ho, Wo, prm != nullptr));   // no slab buffer
         if (pending.partial && (is_pending(in.a) || is_pending(in.b) || is_pending(res) || !use5)) DPIR_TRY(resolve());
-        // the output layer (128 -> 6): GroupNorm / SiLU / split happen in the convolution's own LDS fill (conv8.hip); grad mode keeps the
-        // planes route (the backward pass reads act#s16)
-        static const bool use_conv8 = !(getenv("DPIR_CONV8") && atoi(getenv("DPIR_CONV8")) == 0);
-        if (use_conv8 && cw.w8 && prm && !grad && !emit && !res && mode == 0 && !in.b && in.H == Ho && in.W == Wo &&
-            conv8_supported(B, in.C(), cw.cout, Ho, Wo)) {
+        Conv3Plan p;        // CK_FP32 unless the planner says otherwise
+        if (cw.ks == 3) {
+            Conv3Query q = query(cw, in.C(), Ho, Wo, emit != nullptr, res != nullptr);
+            q.conv8_source = prm && mode == 0 && !in.b && in.H == Ho && in.W == Wo;
+            p = plan_conv3(q, knobs, caps);
+            if (p.refusal) return invalid(p.refusal);
+        } else if (emit) {
+            return invalid("conv: fused emission was requested for a launch that is not on the f16 3x3 path");
+        }
+        if (p.kernel == CK_CONV8) {
             Conv8Args a8;
             a8.x = in.a; a8.prm = prm; a8.w = cw.w8; a8.w_scale = cw.w8_scale; a8.bias = cw.bias; a8.out = out;
-            a8.B = B; a8.C = in.C(); a8.Cout = cw.cout; a8.H = Ho; a8.W = Wo; a8.range_ctr = e->range_ctr; a8.x1 = x1;
+            a8.B = B; a8.C = in.C(); a8.Cout = cw.cout; a8.H = Ho; a8.W = Wo; a8.range_ctr = e->range_ctr; a8.x1 = x1();
             fused.erase(out);
+            log(CK_CONV8, 3, p, HOP_NONE);
             ProfScope ps(&e->prof, PC_CONV3);
             return launch_conv8(s, a8);
         }
-        if (cw.w16 && cw.ks == 3 && conv6_supported(Ho, Wo)) {
-            // operand-split f16 path: one elementwise pre-pass (GroupNorm/FiLM/SiLU/resample/concat/split),
-            // then conv6 (pure LDS-DMA + MFMA, two workgroups per CU); GroupNorm statistics of the output come out of its
-            // epilogue or of its split-K combine
+        if (p.kernel != CK_FP32) {
+            // operand-split f16 path: one elementwise pre-pass (GroupNorm/FiLM/SiLU/resample/concat/split), then the planned kernel (pure
+            // LDS-DMA + MFMA); GroupNorm statistics of the output come out of its epilogue or of its split-K combine
             int eh = mode == 1 ? Ho / 2 : (mode == 2 ? Ho * 2 : Ho), ew = mode == 1 ? Wo / 2 : (mode == 2 ? Wo * 2 : Wo);
             if (eh != in.H || ew != in.W) return invalid("conv: source resolution does not match mode");
             const int C = in.C(), C8 = 2 * ((C + 15) / 16);
@@ -513,21 +510,20 @@ struct Fwd {
             DPIR_TRY(ws.getT("act#s16", 2 * plane, &s16));
             {
                 ProfScope ps(&e->prof, PC_ELEM);
-                DPIR_TRY(launch_act_split(s, CatSrc{in.a, in.ca, in.b, in.cb}, prm, mode, B, Ho, Wo, s16, x1 ? nullptr : s16 + plane, e->range_ctr));
+                DPIR_TRY(launch_act_split(s, CatSrc{in.a, in.ca, in.b, in.cb}, prm, mode, B, Ho, Wo, s16, x1() ? nullptr : s16 + plane, e->range_ctr));
             }
             return conv6_on_planes(cw, s16, plane, res, res_mode, out, Ho, Wo, emit);
         }
-        if (emit) return invalid("conv: fused emission was requested for a launch that is not on the f16 3x3 path");
+        fused.erase(out);
+        log(use5 ? CK_CONV5 : CK_FP32, cw.ks, Conv3Plan{}, HOP_NONE);
         if (use5) {
             Conv5Args a5;
             a5.src = CatSrc{in.a, in.ca, in.b, in.cb}; a5.prm = prm; a5.w16 = cw.w16; a5.w16_scale = cw.w16_scale;
             a5.bias = cw.bias; a5.out = out; a5.res = res; a5.B = B; a5.Cout = cw.cout; a5.H = Ho; a5.W = Wo;
-            a5.range_ctr = e->range_ctr; a5.x1 = x1;
-            fused.erase(out);
+            a5.range_ctr = e->range_ctr; a5.x1 = x1();
             ProfScope ps(&e->prof, PC_CONV1);
             return launch_conv5(s, a5);
         }
-        fused.erase(out);
         ConvArgs a;
         a.src.a = in.a; a.src.ca = in.ca; a.src.b = in.b; a.src.cb = in.cb; a.src.Hs = in.H; a.src.Ws = in.W;
         a.src.mode = mode; a.src.prm = prm;
@@ -568,29 +564,24 @@ struct Fwd {
     }
 
     // The hop conv1 -> GroupNorm + FiLM + SiLU -> conv2 without h1 (Conv6Emit): conv1's epilogue writes conv2's operand planes.
-    // Accumulators / arrival counters of all fused layers of a forward live in one arena, zeroed once per forward.
-    bool fuse_h1 = true;
+    // Accumulators / arrival counters of all hops of a forward that wait across workgroups live in one arena, zeroed once per forward.
+    bool fuse_h1 = true;   // knobs.fuse_h1, and: an f16 precision, no tape, no time-out replay in progress
     long long* fuse_arena = nullptr; size_t fuse_cap = 0, fuse_off = 0;       // in 8-byte words
-    bool h1_fusable(const ResW& r, int Ho, int Wo) const {
-        return fuse_h1 && !grad && e->precision != 0 && r.conv1.w16 && r.conv2.w16 && r.conv1.ks == 3 && r.conv2.ks == 3 && r.gn2.c == r.cout &&
-               conv7_emit_supported(B, r.cout, Ho, Wo) && fuse_arena && fuse_off + (size_t)B * 64 + (size_t)B * (r.cout / 128) <= fuse_cap &&
-               (size_t)B * (2 * ((r.cout + 15) / 16)) * Ho * Wo * 16 < ((size_t)1 << 32);
-    }
-    Status make_emit(const ResW& r, int Ho, int Wo, Conv6Emit* em, char** s16b, size_t* plane2, int cnt_per_img = 0) {
-        if (cnt_per_img <= 0) cnt_per_img = r.cout / 128;
-        const bool x1 = e->precision == 2;
+    // counters: arrival counters per image taken from the arena (ResblockPlan::arena_counters); 0: conv9's hop inside one workgroup, no arena
+    Status make_emit(const ResW& r, int Ho, int Wo, int counters, Conv6Emit* em, char** s16b, size_t* plane2) {
         const int C8 = 2 * ((r.cout + 15) / 16);
         *plane2 = (size_t)B * C8 * Ho * Wo * 16;
         DPIR_TRY(ws.getT("act#s16b", 2 * *plane2, s16b));
-        em->hi = *s16b; em->lo = x1 ? nullptr : *s16b + *plane2; em->C8 = C8;
+        em->hi = *s16b; em->lo = x1() ? nullptr : *s16b + *plane2; em->C8 = C8;
         em->gamma = r.gn2.gamma; em->beta = r.gn2.beta;
         em->film = r.film_off >= 0 ? film : nullptr; em->film_stride = film_stride; em->film_off = r.film_off < 0 ? 0 : r.film_off;
         em->frows = film_rows; em->fstep = fstep;
+        em->range_ctr = e->range_ctr;
+        if (counters <= 0) return Status{};
         em->acc = fuse_arena + fuse_off;
         fuse_off += (size_t)B * 64;                     // [B][32 groups][2]
         em->cnt = reinterpret_cast<unsigned*>(fuse_arena + fuse_off);
-        fuse_off += ((size_t)B * cnt_per_img + 1) / 2;
-        em->range_ctr = e->range_ctr;
+        fuse_off += ((size_t)B * counters + 1) / 2;
         // test hooks for the time-out path (tests/test_gpu_benched_batches.py): a short spin limit and an arrival count that cannot be reached
         static const int spin_env = getenv("DPIR_FUSE_SPIN_LIMIT") ? atoi(getenv("DPIR_FUSE_SPIN_LIMIT")) : 0;
         static const int extra_env = getenv("DPIR_FUSE_EXPECT_EXTRA") ? atoi(getenv("DPIR_FUSE_EXPECT_EXTRA")) : 0;
@@ -601,69 +592,47 @@ struct Fwd {
         return Status{};
     }
 
-    // conv1 of an up-sampling ResBlock as four 2x2 phase convolutions of the source image (csrc/conv_up.hip): an f16 precision, no tape, the
-    // phase pack loaded, the shape supported, and enough workgroups that launch_conv6 would not have split K (its rule: 256).  Everything else
-    // -- source widths below 32, gradient mode, f32 -- keeps the route through the up-sampled planes.  DPIR_CONV_UP=0 restores that route everywhere.
-    bool conv_up_route(const ResW& r, const Act& in) const {
-        static const bool on = !(getenv("DPIR_CONV_UP") && atoi(getenv("DPIR_CONV_UP")) == 0);
-        return on && r.mode == 1 && !grad && e->precision != 0 && r.conv1.wup && !in.b && in.C() == r.gn1.c &&
-               !conv_up_supported(B, in.C(), r.cout, in.H, in.W, false) && conv_up_workgroups(B, r.cout, in.H, in.W) >= 256;
-    }
-    Status resblock_up(const ResW& r, const Act& in, Act* out, int Ho, int Wo, float* h1, size_t on) {
-        const bool x1 = e->precision == 2;
+    // conv1 of an up-sampling ResBlock as four 2x2 phase convolutions of the source image (csrc/conv_up.hip)
+    Status resblock_up(const ResW& r, const ResblockPlan& rp, const Act& in, Act* out, int Ho, int Wo, float* h1, size_t on) {
         const int C = in.C(), C8 = 2 * (C / 16);
         const size_t plane = (size_t)B * C8 * in.H * in.W * 16;
         char* s16 = nullptr;
         DPIR_TRY(ws.getT("act#s16", 2 * plane, &s16));
         // GroupNorm + SiLU + split at the SOURCE resolution (mode 0), as the reference does before it up-samples
-        if (fuse_small && gn_act_small_supported(C, in.H, in.W, 0)) {
-            if (pending.partial && !is_pending(in.a)) DPIR_TRY(resolve());
-            GnActArgs ga;
-            ga.src = CatSrc{in.a, in.ca, nullptr, 0};
-            ga.pend = pending;
-            ga.gamma = r.gn1.gamma; ga.beta = r.gn1.beta;
-            ga.film = nullptr; ga.film_stride = film_stride; ga.film_off = 0; ga.fstep = fstep; ga.frows = film_rows;
-            ga.silu = true; ga.mode = 0; ga.B = B; ga.Hs = in.H; ga.Ws = in.W;
-            ga.hi = s16; ga.lo = x1 ? nullptr : s16 + plane; ga.range_ctr = e->range_ctr;
-            {
-                ProfScope ps(&e->prof, PC_ELEM);
-                DPIR_TRY(launch_gn_act_small(s, ga));
-            }
-            if (pending.partial) { fused.erase(pending.out); pending = PendingConv{}; }   // finished (and stored) by the fused prologue
+        if (knobs.fuse_small && gn_act_small_supported(C, in.H, in.W, 0)) {
+            DPIR_TRY(small_prologue(r.gn1, r.name + "#gn1", -1, in, 0, nullptr, s16, plane));
         } else {
             DPIR_TRY(resolve());
             float4* prm = nullptr;
             DPIR_TRY(gn(r.gn1, in, r.name + "#gn1", -1, true, &prm));
             ProfScope ps(&e->prof, PC_ELEM);
-            DPIR_TRY(launch_act_split(s, CatSrc{in.a, in.ca, nullptr, 0}, prm, 0, B, in.H, in.W, s16, x1 ? nullptr : s16 + plane, e->range_ctr));
+            DPIR_TRY(launch_act_split(s, CatSrc{in.a, in.ca, nullptr, 0}, prm, 0, B, in.H, in.W, s16, x1() ? nullptr : s16 + plane, e->range_ctr));
         }
         ConvUpArgs a;
         a.xhi = s16; a.xlo = s16 + plane; a.wup = r.conv1.wup; a.wup_scale = r.conv1.wup_scale; a.bias = r.conv1.bias;
-        a.B = B; a.Cin = C; a.Cout = r.cout; a.Hs = in.H; a.Ws = in.W; a.x1 = x1;
+        a.B = B; a.Cin = C; a.Cout = r.cout; a.Hs = in.H; a.Ws = in.W; a.x1 = x1();
         float* o = nullptr;
         DPIR_TRY(ws.getT(r.name + "#out", on, &o));
-        // the hop obeys fuse_h1 (DPIR_FUSE_H1=0, time-out replay) and launch_conv6's whole-K rule of 384 workgroups, as conv7's
-        const bool hop = fuse_h1 && r.gn2.c == r.cout && r.conv2.w16 && r.conv2.ks == 3 && conv6_supported(Ho, Wo) && fuse_arena &&
-                         !conv_up_supported(B, C, r.cout, in.H, in.W, true, 384) && fuse_off + (size_t)B * 64 + (size_t)B * (r.cout / 64) <= fuse_cap;
-        if (hop) {
-            Conv6Emit em; char* s16b = nullptr; size_t plane2 = 0;
-            DPIR_TRY(make_emit(r, Ho, Wo, &em, &s16b, &plane2, r.cout / 64));
-            a.emit = &em; a.min_wg_hop = 384;
-            {
-                ProfScope ps(&e->prof, PC_CONV3);
-                DPIR_TRY(launch_conv_up(s, a));
-            }
+        Conv6Emit em; char* s16b = nullptr; size_t plane2 = 0;
+        float2* st = nullptr;
+        if (rp.hop) {
+            DPIR_TRY(make_emit(r, Ho, Wo, rp.arena_counters, &em, &s16b, &plane2));
+            a.emit = &em; a.min_wg_hop = kHopMinWg;
+        } else {
+            DPIR_TRY(ws.getT("st#" + std::to_string(reinterpret_cast<uintptr_t>(h1)), (size_t)B * r.cout * rp.conv1.stat_slots, &st));
+            a.out = h1; a.stat = st;
+        }
+        {
+            ProfScope ps(&e->prof, PC_CONV3);
+            DPIR_TRY(launch_conv_up(s, a));
+        }
+        layer = r.name + "#conv1";
+        log(CK_CONV_UP, 3, rp.conv1, rp.hop);
+        layer = r.name + "#conv2";
+        if (rp.hop) {
             DPIR_TRY(conv6_on_planes(r.conv2, s16b, plane2, in.a, 1, o, Ho, Wo));
         } else {
-            const int slots = conv_up_stat_slots(in.H, in.W);
-            float2* st = nullptr;
-            DPIR_TRY(ws.getT("st#" + std::to_string(reinterpret_cast<uintptr_t>(h1)), (size_t)B * r.cout * slots, &st));
-            a.out = h1; a.stat = st;
-            {
-                ProfScope ps(&e->prof, PC_CONV3);
-                DPIR_TRY(launch_conv_up(s, a));
-            }
-            fused[h1] = FusedStat{st, slots, nullptr};
+            fused[h1] = FusedStat{st, rp.conv1.stat_slots, nullptr};
             tap(r.name + "#h1", h1, on);
             Act h1a; h1a.a = h1; h1a.ca = r.cout; h1a.H = Ho; h1a.W = Wo;
             DPIR_TRY(gn_conv(r.gn2, r.name + "#gn2", r.film_off, r.conv2, h1a, 0, in.a, 1, o, Ho, Wo));
@@ -681,16 +650,25 @@ struct Fwd {
         size_t on = (size_t)B * r.cout * Ho * Wo;
         float* h1 = nullptr;
         DPIR_TRY(ws.getT(r.name + "#h1", on, &h1));
-        if (conv_up_route(r, in)) return resblock_up(r, in, out, Ho, Wo, h1, on);
+        const int Cin = in.C();
+        ResblockQuery rq;
+        rq.B = B; rq.Cin = Cin; rq.Cout = r.cout; rq.H = in.H; rq.W = in.W; rq.mode = r.mode; rq.concat = in.b != nullptr; rq.has_skip = r.has_skip;
+        rq.gn1_c = r.gn1.c; rq.gn2_c = r.gn2.c; rq.precision = e->precision; rq.grad = grad;
+        rq.hop_allowed = fuse_h1; rq.arena_words_left = fuse_arena ? fuse_cap - fuse_off : 0;
+        rq.conv1_w16 = r.conv1.w16; rq.conv1_w11 = r.conv1.w11; rq.conv1_wup = r.conv1.wup; rq.conv2_w16 = r.conv2.w16; rq.conv2_w11 = r.conv2.w11;
+        rq.skip_w16 = r.has_skip && r.skip.w16;
+        rq.small_prologue = gn_act_small_supported(Cin, in.H, in.W, 0); rq.conv5_ok = conv5_supported(B, r.cout, Ho, Wo);
+        rq.slab = true; rq.slab_floats = partial_cap;
+        const ResblockPlan rp = plan_resblock(rq, knobs, caps);
+        if (rp.up) return resblock_up(r, rp, in, out, Ho, Wo, h1, on);
         Act h1a; h1a.a = h1; h1a.ca = r.cout; h1a.H = Ho; h1a.W = Wo;
         const float* res = nullptr; int res_mode = 0;
-        // ResBlock with a 1x1 skip projection at a resolution the fused low-resolution prologue does not take: ONE pass over the
-        // (concat) input feeds both the skip projection and in_layers -- conv5 emits conv1's split operand planes
-        const int Cin = in.C();
-        const size_t eplane = (size_t)B * (2 * ((Cin + 15) / 16)) * Ho * Wo * 16;
-        if ((emit_skip == 2 || (emit_skip == 1 && r.cout <= 128)) && r.has_skip && r.mode == 0 && r.conv1.w16 && r.skip.w16 && conv6_supported(Ho, Wo) && conv5_supported(B, r.cout, Ho, Wo) &&
-            Cin % 16 == 0 && Cin <= kConv5EmitMaxC && (Ho * Wo) % 256 == 0 && eplane < ((size_t)1 << 32) && !(fuse_small && gn_act_small_supported(Cin, in.H, in.W, 0))) {
-            const bool x1 = e->precision == 2;
+        const bool fuse = rp.hop != HOP_NONE;
+        Conv6Emit em; char* s16b = nullptr; size_t plane2 = 0;
+        float* o = nullptr;
+        if (rp.skip_emit) {
+            // ONE pass over the (concat) input feeds both the skip projection and in_layers: conv5 emits conv1's split operand planes
+            const size_t eplane = (size_t)B * (2 * ((Cin + 15) / 16)) * Ho * Wo * 16;
             float4* prm1 = nullptr;
             TapeRes tr{};
             DPIR_TRY(resolve());
@@ -703,23 +681,26 @@ struct Fwd {
             Conv5Args a5;
             a5.src = CatSrc{in.a, in.ca, in.b, in.cb}; a5.prm = nullptr; a5.w16 = r.skip.w16; a5.w16_scale = r.skip.w16_scale;
             a5.bias = r.skip.bias; a5.out = sk; a5.res = nullptr; a5.B = B; a5.Cout = r.cout; a5.H = Ho; a5.W = Wo;
-            a5.range_ctr = e->range_ctr; a5.x1 = x1;
-            a5.emit_prm = prm1; a5.emit_hi = s16; a5.emit_lo = x1 ? nullptr : s16 + eplane;
+            a5.range_ctr = e->range_ctr; a5.x1 = x1();
+            a5.emit_prm = prm1; a5.emit_hi = s16; a5.emit_lo = x1() ? nullptr : s16 + eplane;
             fused.erase(sk);
+            layer = r.name + "#skip";
+            log(CK_CONV5, 1, Conv3Plan{}, HOP_NONE);
             {
                 ProfScope ps(&e->prof, PC_CONV1);
                 DPIR_TRY(launch_conv5(s, a5));
             }
-            float* o = nullptr;
             DPIR_TRY(ws.getT(r.name + "#out", on, &o));
-            if (h1_fusable(r, Ho, Wo)) {
-                Conv6Emit em; char* s16b = nullptr; size_t plane2 = 0;
-                DPIR_TRY(make_emit(r, Ho, Wo, &em, &s16b, &plane2));
+            layer = r.name + "#conv1";
+            if (fuse) {
+                DPIR_TRY(make_emit(r, Ho, Wo, rp.arena_counters, &em, &s16b, &plane2));
                 DPIR_TRY(conv6_on_planes(r.conv1, s16, eplane, nullptr, 0, nullptr, Ho, Wo, &em));
+                layer = r.name + "#conv2";
                 DPIR_TRY(conv6_on_planes(r.conv2, s16b, plane2, sk, 0, o, Ho, Wo));
             } else {
                 DPIR_TRY(conv6_on_planes(r.conv1, s16, eplane, nullptr, 0, h1, Ho, Wo));
                 tap(r.name + "#h1", h1, on);
+                layer = r.name + "#conv2";
                 DPIR_TRY(gn_conv(r.gn2, r.name + "#gn2", r.film_off, r.conv2, h1a, 0, sk, 0, o, Ho, Wo, &tr.prm2, &tr.st2));
             }
             tap(r.name, o, on);
@@ -738,23 +719,12 @@ struct Fwd {
         // profiles/r04/dead_end_side_stream_skip_*.log.)
         float* sk = nullptr;
         if (r.has_skip) DPIR_TRY(ws.getT(r.name + "#skip", on, &sk));
-        // 8 x 8 with both convolutions on conv9: a GroupNorm group of h1 is whole inside one workgroup of conv1, which writes conv2's planes
-        // itself -- nothing of Conv6Emit's arena is used.  Obeys fuse_h1 like conv7's hop (DPIR_FUSE_H1=0, time-out replay: plain conv9 + gn_act_small).
-        const bool hop9 = fuse_h1 && !grad && r.gn2.c == r.cout && conv9_route(r.conv1, Ho, Wo, true) && conv9_route(r.conv2, Ho, Wo, false);
-        const bool fuse = hop9 || h1_fusable(r, Ho, Wo);
-        Conv6Emit em; char* s16b = nullptr; size_t plane2 = 0;
-        if (hop9) {
-            const int C8 = r.cout / 8;
-            plane2 = (size_t)B * C8 * Ho * Wo * 16;
-            DPIR_TRY(ws.getT("act#s16b", 2 * plane2, &s16b));
-            em.hi = s16b; em.lo = e->precision == 2 ? nullptr : s16b + plane2; em.C8 = C8;
-            em.gamma = r.gn2.gamma; em.beta = r.gn2.beta;
-            em.film = r.film_off >= 0 ? film : nullptr; em.film_stride = film_stride; em.film_off = r.film_off < 0 ? 0 : r.film_off;
-            em.frows = film_rows; em.fstep = fstep; em.range_ctr = e->range_ctr;
-        } else if (fuse) DPIR_TRY(make_emit(r, Ho, Wo, &em, &s16b, &plane2));
+        if (fuse) DPIR_TRY(make_emit(r, Ho, Wo, rp.arena_counters, &em, &s16b, &plane2));
+        layer = r.name + "#conv1";
         DPIR_TRY(gn_conv(r.gn1, r.name + "#gn1", -1, r.conv1, in, r.mode, nullptr, 0, fuse ? nullptr : h1, Ho, Wo, &tr.prm1, &tr.st1, fuse ? &em : nullptr));
         if (!fuse) tap(r.name + "#h1", h1, on);
         if (r.has_skip) {
+            layer = r.name + "#skip";
             DPIR_TRY(conv(r.skip, in, 0, nullptr, nullptr, 0, sk, Ho, Wo));
             res = sk;
             tr.sk = sk;
@@ -762,8 +732,8 @@ struct Fwd {
             if (in.b) return invalid("resblock " + r.name + ": identity skip on a concatenated input");
             res = in.a; res_mode = r.mode;
         }
-        float* o = nullptr;
         DPIR_TRY(ws.getT(r.name + "#out", on, &o));
+        layer = r.name + "#conv2";
         if (fuse) DPIR_TRY(conv6_on_planes(r.conv2, s16b, plane2, res, res_mode, o, Ho, Wo));
         else DPIR_TRY(gn_conv(r.gn2, r.name + "#gn2", r.film_off, r.conv2, h1a, 0, res, res_mode, o, Ho, Wo, &tr.prm2, &tr.st2));
         tap(r.name, o, on);
@@ -788,12 +758,14 @@ struct Fwd {
         DPIR_TRY(ws.getT(aw.name + "#qkv", (size_t)B * 3 * aw.c * T, &qkv));
         DPIR_TRY(ws.getT(aw.name + "#att", (size_t)B * aw.c * T, &att));
         DPIR_TRY(ws.getT(aw.name + "#out", (size_t)B * aw.c * T, &o));
+        layer = aw.name + "#qkv";
         DPIR_TRY(conv(aw.qkv, in, 0, prm, nullptr, 0, qkv, in.H, in.W));
         {
             ProfScope ps(&e->prof, PC_ATTN);
             DPIR_TRY(launch_attention(s, qkv, att, B, aw.c, T, 64));
         }
         Act aa; aa.a = att; aa.ca = aw.c; aa.H = in.H; aa.W = in.W;
+        layer = aw.name + "#proj";
         DPIR_TRY(conv(aw.proj, aa, 0, nullptr, in.a, 0, o, in.H, in.W));
         tap(aw.name + "#qkv", qkv, (size_t)B * 3 * aw.c * T);
         tap(aw.name + "#att", att, (size_t)B * aw.c * T);
@@ -862,20 +834,16 @@ Status unet_forward(dpir_engine* e, const float* x, const int* t_dev, const int*
         DPIR_TRY(launch_time_embed(s, t_dev, y_dev, net.freqs, net.te_w0, net.te_b0, net.te_w2, net.te_b2, net.label_emb, Be, mc, tmp, semb));
         DPIR_TRY(launch_rows_gemv(s, net.film_w, net.film_b, semb, Be, net.film_rows, ted, film));
     }
-    // split-K slab: 16 slices of the largest low-resolution output (layers with < 384 workgroups)
+    // split-K slab: 16 slices of the largest low-resolution output (the layers the planner splits along K)
     float* partial = nullptr;
     size_t partial_cap = (size_t)16 * 1024 * 1024;   // 64 MiB
     DPIR_TRY(ws.getT("conv#partial", partial_cap, &partial));
     Fwd f{e, s, ws, B, hoisted ? film_table : film, net.film_rows, (hoisted || one_row) ? 0 : net.film_rows, hoisted ? film_step : nullptr, partial, partial_cap};
     {
-        static const bool fuse_env = !(getenv("DPIR_FUSE_SMALL") && atoi(getenv("DPIR_FUSE_SMALL")) == 0);   // A/B switch (tools/, tests)
-        static const int emit_env = getenv("DPIR_EMIT_SKIP") ? atoi(getenv("DPIR_EMIT_SKIP")) : 1;
-        f.grad = e->grad_enabled;
         // gradient mode keeps the fused prologues (round 4): gn_act_small leaves the {mean, a, b, act} / {mean, rstd} tables the backward reads
-        f.fuse_small = fuse_env;
-        f.emit_skip = emit_env;
-        static const bool fuse_h1_env = !(getenv("DPIR_FUSE_H1") && atoi(getenv("DPIR_FUSE_H1")) == 0);
-        f.fuse_h1 = fuse_h1_env && !e->fuse_h1_off && !f.grad && e->precision != 0;
+        f.grad = e->grad_enabled;
+        f.caps = device_caps();
+        f.fuse_h1 = f.knobs.fuse_h1 && !e->fuse_h1_off && !f.grad && e->precision != 0;
         if (f.fuse_h1) {       // accumulators + arrival counters of the fused conv1 -> conv2 hops: one arena, zeroed once per forward
             f.fuse_cap = (size_t)B * 4096;         // 8-byte words: room for ~60 fused hops of (64 + Cout / 128) words per image
             DPIR_TRY(ws.getT("fuse#arena", f.fuse_cap, &f.fuse_arena));
@@ -884,7 +852,7 @@ Status unet_forward(dpir_engine* e, const float* x, const int* t_dev, const int*
         ++e->fwd_serial;
         if (f.grad) { e->tape.clear(); e->tape.serial = e->fwd_serial; e->tape.B = B; e->tape.H = H; e->tape.W = W; }
     }
-    if (e->collect_taps) e->taps.clear();
+    if (e->collect_taps) { e->taps.clear(); e->route_log.clear(); }
 
     std::vector<Act> hs;
     Act h;
@@ -893,6 +861,7 @@ Status unet_forward(dpir_engine* e, const float* x, const int* t_dev, const int*
         size_t on = (size_t)B * net.conv_in.cout * H * W;
         DPIR_TRY(ws.getT("input_blocks.0.0#out", on, &o));
         Act xin; xin.a = x; xin.ca = 3; xin.H = H; xin.W = W;
+        f.layer = "input_blocks.0.0";
         DPIR_TRY(f.conv(net.conv_in, xin, 0, nullptr, nullptr, 0, o, H, W));
         f.tap("input_blocks.0.0", o, on);
         h.a = o; h.ca = net.conv_in.cout; h.H = H; h.W = W;
@@ -919,6 +888,7 @@ Status unet_forward(dpir_engine* e, const float* x, const int* t_dev, const int*
         h = o;
     }
     float4* fprm = nullptr; float2* fst = nullptr;
+    f.layer = "out";
     DPIR_TRY(f.gn_conv(net.out_gn, "out#gn", -1, net.out_conv, h, 0, nullptr, 0, out, H, W, &fprm, &fst));
     DPIR_TRY(f.resolve());
     if (f.grad) { e->tape.final_h = h.a; e->tape.final_prm = fprm; e->tape.final_st = fst; e->tape.valid = true; }

@@ -91,15 +91,13 @@ typedef struct dpir_debug_conv11_desc {
     double ms_out;
 } dpir_debug_conv11_desc;
 int dpir_debug_conv11_layer(dpir_engine* e, dpir_debug_conv11_desc* d);
-/* conv11 launches of this process so far: plain epilogue, fused hop (the probe's and the forward's; captured graph replays do not count). */
-void dpir_debug_conv11_counts(long long* plain, long long* hop);
 /* conv1 of an up-sampling ResBlock (3x3 on the nearest-x2 up-sampled x) on host operands.  x[B][Cin][Hs][Ws] is at the SOURCE resolution, out
  * [B][Cout][2 Hs][2 Ws]; prm: optional table [B][Cin][4] {mean, scale, shift, SiLU flag} applied by act_split at the source resolution.
  *   route 0: conv_up (csrc/conv_up.hip: four 2x2 phase convolutions of the source image); route 1: the up-sampled planes + launch_conv6.
  *   hop 0: out and stat_out[B][Cout][2] fp64 {sum, sum of squares} (the epilogue's slots, folded here).
  *   hop 1: the first layer's epilogue writes the second layer's planes -- GroupNorm32(gamma2, beta2), optional FiLM rows film2[B][2 Cout], SiLU --
  *     and the second layer (w2 [Cout2][Cout][3][3], bias2) runs through launch_conv6: out2[B][Cout2][2 Hs][2 Ws].
- *   force_hop: the hop without the forward's lower bound of 384 workgroups (small test shapes).
+ *   force_hop: the hop without the forward's lower bound of workgroups (kHopMinWg, csrc/conv_plan.h; small test shapes).
  * A refusal (shape, residual, gradient-mode engine, f32 precision) is a non-zero return code with dpir_last_error's text; ran_out = 1 conv_up,
  * 2 conv_up's hop, 7 launch_conv6's route.  iters > 0: the whole route (act_split and every launch) is repeated that many times, ms_out = average. */
 typedef struct dpir_debug_conv_up_desc {
@@ -110,8 +108,48 @@ typedef struct dpir_debug_conv_up_desc {
     double ms_out;
 } dpir_debug_conv_up_desc;
 int dpir_debug_conv_up_layer(dpir_engine* e, dpir_debug_conv_up_desc* d);
-/* conv_up launches of this process so far: plain epilogue, fused hop (which route a forward took) */
-void dpir_debug_conv_up_counts(long long* plain, long long* hop);
+/* What the engine's last eager forward ran (recorded while taps are collected): one record per convolution launch, in launch order.
+ *   kernel: 0 fp32 kernel, 5 conv5, 6 conv6, 7 conv7, 17 conv7's narrow variant, 8 conv8, 9 conv9, 11 conv11, 12 conv_up, 60 the split-K combine
+ *     launch_conv6_resolve (same layer name as the convolution it finishes); ks: 3 or 1.
+ *   hop: 0 none, 1 conv7 / conv11 through the arena, 2 conv9 inside one workgroup, 3 conv_up through the arena.
+ *   stat_kind: 0 none, 1 epilogue slots, 2 fp64 per plane, 3 the split-K combine was done by the next layer's fused prologue (gn_act_small).
+ * Up to `cap` records are written; *n_out is the number there are. */
+typedef struct dpir_debug_route_rec {
+    char layer[80];
+    int32_t kernel, ks, ksplit, hop, stat_kind, reserved;
+    long long workgroups;
+} dpir_debug_route_rec;
+int dpir_debug_route_log(dpir_engine* e, dpir_debug_route_rec* recs, int cap, int* n_out);
+/* The planner of the 3x3 routes (csrc/conv_plan.h) on its own: no engine, no GPU.  Capacities (resident workgroups of the conv7 / conv11 /
+ * conv_up emitting kernels) are arguments; knobs == NULL means the built-in defaults, whatever the environment says.  Fields as Conv3Query /
+ * Conv3Plan / ResblockQuery / ResblockPlan there; slab_floats 0 = no slab buffer offered; stats: statistics buffers offered. */
+typedef struct dpir_debug_conv_knobs {
+    int32_t conv8, conv9, conv9_min_wg, conv11, conv_up, split_below, split_target, fuse_small, fuse_h1, emit_skip;
+} dpir_debug_conv_knobs;
+void dpir_debug_conv_knobs_default(dpir_debug_conv_knobs* k);
+typedef struct dpir_debug_conv3_query {
+    int32_t B, Cin, Cout, H, W, precision, grad, w16, w8, w11, conv8_source, defer, hop, has_res, stats, force_kernel;
+    long long slab_floats;
+} dpir_debug_conv3_query;
+typedef struct dpir_debug_conv_plan {
+    int32_t kernel, hop, geo, ksplit, chunks_per_split, stat_kind, stat_slots, refused;
+    long long workgroups;
+} dpir_debug_conv_plan;
+/* n queries -> n plans */
+int dpir_debug_conv3_plan(const dpir_debug_conv3_query* q, int n, const dpir_debug_conv_knobs* knobs, int cap7, int cap11, int cap_up,
+                          dpir_debug_conv_plan* out);
+/* One ResBlock (H x W: its input resolution; mode 0 plain, 1 up, 2 down; a 1x1 skip projection when Cin != Cout) with the weight packs
+ * load_conv makes for `precision`. */
+typedef struct dpir_debug_resblock_query {
+    int32_t B, Cin, Cout, H, W, mode, concat, precision, grad, hop_allowed;
+    long long arena_words_left, slab_floats;
+} dpir_debug_resblock_query;
+typedef struct dpir_debug_resblock_plan_out {
+    int32_t up, skip_emit, hop, arena_counters;
+    dpir_debug_conv_plan conv1, conv2;
+} dpir_debug_resblock_plan_out;
+int dpir_debug_resblock_plan(const dpir_debug_resblock_query* q, const dpir_debug_conv_knobs* knobs, int cap7, int cap11, int cap_up,
+                             dpir_debug_resblock_plan_out* out);
 /* The attention core (csrc/attn.hip) and its backward (csrc/grad.hip: launch_attention_bwd) on host operands, through the product's launchers.
  *   qkv[B][3C][T] in the legacy order: heads first, then q | k | v inside each head (QKVAttentionLegacy); head_ch as the model's num_head_channels.
  *   out[B][C][T] = launch_attention.  dAtt[B][C][T] (optional): dqkv[B][3C][T] = launch_attention_bwd, its T x T scratch allocated here.

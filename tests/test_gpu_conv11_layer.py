@@ -253,7 +253,7 @@ def test_refused_engines(engines):
 
 # ------------------------------------------------------------------------------------------------ forward level
 _FWD_SNIPPET = r"""
-import ctypes as C, sys, numpy as np, torch
+import ctypes as C, json, sys, numpy as np, torch
 sys.path.insert(0, {root!r})
 import diffpir_amd
 from diffpir_amd import _lib
@@ -265,14 +265,17 @@ g = torch.Generator().manual_seed(81)
 x = torch.randn(({B}, 3, {size}, {size}), generator=g); t = torch.randint(0, 1000, ({B},), generator=g)
 xd = e.to_device(x.numpy())
 a = e.unet_forward(xd, t.numpy()).numpy()
+first = _lib.route_log(e)
 b = e.unet_forward(xd, t.numpy()).numpy()
+log = _lib.route_log(e)
 assert np.array_equal(a, b), "two forwards of the same input differ"
+assert log == first, "two forwards of the same input took different routes"
 taps = dict(out=a)
 for name in {names!r}:
     taps[name] = e.read_tap(name)
-plain, hop = C.c_longlong(0), C.c_longlong(0)
-_lib.load_debug().dpir_debug_conv11_counts(C.byref(plain), C.byref(hop))
-taps["launches"] = np.array([plain.value, hop.value])
+c11 = [r for r in first + log if r["kernel"] == 11]       # conv11 launches of the two forwards: plain epilogue, fused hop
+taps["launches"] = np.array([sum(r["hop"] == 0 for r in c11), sum(r["hop"] == 1 for r in c11)])
+taps["routes"] = np.array(json.dumps(log))
 np.savez({out!r}, **taps)
 """
 
@@ -318,6 +321,42 @@ def test_forward_takes_the_routes(forwards, forwards_hop):
     assert on[0] > 0 and on[1] == 0, "64 x 64 layers at B = 16: 256 workgroups, plain epilogue only"
     assert hon[0] > 0 and hon[1] > 0, "128 x 128 layers at B = 8: 512 workgroups, the hop is taken"
     assert list(off) == [0, 0] and list(hoff) == [0, 0], "DPIR_CONV11=0 must restore the old dispatch"
+
+
+def _route_class(r):
+    """A route-log record -> the kernel class a kernel trace shows for it (template EMIT argument -> hop)."""
+    k = r["kernel"]
+    if k == 0:
+        return "fp32_3x3" if r["ks"] == 3 else "fp32_1x1"
+    name = {5: "conv5", 6: "conv6", 7: "conv7", 17: "conv7_narrow", 8: "conv8", 9: "conv9", 11: "conv11", 12: "conv_up", 60: "resolve"}[k]
+    return name + "_hop" if r["hop"] else name
+
+
+@pytest.mark.parametrize("cfg", ["B16_64", "B8_128"])
+def test_forward_launches_the_kernels_the_parent_commit_launched(forwards, forwards_hop, cfg):
+    """The route log of one default forward, counted per kernel class, against tests/golden/conv_route_counts.json: the per-kernel launch counts of
+    a rocprofv3 kernel trace of ONE eager forward of the commit BEFORE the planner existed (kernel names reduced to classes), same topology,
+    precision, batch and size.  conv7's three tilings are one class here (the log does not carry the tiling)."""
+    import json
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "conv_route_counts.json")))[cfg]
+    want = {}
+    for k, v in golden.items():
+        k = "conv7" if k.startswith("conv7_g") else k
+        want[k] = want.get(k, 0) + v
+    log = json.loads(str((forwards[0] if cfg == "B16_64" else forwards_hop)["on"]["routes"]))
+    got = {}
+    for r in log:
+        c = _route_class(r)
+        got[c] = got.get(c, 0) + 1
+    print(f"route classes {cfg}: {dict(sorted(got.items()))}")
+    assert got == want
+    # split-K combines: every split launch is either finished by launch_conv6_resolve (a `resolve` record of the same layer right behind its
+    # convolution's statistics kind 2 / 0) or left to the next layer's fused prologue (kind 3); the parent's trace has `resolve` conv6_reduce launches
+    split = [r for r in log if r["ksplit"] > 1 and r["kernel"] in (6, 7)]
+    pending = [r for r in split if r["stat_kind"] == 3]
+    resolved = {r["layer"] for r in log if r["kernel"] == 60}
+    assert len(resolved) == want.get("resolve", 0) and len(split) == len(pending) + len(resolved)
+    assert {r["layer"] for r in split if r["stat_kind"] != 3} == resolved and not {r["layer"] for r in pending} & resolved
 
 
 def test_forward_route_on_equals_route_off_to_the_fused_hop_bar(forwards, forwards_hop):

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from tests import conv3_f64 as cf
+from tests import conv_route_rules as rr
 
 pytestmark = pytest.mark.gpu
 
@@ -103,33 +104,8 @@ def _run(e, op, route=0, split=0, defer=0):
                 err=e.lib.dpir_last_error(e.h) if rc else b"")
 
 
-# ------------------------------------------------------------------------------------------------ launch_conv6's documented rule
-def _geo(H, W):
-    if W % 4 or W < 8 or H < 8:
-        return -1
-    return 0 if W >= 32 else (1 if W >= 16 else 2)
-
-
-def _expected(prec, shape, route=0, split=0):
-    """(path, ksplit) from the rules written in csrc/conv6.hip (launch_conv6) and csrc/unet.hip (Fwd::conv): tiles of 8x32 / 16x16 / 4 images
-    x 8x8; split-K only with a slab buffer and fewer than split_below = 256 workgroups, up to split_target = 256 of them, at most chunks / 2 and
-    16 slabs, no empty slab; conv6 only in the 8x32 geometry, for split-K launches and for a last 128-channel block with at most 64 live channels
-    (unless the whole launch has at most 32 output channels)."""
-    B, ca, cb, cout, H, W = shape
-    g = _geo(H, W)
-    if prec == "f32" or g < 0:
-        return 0, 0
-    tw, th, ti = ((32, 8, 1), (16, 16, 1), (8, 8, 4))[g]
-    blocks = -(-W // tw) * -(-H // th) * -(-B // ti) * -(-cout // 128)
-    chunks = -(-(ca + cb) // 16)
-    S = 1
-    if split and blocks < 256:
-        S = max(1, min(-(-256 // blocks), chunks // 2, 16))
-    per = -(-chunks // S)
-    S = -(-chunks // per)
-    idle_half = cout % 128 != 0 and cout % 128 <= 64 and cout > 32
-    path = route if route in (6, 7) else (6 if g == 0 and (S > 1 or idle_half) else 7)
-    return path, S
+# launch_conv6's documented rule: tests/conv_route_rules.py (shared with the planner's host tests)
+_geo, _expected = rr.geo, rr.expected
 
 
 _refs = {}
