@@ -6,6 +6,7 @@
 #include "blur.h"
 #include "inpaint.h"
 #include "progress.h"
+#include "lpips.h"
 #include <math.h>
 #include <string.h>
 #include <stdlib.h>
@@ -225,6 +226,7 @@ void dpir_destroy(dpir_engine* e) {
     (void)dpir_comm_destroy(e);
     if (e->range_ctr) (void)hipFree(e->range_ctr);
     if (e->progress_premix) (void)hipFree(e->progress_premix);
+    lpips_free(e);
     (void)hipStreamDestroy(e->stream);
     delete e;
 }
@@ -693,6 +695,43 @@ int dpir_metrics(dpir_engine* e, const float* x0, const uint8_t* gt, int B, int 
         if (psnr_y_host) psnr_y_host[i] = mse_y == 0.0 ? INFINITY : (float)(20.0 * log10(2.0 / sqrt(mse_y + 1e-10)));
     }
     return DPIR_OK;
+}
+
+int dpir_lpips_load(dpir_engine* e, const dpir_tensor* weights, int n) {
+    if (!e || !weights || n <= 0) return fail(e, invalid("dpir_lpips_load: null argument"));
+    (void)hipSetDevice(e->device);
+    API_TRY(e, lpips_load(e, weights, n));
+    return DPIR_OK;
+}
+
+int dpir_lpips(dpir_engine* e, const float* x0, const uint8_t* gt_u8, const float* gt_f32, int B, int H, int W, float* lpips_host) {
+    if (!e || !x0 || !lpips_host) return fail(e, invalid("dpir_lpips: null argument"));
+    if ((gt_u8 != nullptr) == (gt_f32 != nullptr)) return fail(e, invalid("dpir_lpips: exactly one of gt_u8_dev and gt_f32_dev must be given"));
+    API_TRY(e, check_shape("dpir_lpips", B, H, W));
+    if (H < 16 || W < 16) return fail(e, invalid("dpir_lpips: H and W must be >= 16 (relu5_3 would be empty; got H " + std::to_string(H) + ", W " + std::to_string(W) + ")"));
+    if (!e->lpips || !e->lpips->loaded) return fail(e, invalid("dpir_lpips: no LPIPS weights loaded (dpir_lpips_load)"));
+    (void)hipSetDevice(e->device);
+    {
+        ProfScope ps(&e->prof, PC_ELEM);
+        API_TRY(e, lpips_run(e, x0, gt_u8, gt_f32, B, H, W));
+    }
+    return dpir_d2h(e, lpips_host, e->lpips->score_f, sizeof(float) * B);
+}
+
+int dpir_lpips_keep_taps(dpir_engine* e, int on) {
+    if (!e) return DPIR_ERR_INVALID;
+    e->lpips_keep_taps = on != 0;
+    return DPIR_OK;
+}
+
+int dpir_lpips_read_tap(dpir_engine* e, int k, float* host_dst, size_t cap, size_t* numel_out) {
+    if (!e || !numel_out) return fail(e, invalid("dpir_lpips_read_tap: null argument"));
+    if (k < 0 || k >= kLpipsTaps) return fail(e, invalid("dpir_lpips_read_tap: tap index must be 0..4"));
+    if (!e->lpips || e->lpips->tap_numel[k] == 0) return fail(e, Status{DPIR_ERR_STATE, "dpir_lpips_read_tap: no kept taps (dpir_lpips_keep_taps before dpir_lpips)"});
+    *numel_out = e->lpips->tap_numel[k];
+    if (!host_dst) return DPIR_OK;
+    if (cap < *numel_out) return fail(e, invalid("dpir_lpips_read_tap: destination too small"));
+    return dpir_d2h(e, host_dst, e->lpips->tap[k], sizeof(float) * *numel_out);
 }
 
 }  // extern "C"

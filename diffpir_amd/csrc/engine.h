@@ -83,6 +83,8 @@ struct Tape {
     void clear() { valid = false; nodes.clear(); res.clear(); attn.clear(); }
 };
 
+struct LpipsState;       // lpips.h: VGG16 trunk + head weights, the chunk arena and the kept taps
+
 struct ResizerTab { int in_len = 0, out_len = 0, taps = 0; float* w = nullptr; int* idx = nullptr; };
 
 }  // namespace dpir
@@ -154,6 +156,8 @@ struct dpir_engine {
         float* strip_f32 = nullptr; uint8_t* strip_u8 = nullptr; float* masked_f32 = nullptr; uint8_t* masked_u8 = nullptr; float* minmax = nullptr;
     } progress;
     float* progress_premix = nullptr; size_t progress_premix_bytes = 0;
+    dpir::LpipsState* lpips = nullptr;           // dpir_lpips_load (lpips.hip); its arena is its own, NOT `ws`: growing that would orphan the step graphs
+    bool lpips_keep_taps = false;                // dpir_lpips_keep_taps: the next dpir_lpips calls keep their five feature maps for dpir_lpips_read_tap
     void* comm = nullptr; int comm_world = 1, comm_rank = 0;     // RCCL communicator (comm.cpp), or null
 
     dpir::Status resizer(int in_len, int sf, dpir::ResizerTab* out);

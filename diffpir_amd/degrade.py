@@ -1,8 +1,8 @@
 """Degradation synthesis and metrics on the device: the steps either side of the restoration loop.
 
 `degrade` mirrors CustomDataset.__getitem__'s arithmetic (main_ddpir.py:84-114) for a batch of uint8 ground-truth images;
-`metrics` mirrors main_ddpir.py:482-517 (PSNR and PSNR on the Y channel).  Both are thin wrappers over dpir_degrade /
-dpir_metrics; PSF and mask GENERATION (a few hundred scalar operations per image under the numpy RNG) stays on the host so that
+`metrics` mirrors main_ddpir.py:482-517 (PSNR and PSNR on the Y channel), `lpips` main_ddpir.py:489-493.  All are thin wrappers over
+dpir_degrade / dpir_metrics / dpir_lpips; PSF and mask GENERATION (a few hundred scalar operations per image under the numpy RNG) stays on the host so that
 kernels and masks remain bit-identical to the reference's.
 """
 from __future__ import annotations
@@ -55,3 +55,20 @@ def metrics(engine: Engine, x0, gt_u8_dev):
     py = np.empty(B, np.float32)
     engine._check(engine.lib.dpir_metrics(engine.h, _ptr(x0), _ptr(gt_u8_dev), B, H, W, p.ctypes.data, py.ctypes.data))
     return p, py
+
+
+def lpips(engine: Engine, x0, gt):
+    """Per-image LPIPS (v0.1, net='vgg') of x0*2-1 against the ground truth*2-1 as a float32 array [B] (dpir_lpips; needs
+    engine.load_lpips).  x0: float32 [B,3,H,W] in [0,1], un-clamped; gt: uint8 [B,H,W,3] (img_H) or float32 [B,3,H,W] in [0,1];
+    DeviceArrays or numpy."""
+    if isinstance(x0, np.ndarray):
+        x0 = engine.to_device(np.ascontiguousarray(x0, dtype=np.float32))
+    if isinstance(gt, np.ndarray):
+        gt = engine.to_device(np.ascontiguousarray(gt))
+    B, _, H, W = x0.shape
+    u8 = np.dtype(gt.dtype) == np.uint8
+    if tuple(gt.shape) != ((B, H, W, 3) if u8 else (B, 3, H, W)) or not (u8 or np.dtype(gt.dtype) == np.float32):
+        raise ValueError(f"lpips: ground truth {gt.dtype} {tuple(gt.shape)} does not go with x0 {tuple(x0.shape)} (uint8 [B,H,W,3] or float32 [B,3,H,W])")
+    out = np.empty(B, np.float32)
+    engine._check(engine.lib.dpir_lpips(engine.h, _ptr(x0), _ptr(gt) if u8 else None, None if u8 else _ptr(gt), B, H, W, out.ctypes.data))
+    return out

@@ -237,6 +237,35 @@ class Engine:
                 arr[i].shape[d] = a.shape[d]
         self._check(self.lib.dpir_load_unet(self.h, C.byref(desc), arr, n))
 
+    # ---- LPIPS (csrc/lpips.hip)
+    def load_lpips(self, state_dict):
+        """VGG16 trunk + LPIPS heads (dpir_lpips_load).  state_dict: any layout lpips.canonical recognises (torchvision's features.N.*, a
+        full lpips.LPIPS(net='vgg') state dict, the heads-only file merged with a trunk, or the canonical keys)."""
+        from . import lpips as lp
+        sd = lp.canonical(state_dict)
+        arr = (_lib.Tensor * len(sd))()
+        for i, (k, a) in enumerate(sd.items()):
+            arr[i].name = k.encode()
+            arr[i].data = a.ctypes.data
+            arr[i].ndim = a.ndim
+            for d in range(a.ndim):
+                arr[i].shape[d] = a.shape[d]
+        self._check(self.lib.dpir_lpips_load(self.h, arr, len(sd)))
+        self.lpips_loaded = True
+
+    lpips_loaded = False
+
+    def lpips_keep_taps(self, on=True):
+        self._check(self.lib.dpir_lpips_keep_taps(self.h, 1 if on else 0))
+
+    def lpips_read_tap(self, k: int) -> np.ndarray:
+        """Tap k (0..4: relu1_2 ... relu5_3) of the last dpir_lpips call, flat: [2B, C_k, H_k, W_k], estimate rows first."""
+        n = C.c_size_t()
+        self._check(self.lib.dpir_lpips_read_tap(self.h, int(k), None, 0, C.byref(n)))
+        out = np.empty(n.value, np.float32)
+        self._check(self.lib.dpir_lpips_read_tap(self.h, int(k), out.ctypes.data, n.value, C.byref(n)))
+        return out
+
     def unet_forward(self, x, t, y=None, out=None):
         B, _, H, W = x.shape
         t = np.ascontiguousarray(t, dtype=np.int64)

@@ -9,7 +9,9 @@ Accepts the reference's configs/*.yaml unchanged.  What it keeps from the refere
 (noise_level_img/255, sigma = max(0.001, .), kernel_std), the per-task lambda/zeta sweeps (main_ddpir.py:548-580),
 the per-image degradation recipe (main_ddpir.py:46-117) and the batch PSNR log line.  What it does differently:
 the loop body is one engine call (restore.restore_batch), images are read / written with PIL when available (cv2
-is not installed here), LPIPS is skipped (package absent; `calc_LPIPS` is honoured as "not available"), and with no
+is not installed here), LPIPS is computed by the engine (dpir_lpips) from the two weight files under <cwd>/model_zoo when `calc_LPIPS`
+is set and they are there (one WARNING and no LPIPS otherwise: never a metric on synthetic weights), and the batch's LPIPS is the mean over
+its images (the reference keeps image 0's score times the batch size, main_ddpir.py:491: the same thing at batch_size 1).  With no
 dataset / checkpoint on disk it falls back to synthetic ground truth and synthetic weights, saying so in the log.
 """
 from __future__ import annotations
@@ -23,7 +25,7 @@ import time
 import numpy as np
 import yaml
 
-from . import restore, synth, script_util, utils_model, weights, degrade as dgr
+from . import restore, synth, script_util, utils_model, weights, degrade as dgr, lpips as lpips_host
 from .engine import Engine
 from .utils_inpaint import mask_generator
 
@@ -123,7 +125,33 @@ def check_batch_sweeps(config):
     restore.check_per_image(loop_config(config, *sweeps(config)[0]), restore.PerImage(lambda_=[], zeta=[]))
 
 
-def run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph, cache):
+def setup_lpips(eng, config) -> bool:
+    """calc_LPIPS (main_ddpir.py:542-545): load the VGG16 trunk and the LPIPS heads once.  False -- after ONE warning -- when the key is off
+    or the weight files are not under <cwd>/model_zoo; the run then continues exactly as without the key."""
+    if not bool(config.get("calc_LPIPS", False)):
+        return False
+    paths = lpips_host.find_weight_files(config)
+    try:
+        if not paths:
+            raise FileNotFoundError("no weight file found")
+        eng.load_lpips(lpips_host.load_weights(*paths))
+    except (FileNotFoundError, KeyError) as ex:
+        log.warning("calc_LPIPS: LPIPS is not computed -- %s.  It needs model_zoo/%s (torchvision's VGG16) and model_zoo/%s (the lpips package's "
+                    "weights/v0.1/vgg.pth) under cwd=%r; see INTEGRATION.md", ex, config.get("lpips_vgg_path", "vgg16-397923af.pth"),
+                    config.get("lpips_lin_path", "lpips_vgg.pth"), config.get("cwd", ""))
+        return False
+    return True
+
+
+def metric_rows(eng, out_f32, gt_dev, with_lpips):
+    """float64 [n, 2 or 3]: per-image PSNR, PSNR-Y [, LPIPS] (dpir_metrics, dpir_lpips)."""
+    cols = list(dgr.metrics(eng, out_f32, gt_dev))
+    if with_lpips:
+        cols.append(dgr.lpips(eng, out_f32, gt_dev))
+    return np.stack(cols, 1).astype(np.float64)
+
+
+def run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph, cache, with_lpips=False):
     """The sweep loop of main() flattened into full batches (YAML `engine_batch_sweeps: true`): every batch holds batch_size (point, image) pairs
     and runs as ONE restore_batch call with per-image (lambda, zeta) and the images' global numbers as noise keys.  Each distinct image of a batch
     is degraded once, with the seed and image_offset the sequential driver uses, and its y / k / mask / ground-truth rows are gathered on the
@@ -133,6 +161,7 @@ def run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph,
     batches = flatten_sweeps(len(points), n_img, bs)
     cfg = loop_config(config, *points[0])
     values, t0 = [], time.time()
+    ncol = 3 if with_lpips else 2
 
     def gather(parts, rows):
         """device rows: rows[j] = (part index, row inside it) -> one DeviceArray [len(rows), ...] (dpir_d2d per row), or None"""
@@ -149,7 +178,7 @@ def run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph,
         mine = pairs[lo:hi]
         wanted = {g for _, g in mine}
         u8_local = eng.empty((hi - lo, H, W, 3), np.uint8)
-        per_img = np.zeros((0, 2))
+        per_img = np.zeros((0, ncol))
         where, ys, ks, ms, gts = {}, [], [], [], []
         for g0, cnt in image_runs(list(dict.fromkeys(g for _, g in pairs))):
             k_all, mask_all = make_operators(config, cnt, g0, H, W)          # every rank draws every operator of the batch (seeded numpy)
@@ -166,31 +195,43 @@ def run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph,
             out_f32 = restore.restore_batch(eng, cfg, gather(ys, rows), k=gather(ks, rows), mask=gather(ms, rows), noise_source="device",
                                             seed=config.seed, use_graph=use_graph, out_u8=u8_local, _cache=cache,
                                             skip_dead_final_eval=bool(config.get("engine_skip_dead_final_eval", False)), per_image=pi)
-            psnr_i, psnr_y_i = dgr.metrics(eng, out_f32, gather(gts, rows))
-            per_img = np.stack([psnr_i, psnr_y_i], 1).astype(np.float64)
+            per_img = metric_rows(eng, out_f32, gather(gts, rows), with_lpips)
         ddist.all_gather_results(u8_local, len(pairs), rank, world, engine=eng)           # the one collective of the path
-        allm = ddist.all_gather_results(per_img.reshape(-1, 2), len(pairs), rank, world, engine=eng)
+        allm = ddist.all_gather_results(per_img.reshape(-1, ncol), len(pairs), rank, world, engine=eng)
         values.append([tuple(v) for v in allm])
     dt = time.time() - t0
     results = []
     for (lambda_, zeta), per_point in zip(points, regroup_sweeps(batches, values, len(points), n_img)):
         if rank == 0:
             log.info("eta:%s, zeta:%s, lambda:%s, guidance_scale:%s", config.eta, zeta, lambda_, config.guidance_scale)
-        psnrs, psnrs_y = [], []
+        psnrs, psnrs_y, lps = [], [], []
         for i0 in range(0, n_img, bs):             # the sequential driver's batches of this point: the same averages, the same log lines
             chunk = np.asarray(per_point[i0:i0 + bs], np.float64)
             p, p_y = float(np.mean(chunk[:, 0])), float(np.mean(chunk[:, 1]))
             psnrs.append(p * len(chunk))
             psnrs_y.append(p_y * len(chunk))
+            if with_lpips:
+                lps.append(float(np.mean(chunk[:, 2])) * len(chunk))
             if rank == 0:
-                log.info("batch%4d--> PSNR: %.4fdB", i0 // bs + 1, p)
+                log_batch(i0 // bs + 1, p, lps[-1] / len(chunk) if with_lpips else None, sum(lps) / n_img)
         if rank == 0:
             log.info("-----------> Average PSNR(RGB) of (%s) scale factor: (%d), sigma: (%.3f): %.4f dB  [%.2f images/s on %d GPU(s)]",
                      config.testset_name, config.sf, config.noise_level_model, sum(psnrs) / n_img, len(points) * n_img / dt, world)
             log.info("-----------> Average PSNR(Y) of (%s) scale factor: (%d), sigma: (%.3f): %.4f dB",
                      config.testset_name, config.sf, config.noise_level_model, sum(psnrs_y) / n_img)
+            if with_lpips:
+                log.info("-----------> Average LPIPS of (%s) scale factor: (%d), sigma: (%.3f): %.4f",
+                         config.testset_name, config.sf, config.noise_level_model, sum(lps) / n_img)
         results.append(sum(psnrs) / n_img)
     return results
+
+
+def log_batch(number, psnr, lpips_score, ave_lpips):
+    """The batch line of main_ddpir.py:493 / :495.  `ave LPIPS` is the running sum over the WHOLE test set's image count, as in the reference."""
+    if lpips_score is None:
+        log.info("batch%4d--> PSNR: %.4fdB", number, psnr)
+    else:
+        log.info("batch%4d--> PSNR: %.4fdB; LPIPS: %.4f; ave LPIPS: %.4f", number, psnr, lpips_score, ave_lpips)
 
 
 def load_images(config, n_synth):
@@ -419,6 +460,8 @@ def main(argv=None):
         log.info("checkpoint %s not found: using synthetic weights (results are not meaningful images)", margs.model_path)
         model.load_state_dict(weights.synth_state_dict("ffhq" if config.model_name == "diffusion_ffhq_10m" else "imagenet256"))
 
+    with_lpips = setup_lpips(eng, config)
+    ncol = 3 if with_lpips else 2
     imgs, names = load_images(config, args.synthetic)
     use_graph = bool(config.get("engine_graph", True))
     noise = config.get("engine_noise", "device")
@@ -437,19 +480,19 @@ def main(argv=None):
         ddist.check_dps_sharding(eng, loop_config(config, *sweeps(config)[0]), min(config.batch_size, len(imgs) - i0), world)
     points = sweeps(config)[:args.max_sweeps] if args.max_sweeps else sweeps(config)
     if batch_sweeps:
-        results = run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph, cache)
+        results = run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph, cache, with_lpips)
         points = []
     for si, (lambda_, zeta) in enumerate(points):
         cfg = loop_config(config, lambda_, zeta)
         if rank == 0:
             log.info("eta:%s, zeta:%s, lambda:%s, guidance_scale:%s", config.eta, zeta, lambda_, config.guidance_scale)
-        psnrs, psnrs_y, t0, n = [], [], time.time(), 0
+        psnrs, psnrs_y, lps, t0, n = [], [], [], time.time(), 0
         for i0 in range(0, len(imgs), config.batch_size):
             gt = imgs[i0:i0 + config.batch_size]                           # uint8 [n,H,W,3]
             n_b, H, W = gt.shape[0], gt.shape[1], gt.shape[2]
             k_all, mask_all = make_operators(config, n_b, i0, H, W)      # every rank draws the same operators (seeded numpy)
             lo, hi = ddist.shard_range(n_b, rank, world)                 # this rank's images of the batch
-            per_img = np.zeros((0, 2))
+            per_img = np.zeros((0, ncol))
             u8_local = eng.empty((hi - lo, H, W, 3), np.uint8)          # engine-owned result buffer (send side of the all-gather)
             drawn = None
             dps_mode = cfg.generate_mode in ("DPS_y0", "DPS_yt")
@@ -497,24 +540,28 @@ def main(argv=None):
                 out_f32 = restore.restore_batch(eng, cfg, y, k=ops.get("k"), mask=None if dps_mode else ops.get("mask"), noise_source=noise,
                                                 predrawn=drawn, noise_fn=dps_nf, seed=config.seed, image_offset=i0 + lo, use_graph=use_graph and not deb_grad, out_u8=u8_local, _cache=cache,
                                                 skip_dead_final_eval=bool(config.get("engine_skip_dead_final_eval", False)), progress=pg)
-                psnr_i, psnr_y_i = dgr.metrics(eng, out_f32, ops["gt"])            # dpir_metrics: per-image PSNR / PSNR-Y
+                per_img = metric_rows(eng, out_f32, ops["gt"], with_lpips)         # dpir_metrics: per-image PSNR / PSNR-Y; dpir_lpips
                 if pg is not None:
-                    emit_progress(config, pg, names[i0 + lo:i0 + hi], lambda_, psnr_i)
-                per_img = np.stack([psnr_i, psnr_y_i], 1).astype(np.float64)
+                    emit_progress(config, pg, names[i0 + lo:i0 + hi], lambda_, per_img[:, 0].astype(np.float32))
             u8 = ddist.all_gather_results(u8_local, n_b, rank, world, engine=eng)           # the one collective of the path
-            allm = ddist.all_gather_results(per_img.reshape(-1, 2), n_b, rank, world, engine=eng)      # per-image PSNR rows (host numpy)
+            allm = ddist.all_gather_results(per_img.reshape(-1, ncol), n_b, rank, world, engine=eng)   # per-image PSNR [/ LPIPS] rows (host numpy)
             p, p_y = float(np.mean(allm[:, 0])), float(np.mean(allm[:, 1]))
             psnrs.append(p * n_b)
             psnrs_y.append(p_y * n_b)
             n += n_b
+            if with_lpips:
+                lps.append(float(np.mean(allm[:, 2])) * n_b)           # the mean over the batch's images (Q: the reference keeps image 0's)
             if rank == 0:
-                log.info("batch%4d--> PSNR: %.4fdB", i0 // config.batch_size + 1, p)
+                log_batch(i0 // config.batch_size + 1, p, lps[-1] / n_b if with_lpips else None, sum(lps) / len(imgs))
         dt = time.time() - t0
         if rank == 0:
             log.info("-----------> Average PSNR(RGB) of (%s) scale factor: (%d), sigma: (%.3f): %.4f dB  [%.2f images/s on %d GPU(s)]",
                      config.testset_name, config.sf, config.noise_level_model, sum(psnrs) / n, n / dt, world)
             log.info("-----------> Average PSNR(Y) of (%s) scale factor: (%d), sigma: (%.3f): %.4f dB",
                      config.testset_name, config.sf, config.noise_level_model, sum(psnrs_y) / n)
+            if with_lpips:
+                log.info("-----------> Average LPIPS of (%s) scale factor: (%d), sigma: (%.3f): %.4f",
+                         config.testset_name, config.sf, config.noise_level_model, sum(lps) / n)
         results.append(sum(psnrs) / n)
     ddist.shutdown()
     eng.close()

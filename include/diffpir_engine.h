@@ -499,6 +499,29 @@ int dpir_degrade(dpir_engine* e, const dpir_degrade_desc* d, const uint8_t* gt_u
  * a 63-pixel image at 87 dB); the two agree to 2e-5 dB on the reference's fixture.  Identical images give +inf in both. */
 int dpir_metrics(dpir_engine* e, const float* x0_dev, const uint8_t* gt_u8_dev, int B, int H, int W, float* psnr_host, float* psnr_y_host);
 
+/* ---- LPIPS (calc_LPIPS: main_ddpir.py:489-493, 532-535, 543-545) --------------------------- */
+/* Replaces loss_fn_vgg = lpips.LPIPS(net='vgg') and its call loss_fn_vgg(x_0*2-1, img_H/255*2-1) (LPIPS v0.1, eval, normalize=False, spatial=False):
+ * the scaling layer (shift -.030 -.088 -.188, scale .458 .448 .450, applied before the first convolution's zero padding), the 13 convolutions of
+ * VGG16 `features` (3x3 pad 1 + bias + ReLU; 2x2 stride-2 max-pool, floor, behind convolutions 2, 4, 7, 10), taps behind the ReLU of convolutions
+ * 2, 4, 7, 10, 13, and per tap n = f / (sqrt(sum_c f^2) + 1e-10), d = sum_c w_c (n0 - n1)^2, spatial mean; the score is the sum of the five means.
+ * dpir_lpips_load copies and packs the weights (caller keeps the host arrays).  Canonical keys: features.{0,2,5,7,10,12,14,17,19,21,24,26,28}.{weight,
+ * bias} (OIHW / [Cout]) and lin{0..4}.weight (64, 128, 256, 512, 512 values, any rank); DPIR_ERR_INVALID naming the first missing / mis-shaped key.
+ * Independent of dpir_load_unet and dpir_set_precision: the trunk always runs the exact-fp32 MFMA convolution. */
+int dpir_lpips_load(dpir_engine* e, const dpir_tensor* weights, int n_weights);
+/* x0_dev [B,3,H,W] float32 in [0,1] and NOT clamped (x_0 of main_ddpir.py:470); the ground truth as uint8 [B,H,W,3] (gt_u8_dev; img_H/255 formed
+ * as dpir_metrics forms it) or float32 [B,3,H,W] in [0,1] (gt_f32_dev) -- exactly one of the two.  lpips_host: HOST array of B floats (syncs).
+ * Features are float32; the channel norms, the distance and the means are evaluated in float64 and rounded to float once.  An image's score has
+ * the same bits wherever it sits in a batch, for every B and on every repeat (no atomics; fixed-order reductions); identical images give 0.
+ * The 2B rows run in chunks through an engine-owned arena of at most 8 rows at 256 x 256 (about 0.8 GB; one pair at least for larger images);
+ * env DPIR_LPIPS_CHUNK=<rows> forces a smaller chunk (tests) -- chunking changes no bit.  DPIR_ERR_INVALID before anything is enqueued: H or W
+ * below 16 (relu5_3 would be empty), no weights loaded, both or neither ground truth. */
+int dpir_lpips(dpir_engine* e, const float* x0_dev, const uint8_t* gt_u8_dev, const float* gt_f32_dev, int B, int H, int W, float* lpips_host);
+/* Parity taps: with keep on, every dpir_lpips call keeps its five post-ReLU feature maps (relu1_2 ... relu5_3) and dpir_lpips_read_tap copies
+ * tap k of the last call to host as [2B,C_k,H_k,W_k]: rows [0,B) the estimate, rows [B,2B) the ground truth.  Off by default (a B = 16 call at
+ * 256 x 256 would keep 1 GB).  host_dst NULL: only numel_out is written. */
+int dpir_lpips_keep_taps(dpir_engine* e, int on);
+int dpir_lpips_read_tap(dpir_engine* e, int k, float* host_dst, size_t cap_floats, size_t* numel_out);
+
 /* ---- instrumentation --------------------------------------------------------------------- */
 /* Kernel-time accounting with HIP events on the engine stream.  class ids: 0 conv3x3, 1 conv1x1,
  * 2 groupnorm-stats, 3 attention, 4 fft-prox, 5 elementwise/other, 6 whole unet forward.
