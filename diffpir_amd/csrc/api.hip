@@ -1219,10 +1219,18 @@ static Status p_sample_impl(dpir_engine* e, const float* x, const int* t_dev, co
     return Status{};
 }
 
+// The measurement operator of the gradient modes, the one thing the two families differ in: Resizer(1 / sf) (k == nullptr; ONE residual norm for
+// the whole batch, all-reduced over the communicator) or the deblurring program's reflect-padded blur Tx with one K x K PSF per image (sf 1; one
+// norm PER IMAGE, no collective).  The measurement itself is a BlurResidual's y / noise / ma / mb / sa / s1m / qa / qb for both.
+struct GradOp {
+    int sf = 1; const float* k = nullptr; int K = 0;
+    int norm_images(int B) const { return k ? B : 0; }        // the `images` of launch_grad_step / launch_neg_scale_by_norm, the floats of the norm (0: one)
+    size_t measurement_count(int B, int H, int W) const { return (size_t)B * 3 * (H / sf) * (W / sf); }
+};
+
 // d || m - Resizer(x_hat) || / d x_hat, un-normalised: diff = m - Resizer(x_hat) (kept), the norm (device float), gup = Resizer^T diff.
-// measurement = sa (ma y + mb) + s1m noise.
-static Status dps_residual(dpir_engine* e, const float* x_hat, const float* y, float ma, float mb, float sa, float s1m, const float* noise, int sf,
-                           int B, int H, int W, float** gup_out, float** norm_out) {
+// measurement = sa (ma y + mb) + s1m noise (qa / qb are the blur operator's).
+static Status dps_residual(dpir_engine* e, const float* x_hat, const BlurResidual& meas, int sf, int B, int H, int W, float** gup_out, float** norm_out) {
     const int h = H / sf, w = W / sf;
     const size_t total = (size_t)B * 3 * H * W, small = (size_t)B * 3 * h * w;
     hipStream_t s = e->stream;
@@ -1237,7 +1245,7 @@ static Status dps_residual(dpir_engine* e, const float* x_hat, const float* y, f
     DPIR_TRY(e->resizer(H, sf, &th));
     DPIR_TRY(e->resizer(W, sf, &tw));
     DPIR_TRY(resize_down_impl(e, x_hat, 1.f, 0.f, down, sf, B, H, W));
-    DPIR_TRY(launch_diff_norm(s, y, ma, mb, down, diff, small, part, 256, nullptr, sa, s1m, noise));
+    DPIR_TRY(launch_diff_norm(s, meas.y, meas.ma, meas.mb, down, diff, small, part, 256, nullptr, meas.sa, meas.s1m, meas.noise));
     DPIR_TRY(dps_norm(e, part, 256, normv));
     // Resizer^T: the forward resamples dim 2 (H) first, then dim 3 (W) -> adjoint W first, then H
     DPIR_TRY(launch_band_resample_T(s, diff, tw.w, tw.idx, tw.taps, B * 3 * h, W, w, 1, 1.f, gmid));
@@ -1246,10 +1254,41 @@ static Status dps_residual(dpir_engine* e, const float* x_hat, const float* y, f
     return Status{};
 }
 
+static Status blur_adjoint_impl(dpir_engine* e, const float* g, const float* k, int K, float xa, float* gx, int B, int H, int W) {
+    float* pad = nullptr;
+    DPIR_TRY(e->ws.getT("blur#pad", (size_t)B * 3 * (H + K - 1) * (W + K - 1), &pad));
+    return launch_blur_reflect_adjoint(e->stream, g, k, K, xa, pad, gx, B, H, W);
+}
+
+// difference = m - Tx(x_hat) (main_ddpir_deblur.py:307-311), one norm PER IMAGE (the program restores one image at a time, so utils_model.py:392 sees a
+// batch of one), gup = Tx^T difference = 0.5 R^T C^T difference.  m = (sa (ma y + mb) + s1m noise) qa + qb.
+static Status blur_residual(dpir_engine* e, const float* x_hat, const BlurResidual& meas, const float* k, int K, int B, int H, int W,
+                            float** gup_out, float** norm_out) {
+    const size_t total = (size_t)B * 3 * H * W;
+    const int per_img = 3 * blur_tiles(H, W);
+    BlurResidual r = meas;
+    float *gup = nullptr, *normv = nullptr;
+    DPIR_TRY(e->ws.getT("blur#diff", total, &r.diff));
+    DPIR_TRY(e->ws.getT("blur#part", (size_t)B * per_img, &r.part));
+    DPIR_TRY(e->ws.getT("blur#norm", (size_t)(B < 4 ? 4 : B), &normv));
+    DPIR_TRY(e->ws.getT("blur#gup", total, &gup));
+    DPIR_TRY(launch_blur_reflect(e->stream, x_hat, k, K, 0.5f, 0.5f, nullptr, B, H, W, &r));
+    DPIR_TRY(launch_norm_fold_per_image(e->stream, r.part, per_img, B, normv));
+    DPIR_TRY(blur_adjoint_impl(e, r.diff, k, K, 0.5f, gup, B, H, W));
+    *gup_out = gup; *norm_out = normv;
+    return Status{};
+}
+
+// gup = A^T (m - A(x_hat)), un-normalised, and || m - A(x_hat) || (one float, or one per image) for the operator A of `op`
+static Status grad_residual(dpir_engine* e, const GradOp& op, const float* x_hat, const BlurResidual& meas, int B, int H, int W,
+                            float** gup_out, float** norm_out) {
+    if (op.k) return blur_residual(e, x_hat, meas, op.k, op.K, B, H, W, gup_out, norm_out);
+    return dps_residual(e, x_hat, meas, op.sf, B, H, W, gup_out, norm_out);
+}
+
 // torch.autograd.grad(norm, x) with x_hat = x0 of the last p_sample_impl(x): the clamp mask, the direct c1 term and the network backward.
 // Leaves direct / dx_net in the workspace (norm_grad = direct + dx_net).
-static Status dps_grad_through_network(dpir_engine* e, const float* gup, const float* normv, float** direct_out, float** dxn_out,
-                                       bool norm_per_image = false) {
+static Status dps_grad_through_network(dpir_engine* e, const float* gup, const float* normv, float** direct_out, float** dxn_out, bool norm_per_image) {
     const int B = e->ps_B, H = e->ps_H, W = e->ps_W, oc = e->net.desc.out_channels;
     const size_t total = (size_t)B * 3 * H * W;
     float *dout6 = nullptr, *direct = nullptr, *dxn = nullptr; unsigned char* inside = nullptr;
@@ -1296,167 +1335,13 @@ int dpir_eps_from_xstart(dpir_engine* e, const float* x_dev, const float* x0_dev
     return DPIR_OK;
 }
 
-int dpir_grad_and_value(dpir_engine* e, int through_network, const float* x_hat_dev, const float* measurement_dev, int sf, float* norm_grad_out_dev,
-                        float* norm_out_dev, int B, int H, int W) {
-    if (!e || !x_hat_dev || !measurement_dev || !norm_grad_out_dev) return fail(e, invalid("dpir_grad_and_value: null argument"));
-    API_TRY(e, check_shape("dpir_grad_and_value", B, H, W, sf));
-    (void)hipSetDevice(e->device);
-    float *gup = nullptr, *normv = nullptr;
-    const size_t total = (size_t)B * 3 * H * W;
-    if (through_network) {
-        if (!e->grad_enabled) return fail(e, Status{DPIR_ERR_STATE, "grad_and_value through the denoiser needs gradient mode: dpir_enable_grad before dpir_load_unet"});
-        if (!e->tape.valid || e->tape.serial != e->ps_serial || e->ps_serial != e->fwd_serial || e->ps_x0 != x_hat_dev || e->ps_B != B || e->ps_H != H || e->ps_W != W)
-            return fail(e, Status{DPIR_ERR_STATE, "grad_and_value(x, x_hat): x_hat must be the pred_xstart output of the LAST dpir_p_sample call on this engine "
-                                                  "(the tape of that forward is what the gradient runs through)"});
-    }
-    ProfScope ps(&e->prof, PC_ELEM);
-    API_TRY(e, dps_residual(e, x_hat_dev, measurement_dev, 1.f, 0.f, 1.f, 0.f, nullptr, sf, B, H, W, &gup, &normv));
-    if (through_network) {
-        float *direct = nullptr, *dxn = nullptr;
-        API_TRY(e, dps_grad_through_network(e, gup, normv, &direct, &dxn));
-        API_TRY(e, launch_dps_update(e->stream, nullptr, direct, dxn, 0.f, nullptr, norm_grad_out_dev, total));
-    } else {
-        // norm_grad = -gup / norm: grad_step with src = 0, lam * nv / rho * tail = 1  ->  dst = 0 - ng  ... evaluated as a plain scale instead
-        API_TRY(e, launch_neg_scale_by_norm(e->stream, gup, normv, norm_grad_out_dev, total));
-    }
-    if (norm_out_dev) API_HIP(e, hipMemcpyAsync(norm_out_dev, normv, sizeof(float), hipMemcpyDeviceToDevice, e->stream));
-    return DPIR_OK;
-}
-
-int dpir_run_dps_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, const dpir_dps_coef* coefs, int n_steps,
-                      int variant, float lambda_, const float* noise_ps_dev, const float* noise_yt_dev, float step_scale, float* out_f32,
-                      uint8_t* out_u8) {
-    ProgressOneShot one_shot{e};
-    if (!e || !dd || !steps || !coefs || n_steps <= 0) return fail(e, invalid("dpir_run_dps_loop: null argument"));
-    if (variant != 0 && variant != 1) return fail(e, invalid("dpir_run_dps_loop: variant must be 0 (DPS_y0) or 1 (DPS_yt)"));
-    (void)hipSetDevice(e->device);
-    const dpir_loop_desc& d = *dd;
-    if (!e->net.loaded) return fail(e, Status{DPIR_ERR_STATE, "dpir_load_unet has not been called"});
-    if (variant == 0 && !e->grad_enabled) return fail(e, Status{DPIR_ERR_STATE, "DPS_y0 needs gradient mode: dpir_enable_grad before dpir_load_unet"});
-    if (d.task != DPIR_TASK_SR_BLUR && d.task != DPIR_TASK_SR_CUBIC)
-        return fail(e, Status{DPIR_ERR_UNSUPPORTED, "DPS_y0 is implemented for the super-resolution tasks (the reference's deblurring operator raises at "
-                                                    "main_ddpir.py:302 and its inpainting branch never defines xt)"});
-    if (d.B <= 0 || d.H <= 0 || d.W <= 0 || d.sf < 1 || d.H % d.sf || d.W % d.sf || !d.y_dev) return fail(e, invalid("dpir_run_dps_loop: bad shape"));
-    if ((e->net.desc.num_classes > 0) != (d.labels_host != nullptr)) return fail(e, invalid("labels iff class-conditional model"));
-    API_TRY(e, progress_check(e, "dpir_run_dps_loop", n_steps, d));
-    const int B = d.B, H = d.H, W = d.W, sf = d.sf, h = H / sf, w = W / sf, oc = e->net.desc.out_channels;
-    const size_t total = (size_t)B * 3 * H * W, small = (size_t)B * 3 * h * w;
-    hipStream_t s = e->stream;
-    range_clear(e);
-    LoopBufs b{};
-    float *xprev = nullptr, *diff = nullptr;
-    API_TRY(e, e->ws.getT("loop#x", total, &b.x));
-    API_TRY(e, e->ws.getT("loop#x0", total, &b.x0));
-    API_TRY(e, e->ws.getT("loop#out6", (size_t)B * oc * H * W, &b.out6));
-    API_TRY(e, e->ws.getT("loop#n2", total, &b.n2));
-    API_TRY(e, e->ws.getT("loop#init", total, &b.init_src));
-    API_TRY(e, e->ws.getT("loop#t", (size_t)B, &b.t_dev));
-    API_TRY(e, e->ws.getT("dps#xprev", total, &xprev));
-    API_TRY(e, e->ws.getT("dps#diff", small, &diff));
-    API_TRY(e, upload_ints(e, "loop#y", d.labels_host, B, &b.y_dev));
-    // init (main_ddpir.py:293-315): bicubic up-sampling of y, forward noising to t_start
-    {
-        ProfScope ps(&e->prof, PC_ELEM);
-        API_TRY(e, launch_bicubic_up(s, d.y_dev, b.init_src, B * 3, h, w, sf));
-        const float* n0 = d.noise_init_dev;
-        if (!n0) { API_TRY(e, launch_randn(s, b.n2, d.seed, 0, d.image_offset, B, (size_t)3 * H * W)); n0 = b.n2; }
-        API_TRY(e, launch_init_x(s, b.init_src, nullptr, n0, d.sa_start, d.s1m_start, b.x, total));
-    }
-    for (int i = 0; i < n_steps; ++i) {
-        API_TRY(e, progress_emit(e, i - 1, b.x, d));     // the panel of step i - 1: x after its update
-        const dpir_step& st = steps[i];
-        if (st.last && d.skip_dead_final_eval) continue;
-        std::vector<int64_t> tv(B, st.t);
-        int* t_dev = nullptr;
-        API_TRY(e, upload_ints(e, "loop#tt", tv.data(), B, &t_dev));
-        if (st.last) {                                            // the final denoiser call is dead (main_ddpir.py:384, 470)
-            API_TRY(e, unet_forward(e, b.x, t_dev, b.y_dev, b.out6, B, H, W));
-            continue;
-        }
-        const float* nz = noise_ps_dev ? noise_ps_dev + (size_t)i * total : nullptr;
-        if (!nz) { ProfScope ps(&e->prof, PC_ELEM); API_TRY(e, launch_randn(s, b.n2, d.seed, (uint64_t)4 * (i + 1), d.image_offset, B, (size_t)3 * H * W)); nz = b.n2; }
-        PSampleCoef cf{st.c1, st.c2, coefs[i].pc1, coefs[i].pc2, coefs[i].min_log, coefs[i].max_log, st.t != 0 ? 1.0f : 0.0f,
-                       d.ddim_sample, coefs[i].sa_prev, coefs[i].s1m_prev};
-        API_TRY(e, p_sample_impl(e, b.x, t_dev, b.y_dev, cf, nz, b.out6, xprev, b.x0, B, H, W));
-        ProfScope ps(&e->prof, PC_ELEM);
-        float *gup = nullptr, *normv = nullptr;
-        if (variant == 1) {
-            // DPS_yt (main_ddpir.py:439-445): the measurement is noised to level t, the residual is taken at xt = p_sample's sample and
-            // differentiated w.r.t. xt itself -- no backward through the network.  The norm is multiplied back in (:444); it is still the
-            // whole batch's (all-reduced in dps_norm when a communicator is attached), so the last bit does not depend on the sharding
-            const float* ny = noise_yt_dev ? noise_yt_dev + (size_t)i * small : nullptr;
-            if (!ny) { API_TRY(e, launch_randn(s, diff, d.seed, (uint64_t)4 * (i + 1) + 1, d.image_offset, B, (size_t)3 * h * w)); ny = diff; }
-            float* nyb = nullptr;
-            API_TRY(e, e->ws.getT("dps#ny", small, &nyb));
-            API_HIP(e, hipMemcpyAsync(nyb, ny, small * sizeof(float), hipMemcpyDeviceToDevice, s));
-            API_TRY(e, dps_residual(e, xprev, d.y_dev, 2.f, -1.f, st.sa_t, st.s1m_t, nyb, sf, B, H, W, &gup, &normv));
-            API_TRY(e, launch_grad_step(s, xprev, gup, normv, lambda_, st.tau, 0.35f, b.x, total));
-            continue;
-        }
-        // difference = (2y - 1) - Resizer(x0), norm over the whole batch (utils_model.py:391-392)
-        float *direct = nullptr, *dxn = nullptr;
-        API_TRY(e, dps_residual(e, b.x0, d.y_dev, 2.f, -1.f, 1.f, 0.f, nullptr, sf, B, H, W, &gup, &normv));
-        API_TRY(e, dps_grad_through_network(e, gup, normv, &direct, &dxn));
-        API_TRY(e, launch_dps_update(s, xprev, direct, dxn, step_scale, b.x, nullptr, total));
-    }
-    API_TRY(e, progress_emit(e, n_steps - 1, b.x, d));
-    {
-        ProfScope ps(&e->prof, PC_ELEM);
-        API_TRY(e, launch_finalize(s, b.x, out_f32, out_u8, B, H * W));
-    }
-    return DPIR_OK;
-}
-
-// ------------------------------------------------------------------------------------------ deblurring program: blur operator + gradient modes
-int dpir_blur_reflect(dpir_engine* e, const float* x_dev, const float* k_dev, int kh, int kw, float xa, float xb, float* out_dev, int B, int H, int W) {
-    if (!e || !x_dev || !k_dev || !out_dev) return fail(e, invalid("dpir_blur_reflect: null argument"));
-    API_TRY(e, blur_check("dpir_blur_reflect", kh, kw, B, H, W));
-    (void)hipSetDevice(e->device);
-    ProfScope ps(&e->prof, PC_ELEM);
-    API_TRY(e, launch_blur_reflect(e->stream, x_dev, k_dev, kh, xa, xb, out_dev, B, H, W));
-    return DPIR_OK;
-}
-
-static Status blur_adjoint_impl(dpir_engine* e, const float* g, const float* k, int K, float xa, float* gx, int B, int H, int W) {
-    float* pad = nullptr;
-    DPIR_TRY(e->ws.getT("blur#pad", (size_t)B * 3 * (H + K - 1) * (W + K - 1), &pad));
-    return launch_blur_reflect_adjoint(e->stream, g, k, K, xa, pad, gx, B, H, W);
-}
-
-int dpir_blur_reflect_adjoint(dpir_engine* e, const float* g_dev, const float* k_dev, int kh, int kw, float xa, float* gx_dev, int B, int H, int W) {
-    if (!e || !g_dev || !k_dev || !gx_dev) return fail(e, invalid("dpir_blur_reflect_adjoint: null argument"));
-    API_TRY(e, blur_check("dpir_blur_reflect_adjoint", kh, kw, B, H, W));
-    (void)hipSetDevice(e->device);
-    ProfScope ps(&e->prof, PC_ELEM);
-    API_TRY(e, blur_adjoint_impl(e, g_dev, k_dev, kh, xa, gx_dev, B, H, W));
-    return DPIR_OK;
-}
-
-// difference = m - Tx(x_hat) (main_ddpir_deblur.py:307-311), one norm PER IMAGE (the program restores one image at a time, so utils_model.py:392 sees a
-// batch of one), gup = Tx^T difference = 0.5 R^T C^T difference.  m = (sa (ma y + mb) + s1m noise) qa + qb.
-static Status blur_residual(dpir_engine* e, const float* x_hat, const BlurResidual& meas, const float* k, int K, int B, int H, int W,
-                            float** gup_out, float** norm_out) {
-    const size_t total = (size_t)B * 3 * H * W;
-    const int per_img = 3 * blur_tiles(H, W);
-    BlurResidual r = meas;
-    float *gup = nullptr, *normv = nullptr;
-    DPIR_TRY(e->ws.getT("blur#diff", total, &r.diff));
-    DPIR_TRY(e->ws.getT("blur#part", (size_t)B * per_img, &r.part));
-    DPIR_TRY(e->ws.getT("blur#norm", (size_t)(B < 4 ? 4 : B), &normv));
-    DPIR_TRY(e->ws.getT("blur#gup", total, &gup));
-    DPIR_TRY(launch_blur_reflect(e->stream, x_hat, k, K, 0.5f, 0.5f, nullptr, B, H, W, &r));
-    DPIR_TRY(launch_norm_fold_per_image(e->stream, r.part, per_img, B, normv));
-    DPIR_TRY(blur_adjoint_impl(e, r.diff, k, K, 0.5f, gup, B, H, W));
-    *gup_out = gup; *norm_out = normv;
-    return Status{};
-}
-
-int dpir_grad_and_value_blur(dpir_engine* e, int through_network, const float* x_hat_dev, const float* measurement_dev, const float* k_dev, int kh, int kw,
-                             float* norm_grad_out_dev, float* norm_out_dev, int B, int H, int W) {
-    if (!e || !x_hat_dev || !measurement_dev || !k_dev || !norm_grad_out_dev) return fail(e, invalid("dpir_grad_and_value_blur: null argument"));
-    API_TRY(e, blur_check("dpir_grad_and_value_blur", kh, kw, B, H, W));
+// utils_model.grad_and_value over the operator of `op`, the body of dpir_grad_and_value and dpir_grad_and_value_blur (their arguments are checked):
+// norm_grad_out = d norm / d x, norm_out (may be null) = the norm, one float or one per image.
+static int grad_and_value_impl(dpir_engine* e, int through_network, const float* x_hat_dev, const float* measurement_dev, const GradOp& op,
+                               float* norm_grad_out_dev, float* norm_out_dev, int B, int H, int W) {
     (void)hipSetDevice(e->device);
     const size_t total = (size_t)B * 3 * H * W;
+    const int images = op.norm_images(B);
     if (through_network) {
         if (!e->grad_enabled) return fail(e, Status{DPIR_ERR_STATE, "grad_and_value through the denoiser needs gradient mode: dpir_enable_grad before dpir_load_unet"});
         if (!e->tape.valid || e->tape.serial != e->ps_serial || e->ps_serial != e->fwd_serial || e->ps_x0 != x_hat_dev || e->ps_B != B || e->ps_H != H || e->ps_W != W)
@@ -1466,41 +1351,51 @@ int dpir_grad_and_value_blur(dpir_engine* e, int through_network, const float* x
     ProfScope ps(&e->prof, PC_ELEM);
     float *gup = nullptr, *normv = nullptr;
     BlurResidual meas; meas.y = measurement_dev;
-    API_TRY(e, blur_residual(e, x_hat_dev, meas, k_dev, kh, B, H, W, &gup, &normv));
+    API_TRY(e, grad_residual(e, op, x_hat_dev, meas, B, H, W, &gup, &normv));
     if (through_network) {
         float *direct = nullptr, *dxn = nullptr;
-        API_TRY(e, dps_grad_through_network(e, gup, normv, &direct, &dxn, true));
+        API_TRY(e, dps_grad_through_network(e, gup, normv, &direct, &dxn, images != 0));
         API_TRY(e, launch_dps_update(e->stream, nullptr, direct, dxn, 0.f, nullptr, norm_grad_out_dev, total));
     } else {
-        API_TRY(e, launch_neg_scale_by_norm(e->stream, gup, normv, norm_grad_out_dev, total, B));
+        // norm_grad = -gup / norm: grad_step with src = 0, lam * nv / rho * tail = 1  ->  dst = 0 - ng  ... evaluated as a plain scale instead
+        API_TRY(e, launch_neg_scale_by_norm(e->stream, gup, normv, norm_grad_out_dev, total, images));
     }
-    if (norm_out_dev) API_HIP(e, hipMemcpyAsync(norm_out_dev, normv, sizeof(float) * B, hipMemcpyDeviceToDevice, e->stream));
+    if (norm_out_dev) API_HIP(e, hipMemcpyAsync(norm_out_dev, normv, sizeof(float) * (images ? images : 1), hipMemcpyDeviceToDevice, e->stream));
     return DPIR_OK;
 }
 
-int dpir_run_deblur_grad_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, const dpir_dps_coef* coefs, int n_steps, int variant,
-                              float lambda_, const float* noise_ps_dev, const float* noise_yt_dev, float* out_f32, uint8_t* out_u8) {
-    ProgressOneShot one_shot{e};
-    if (!e || !dd || !steps || n_steps <= 0) return fail(e, invalid("dpir_run_deblur_grad_loop: null argument"));
-    if (variant < 0 || variant > 2) return fail(e, invalid("dpir_run_deblur_grad_loop: variant must be 0 (DPS_y0), 1 (DPS_yt) or 2 (first-order data step)"));
-    if (variant != 2 && !coefs) return fail(e, invalid("dpir_run_deblur_grad_loop: the DPS variants need the p_sample coefficients"));
-    (void)hipSetDevice(e->device);
-    const dpir_loop_desc& d = *dd;
-    if (!e->net.loaded) return fail(e, Status{DPIR_ERR_STATE, "dpir_load_unet has not been called"});
-    if (variant == 0 && !e->grad_enabled) return fail(e, Status{DPIR_ERR_STATE, "DPS_y0 needs gradient mode: dpir_enable_grad before dpir_load_unet"});
-    if (d.task != DPIR_TASK_DEBLUR || d.sf != 1) return fail(e, invalid("dpir_run_deblur_grad_loop: the deblurring program runs task deblur (sf 1) only"));
-    if (!d.y_dev || !d.k_dev) return fail(e, invalid("dpir_run_deblur_grad_loop: y and the PSF are required"));
-    API_TRY(e, blur_check("dpir_run_deblur_grad_loop", d.kh, d.kw, d.B, d.H, d.W));
+int dpir_grad_and_value(dpir_engine* e, int through_network, const float* x_hat_dev, const float* measurement_dev, int sf, float* norm_grad_out_dev,
+                        float* norm_out_dev, int B, int H, int W) {
+    if (!e || !x_hat_dev || !measurement_dev || !norm_grad_out_dev) return fail(e, invalid("dpir_grad_and_value: null argument"));
+    API_TRY(e, check_shape("dpir_grad_and_value", B, H, W, sf));
+    GradOp op; op.sf = sf;
+    return grad_and_value_impl(e, through_network, x_hat_dev, measurement_dev, op, norm_grad_out_dev, norm_out_dev, B, H, W);
+}
+
+// What both whole-loop entries of the gradient modes refuse ahead of their own task / shape checks
+static Status grad_loop_ready(dpir_engine* e, int variant) {
+    if (!e->net.loaded) return Status{DPIR_ERR_STATE, "dpir_load_unet has not been called"};
+    if (variant == 0 && !e->grad_enabled) return Status{DPIR_ERR_STATE, "DPS_y0 needs gradient mode: dpir_enable_grad before dpir_load_unet"};
+    return Status{};
+}
+
+// The loop of the gradient modes over the operator of `op`: the body of dpir_run_dps_loop (main_ddpir.py:291-470) and dpir_run_deblur_grad_loop
+// (main_ddpir_deblur.py:228-360), which have checked the task, the shape and the variants they admit.  The operator decides the image the initial
+// x is noised from (bicubic up-sampling of y | y), the measurement ((2y - 1) and sa_t (2y - 1) + s1m_t n | y and that / 2 + 0.5), the extent of
+// the y_t draw and whether the norm is the batch's or each image's.  Eager launches, no step graph.
+static int run_grad_loop(dpir_engine* e, const char* entry, const dpir_loop_desc& d, const dpir_step* steps, const dpir_dps_coef* coefs, int n_steps,
+                         int variant, float lambda_, const float* noise_ps_dev, const float* noise_yt_dev, float step_scale, const GradOp& op,
+                         float* out_f32, uint8_t* out_u8) {
     if ((e->net.desc.num_classes > 0) != (d.labels_host != nullptr)) return fail(e, invalid("labels iff class-conditional model"));
-    API_TRY(e, progress_check(e, "dpir_run_deblur_grad_loop", n_steps, d));
-    const int B = d.B, H = d.H, W = d.W, K = d.kh, oc = e->net.desc.out_channels;
-    const size_t total = (size_t)B * 3 * H * W;
+    API_TRY(e, progress_check(e, entry, n_steps, d));
+    const int B = d.B, H = d.H, W = d.W, oc = e->net.desc.out_channels, images = op.norm_images(B);
+    const size_t total = (size_t)B * 3 * H * W, small = op.measurement_count(B, H, W);
     bool with_n1 = false;
     for (int i = 0; i < n_steps; ++i) {
-        if (i > 0 && steps[i - 1].last && !steps[i].last) return fail(e, invalid("dpir_run_deblur_grad_loop: a non-final step may not follow a final step"));
+        if (i > 0 && steps[i - 1].last && !steps[i].last) return fail(e, invalid(std::string(entry) + ": a non-final step may not follow a final step"));
         if (variant == 2 && !steps[i].last && steps[i].es != 0.f) with_n1 = true;
     }
-    if (with_n1 && d.noise_n2_dev && !d.noise_n1_dev) return fail(e, invalid("dpir_run_deblur_grad_loop: eta != 0 with host noise needs noise_n1_dev"));
+    if (with_n1 && d.noise_n2_dev && !d.noise_n1_dev) return fail(e, invalid(std::string(entry) + ": eta != 0 with host noise needs noise_n1_dev"));
     hipStream_t s = e->stream;
     range_clear(e);
     LoopBufs b{};
@@ -1508,16 +1403,20 @@ int dpir_run_deblur_grad_loop(dpir_engine* e, const dpir_loop_desc* dd, const dp
     API_TRY(e, e->ws.getT("loop#x", total, &b.x));
     API_TRY(e, e->ws.getT("loop#x0", total, &b.x0));
     API_TRY(e, e->ws.getT("loop#out6", (size_t)B * oc * H * W, &b.out6));
-    API_TRY(e, e->ws.getT("loop#n1", total, &b.n1));
     API_TRY(e, e->ws.getT("loop#n2", total, &b.n2));
+    if (with_n1) API_TRY(e, e->ws.getT("loop#n1", total, &b.n1));
+    if (!op.k) API_TRY(e, e->ws.getT("loop#init", total, &b.init_src));
     API_TRY(e, e->ws.getT("dps#xprev", total, &xprev));
     API_TRY(e, upload_ints(e, "loop#y", d.labels_host, B, &b.y_dev));
-    // init (main_ddpir_deblur.py:228-231): y noised from its own level t_y up to t_start; the two coefficients come from the host
+    // init: the Resizer noises the bicubic up-sampling of y to t_start (main_ddpir.py:293-315); the deblurring program noises y itself from its own
+    // level t_y up to t_start (main_ddpir_deblur.py:228-231).  The two coefficients come from the host either way
     {
         ProfScope ps(&e->prof, PC_ELEM);
+        const float* src = d.y_dev;
+        if (!op.k) { API_TRY(e, launch_bicubic_up(s, d.y_dev, b.init_src, B * 3, H / op.sf, W / op.sf, op.sf)); src = b.init_src; }
         const float* n0 = d.noise_init_dev;
         if (!n0) { API_TRY(e, launch_randn(s, b.n2, d.seed, 0, d.image_offset, B, (size_t)3 * H * W)); n0 = b.n2; }
-        API_TRY(e, launch_init_x(s, d.y_dev, nullptr, n0, d.sa_start, d.s1m_start, b.x, total));
+        API_TRY(e, launch_init_x(s, src, nullptr, n0, d.sa_start, d.s1m_start, b.x, total));
     }
     for (int i = 0; i < n_steps; ++i) {
         API_TRY(e, progress_emit(e, i - 1, b.x, d));     // the panel of step i - 1: x after its update
@@ -1526,19 +1425,20 @@ int dpir_run_deblur_grad_loop(dpir_engine* e, const dpir_loop_desc* dd, const dp
         std::vector<int64_t> tv(B, st.t);
         int* t_dev = nullptr;
         API_TRY(e, upload_ints(e, "loop#tt", tv.data(), B, &t_dev));
-        if (st.last) {                                            // the final denoiser call is dead (main_ddpir_deblur.py:284, 339, 360)
+        if (st.last) {                                            // the final denoiser call is dead (main_ddpir.py:384, 470; main_ddpir_deblur.py:284, 339, 360)
             API_TRY(e, unet_forward(e, b.x, t_dev, b.y_dev, b.out6, B, H, W));
             continue;
         }
         float *gup = nullptr, *normv = nullptr;
-        BlurResidual meas; meas.y = d.y_dev;                      // measurement = y (:312, :324)
+        BlurResidual meas; meas.y = d.y_dev;                      // Tx is measured against y in [0, 1] (main_ddpir_deblur.py:312, 324) ...
+        if (!op.k) { meas.ma = 2.f; meas.mb = -1.f; }             // ... the Resizer against 2y - 1 (utils_model.py:391-392)
         if (variant == 2) {
-            // first-order data step (:305-314) in place of the closed-form prox, then the usual re-noise (:339-347)
+            // first-order data step (main_ddpir_deblur.py:305-314) in place of the closed-form prox, then the usual re-noise (:339-347)
             API_TRY(e, unet_forward(e, b.x, t_dev, b.y_dev, b.out6, B, H, W, nullptr, nullptr, true));
             ProfScope ps(&e->prof, PC_ELEM);
             API_TRY(e, launch_xstart(s, b.x, b.out6, oc, st.c1, st.c2, b.x0, B, H * W));
-            API_TRY(e, blur_residual(e, b.x0, meas, d.k_dev, K, B, H, W, &gup, &normv));
-            API_TRY(e, launch_grad_step(s, b.x0, gup, normv, 1.f, st.tau, 1.f, b.x0, total, nullptr, B));
+            API_TRY(e, grad_residual(e, op, b.x0, meas, B, H, W, &gup, &normv));
+            API_TRY(e, launch_grad_step(s, b.x0, gup, normv, 1.f, st.tau, 1.f, b.x0, total, nullptr, images));
             const float *n1 = nullptr, *n2 = nullptr;
             if (st.es != 0.f) {
                 if (d.noise_n1_dev) n1 = d.noise_n1_dev + (size_t)i * total;
@@ -1556,19 +1456,27 @@ int dpir_run_deblur_grad_loop(dpir_engine* e, const dpir_loop_desc* dd, const dp
         API_TRY(e, p_sample_impl(e, b.x, t_dev, b.y_dev, cf, nz, b.out6, xprev, b.x0, B, H, W));
         ProfScope ps(&e->prof, PC_ELEM);
         if (variant == 1) {
-            // DPS_yt (:329-336): y_t = sa_t (2y - 1) + s1m_t n, measured as y_t / 2 + 0.5 against Tx(xt), differentiated w.r.t. xt itself
-            const float* ny = noise_yt_dev ? noise_yt_dev + (size_t)i * total : nullptr;
-            if (!ny) { API_TRY(e, launch_randn(s, b.n1, d.seed, (uint64_t)4 * (i + 1) + 1, d.image_offset, B, (size_t)3 * H * W)); ny = b.n1; }
-            meas.ma = 2.f; meas.mb = -1.f; meas.sa = st.sa_t; meas.s1m = st.s1m_t; meas.noise = ny; meas.qa = 0.5f; meas.qb = 0.5f;
-            API_TRY(e, blur_residual(e, xprev, meas, d.k_dev, K, B, H, W, &gup, &normv));
-            API_TRY(e, launch_grad_step(s, xprev, gup, normv, lambda_, st.tau, 0.35f, b.x, total, nullptr, B));
+            // DPS_yt (main_ddpir.py:439-445, main_ddpir_deblur.py:329-336): y_t = sa_t (2y - 1) + s1m_t n, which Tx measures as y_t / 2 + 0.5; the
+            // residual is taken at xt = p_sample's sample and differentiated w.r.t. xt itself -- no backward through the network.  The norm is
+            // multiplied back in (:444); the Resizer's is still the whole batch's (all-reduced in dps_norm), so no bit depends on the sharding
+            const float* ny = noise_yt_dev ? noise_yt_dev + (size_t)i * small : nullptr;
+            if (!ny) {
+                float* nyb = nullptr;
+                API_TRY(e, e->ws.getT("dps#ny", small, &nyb));
+                API_TRY(e, launch_randn(s, nyb, d.seed, (uint64_t)4 * (i + 1) + 1, d.image_offset, B, small / B));
+                ny = nyb;
+            }
+            meas.ma = 2.f; meas.mb = -1.f; meas.sa = st.sa_t; meas.s1m = st.s1m_t; meas.noise = ny;
+            if (op.k) meas.qa = meas.qb = 0.5f;
+            API_TRY(e, grad_residual(e, op, xprev, meas, B, H, W, &gup, &normv));
+            API_TRY(e, launch_grad_step(s, xprev, gup, normv, lambda_, st.tau, 0.35f, b.x, total, nullptr, images));
             continue;
         }
-        // DPS_y0 (:323-327): x = xt - d || y - Tx(x0) || / d x, through the clamp and the denoiser, unit step
+        // DPS_y0 (main_ddpir.py:434-438, main_ddpir_deblur.py:323-327): x = xt - step_scale d || m - A(x0) || / d x, through the clamp and the denoiser
         float *direct = nullptr, *dxn = nullptr;
-        API_TRY(e, blur_residual(e, b.x0, meas, d.k_dev, K, B, H, W, &gup, &normv));
-        API_TRY(e, dps_grad_through_network(e, gup, normv, &direct, &dxn, true));
-        API_TRY(e, launch_dps_update(s, xprev, direct, dxn, 1.f, b.x, nullptr, total));
+        API_TRY(e, grad_residual(e, op, b.x0, meas, B, H, W, &gup, &normv));
+        API_TRY(e, dps_grad_through_network(e, gup, normv, &direct, &dxn, images != 0));
+        API_TRY(e, launch_dps_update(s, xprev, direct, dxn, step_scale, b.x, nullptr, total));
     }
     API_TRY(e, progress_emit(e, n_steps - 1, b.x, d));
     {
@@ -1576,6 +1484,67 @@ int dpir_run_deblur_grad_loop(dpir_engine* e, const dpir_loop_desc* dd, const dp
         API_TRY(e, launch_finalize(s, b.x, out_f32, out_u8, B, H * W));
     }
     return DPIR_OK;
+}
+
+int dpir_run_dps_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, const dpir_dps_coef* coefs, int n_steps,
+                      int variant, float lambda_, const float* noise_ps_dev, const float* noise_yt_dev, float step_scale, float* out_f32,
+                      uint8_t* out_u8) {
+    ProgressOneShot one_shot{e};
+    if (!e || !dd || !steps || !coefs || n_steps <= 0) return fail(e, invalid("dpir_run_dps_loop: null argument"));
+    if (variant != 0 && variant != 1) return fail(e, invalid("dpir_run_dps_loop: variant must be 0 (DPS_y0) or 1 (DPS_yt)"));
+    (void)hipSetDevice(e->device);
+    const dpir_loop_desc& d = *dd;
+    API_TRY(e, grad_loop_ready(e, variant));
+    if (d.task != DPIR_TASK_SR_BLUR && d.task != DPIR_TASK_SR_CUBIC)
+        return fail(e, Status{DPIR_ERR_UNSUPPORTED, "DPS_y0 is implemented for the super-resolution tasks (the reference's deblurring operator raises at "
+                                                    "main_ddpir.py:302 and its inpainting branch never defines xt)"});
+    if (d.B <= 0 || d.H <= 0 || d.W <= 0 || d.sf < 1 || d.H % d.sf || d.W % d.sf || !d.y_dev) return fail(e, invalid("dpir_run_dps_loop: bad shape"));
+    GradOp op; op.sf = d.sf;
+    return run_grad_loop(e, "dpir_run_dps_loop", d, steps, coefs, n_steps, variant, lambda_, noise_ps_dev, noise_yt_dev, step_scale, op, out_f32, out_u8);
+}
+
+// ------------------------------------------------------------------------------------------ deblurring program: blur operator + gradient modes
+int dpir_blur_reflect(dpir_engine* e, const float* x_dev, const float* k_dev, int kh, int kw, float xa, float xb, float* out_dev, int B, int H, int W) {
+    if (!e || !x_dev || !k_dev || !out_dev) return fail(e, invalid("dpir_blur_reflect: null argument"));
+    API_TRY(e, blur_check("dpir_blur_reflect", kh, kw, B, H, W));
+    (void)hipSetDevice(e->device);
+    ProfScope ps(&e->prof, PC_ELEM);
+    API_TRY(e, launch_blur_reflect(e->stream, x_dev, k_dev, kh, xa, xb, out_dev, B, H, W));
+    return DPIR_OK;
+}
+
+int dpir_blur_reflect_adjoint(dpir_engine* e, const float* g_dev, const float* k_dev, int kh, int kw, float xa, float* gx_dev, int B, int H, int W) {
+    if (!e || !g_dev || !k_dev || !gx_dev) return fail(e, invalid("dpir_blur_reflect_adjoint: null argument"));
+    API_TRY(e, blur_check("dpir_blur_reflect_adjoint", kh, kw, B, H, W));
+    (void)hipSetDevice(e->device);
+    ProfScope ps(&e->prof, PC_ELEM);
+    API_TRY(e, blur_adjoint_impl(e, g_dev, k_dev, kh, xa, gx_dev, B, H, W));
+    return DPIR_OK;
+}
+
+int dpir_grad_and_value_blur(dpir_engine* e, int through_network, const float* x_hat_dev, const float* measurement_dev, const float* k_dev, int kh, int kw,
+                             float* norm_grad_out_dev, float* norm_out_dev, int B, int H, int W) {
+    if (!e || !x_hat_dev || !measurement_dev || !k_dev || !norm_grad_out_dev) return fail(e, invalid("dpir_grad_and_value_blur: null argument"));
+    API_TRY(e, blur_check("dpir_grad_and_value_blur", kh, kw, B, H, W));
+    GradOp op; op.k = k_dev; op.K = kh;
+    return grad_and_value_impl(e, through_network, x_hat_dev, measurement_dev, op, norm_grad_out_dev, norm_out_dev, B, H, W);
+}
+
+int dpir_run_deblur_grad_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, const dpir_dps_coef* coefs, int n_steps, int variant,
+                              float lambda_, const float* noise_ps_dev, const float* noise_yt_dev, float* out_f32, uint8_t* out_u8) {
+    ProgressOneShot one_shot{e};
+    if (!e || !dd || !steps || n_steps <= 0) return fail(e, invalid("dpir_run_deblur_grad_loop: null argument"));
+    if (variant < 0 || variant > 2) return fail(e, invalid("dpir_run_deblur_grad_loop: variant must be 0 (DPS_y0), 1 (DPS_yt) or 2 (first-order data step)"));
+    if (variant != 2 && !coefs) return fail(e, invalid("dpir_run_deblur_grad_loop: the DPS variants need the p_sample coefficients"));
+    (void)hipSetDevice(e->device);
+    const dpir_loop_desc& d = *dd;
+    API_TRY(e, grad_loop_ready(e, variant));
+    if (d.task != DPIR_TASK_DEBLUR || d.sf != 1) return fail(e, invalid("dpir_run_deblur_grad_loop: the deblurring program runs task deblur (sf 1) only"));
+    if (!d.y_dev || !d.k_dev) return fail(e, invalid("dpir_run_deblur_grad_loop: y and the PSF are required"));
+    API_TRY(e, blur_check("dpir_run_deblur_grad_loop", d.kh, d.kw, d.B, d.H, d.W));
+    GradOp op; op.k = d.k_dev; op.K = d.kh;
+    // the program's DPS_y0 update is a unit step (main_ddpir_deblur.py:326)
+    return run_grad_loop(e, "dpir_run_deblur_grad_loop", d, steps, coefs, n_steps, variant, lambda_, noise_ps_dev, noise_yt_dev, 1.f, op, out_f32, out_u8);
 }
 
 // ------------------------------------------------------------------------------------------ profiling

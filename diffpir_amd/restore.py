@@ -16,7 +16,7 @@ draw index), which makes results independent of how a batch is sharded across GP
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Callable, Optional
 
 import numpy as np
@@ -350,6 +350,68 @@ def draw_host_noise(noise_fn: Callable, steps, shape, need_n1: bool, repaint: bo
     return (init, n1, n2, nrp) if repaint else (init, n1, n2)
 
 
+def _dev(engine, a, dtype, keep: list):
+    """a as a device array (a numpy array is uploaded), held in `keep` so that it outlives the asynchronous call; None stays None."""
+    if a is None:
+        return None
+    if isinstance(a, np.ndarray):
+        a = engine.to_device(a, dtype)
+    keep.append(a)
+    return a
+
+
+def _loop_desc(cfg: LoopConfig, B, H, W, sf, start, y, k=None, mask=None, labels=None, seed=0, image_offset=0, use_graph=False,
+               skip_dead_final_eval=False):
+    """(_lib.LoopDesc without its noise pointers, the int64 label array or None) for every whole-loop entry.  start: (sa, s1m) of the initial x.
+    The descriptor holds only the ADDRESS of the labels: the caller keeps the returned array until the engine call has returned."""
+    d = _lib.LoopDesc()
+    d.task = cfg.engine_task()
+    d.B, d.H, d.W, d.sf = B, H, W, sf
+    if k is not None:
+        d.kh, d.kw = k.shape[2], k.shape[3]
+    d.in_iter, d.gamma, d.guidance = cfg.inIter, cfg.gamma, cfg.guidance_scale
+    d.sa_start, d.s1m_start = [float(v) for v in start]
+    d.y_dev, d.k_dev, d.mask_dev = _ptr(y), _ptr(k), _ptr(mask)
+    lab = None
+    if labels is not None:
+        lab = np.ascontiguousarray(labels, dtype=np.int64)
+        d.labels_host = lab.ctypes.data
+    d.seed, d.image_offset = seed, image_offset
+    d.use_graph, d.skip_dead_final_eval = int(use_graph), int(skip_dead_final_eval)
+    d.generate_mode = GENERATE_MODES[cfg.generate_mode]
+    d.first_order = 0 if cfg.sub_1_analytic else 1
+    # config.ddim_sample reaches model_fn(..., 'pred_x_prev_and_start') (main_ddpir.py:371-373): only the gradient-mode loops read it
+    d.ddim_sample = 1 if cfg.ddim_sample else 0
+    return d, lab
+
+
+def _host_noise(noise_source, noise_fn, predrawn=None) -> bool:
+    """Whether the call feeds host noise; a host-noise call must bring noise_fn or draws made ahead."""
+    if noise_source == "host":
+        if predrawn is None and noise_fn is None:
+            raise EngineError("noise_source='host' needs noise_fn")
+        return True
+    if noise_source != "device":
+        raise ValueError("noise_source must be 'host' or 'device'")
+    return False
+
+
+def _outputs(engine, B, H, W, out_f32, out_u8, return_u8):
+    if out_f32 is None:
+        out_f32 = engine.empty((B, 3, H, W))
+    if out_u8 is None and return_u8:
+        out_u8 = engine.empty((B, H, W, 3), np.uint8)
+    return out_f32, out_u8
+
+
+def _call_loop(engine, progress, cfg, entries, B, H, W, has_mask, call):
+    """One whole-loop engine call with the progress request, if any, armed before it and downloaded after it."""
+    armed = _arm(engine, progress, cfg, entries, B, H, W, has_mask)
+    engine._check(call())
+    if armed:
+        armed.finish()
+
+
 def restore_batch(engine: Engine, cfg: LoopConfig, y, k=None, mask=None, labels=None, noise_source="device",
                   noise_fn: Optional[Callable] = None, seed: int = 0, image_offset: int = 0, use_graph: bool = False,
                   skip_dead_final_eval: bool = False, out_f32=None, out_u8=None, return_u8: bool = False, _cache: dict = None,
@@ -368,24 +430,15 @@ def restore_batch(engine: Engine, cfg: LoopConfig, y, k=None, mask=None, labels=
     if cfg.driver == "main_ddpir_deblur" and (cfg.generate_mode != "DiffPIR" or not cfg.sub_1_analytic):
         if predrawn is not None or mask is not None or use_graph:
             raise NotImplementedError("the deblurring program's gradient modes take host noise through noise_fn, no mask and no step graph")
-        return _restore_deblur_grad(engine, cfg, y, k, labels, noise_source, noise_fn, seed, image_offset, skip_dead_final_eval, out_f32, out_u8, return_u8,
-                                    progress=progress)
+        return _restore_grad(engine, cfg, y, k, labels, noise_source, noise_fn, seed, image_offset, skip_dead_final_eval, out_f32, out_u8, return_u8,
+                             progress=progress)
     if cfg.generate_mode in ("DPS_y0", "DPS_yt"):
         if predrawn is not None or mask is not None:
             raise NotImplementedError("DPS modes take host noise through noise_fn (their draw order differs from the DiffPIR loop's) and no mask")
-        return _restore_dps(engine, cfg, y, labels, noise_source, noise_fn, seed, image_offset, skip_dead_final_eval, out_f32, out_u8, return_u8,
-                            progress=progress)
+        return _restore_grad(engine, cfg, y, None, labels, noise_source, noise_fn, seed, image_offset, skip_dead_final_eval, out_f32, out_u8, return_u8,
+                             progress=progress)
     keep = []
-
-    def dev(a, dtype):
-        if a is None:
-            return None
-        if isinstance(a, np.ndarray):
-            d = engine.to_device(a, dtype)
-            keep.append(d)
-            return d
-        return a
-    y = dev(y, np.float32); k = dev(k, np.float32); mask = dev(mask, np.uint8)
+    y = _dev(engine, y, np.float32, keep); k = _dev(engine, k, np.float32, keep); mask = _dev(engine, mask, np.uint8, keep)
     B, _, h, w = y.shape
     table = index = None
     if per_image is not None:
@@ -398,57 +451,23 @@ def restore_batch(engine: Engine, cfg: LoopConfig, y, k=None, mask=None, labels=
     if table is None:
         dt, steps, arr = _steps(cfg)
     H, W = h * cfg.sf, w * cfg.sf
-    d = _lib.LoopDesc()
-    d.task = cfg.engine_task()
-    d.B, d.H, d.W, d.sf = B, H, W, cfg.sf
-    if k is not None:
-        d.kh, d.kw = k.shape[2], k.shape[3]
-    d.in_iter, d.gamma, d.guidance = cfg.inIter, cfg.gamma, cfg.guidance_scale
-    d.sa_start, d.s1m_start = [float(v) for v in start_coefficients(cfg, dt)]
-    d.y_dev, d.k_dev, d.mask_dev = _ptr(y), _ptr(k), _ptr(mask)
-    lab = None
-    if labels is not None:
-        lab = np.ascontiguousarray(labels, dtype=np.int64)
-        d.labels_host = lab.ctypes.data
-    if noise_source == "host":
+    d, lab = _loop_desc(cfg, B, H, W, cfg.sf, start_coefficients(cfg, dt), y, k, mask, labels, seed, image_offset, use_graph, skip_dead_final_eval)
+    if _host_noise(noise_source, noise_fn, predrawn):
         rp = cfg.generate_mode == "repaint"
-        if predrawn is not None:                 # (init, n1, n2[, nrp]) already drawn in the reference's order (sharded runs)
-            drawn = predrawn
-        elif noise_fn is None:
-            raise EngineError("noise_source='host' needs noise_fn")
-        else:
-            drawn = draw_host_noise(noise_fn, steps, (B, 3, H, W), cfg.eta != 0, repaint=rp)
+        # predrawn: (init, n1, n2[, nrp]) already drawn in the reference's order (sharded runs)
+        drawn = predrawn if predrawn is not None else draw_host_noise(noise_fn, steps, (B, 3, H, W), cfg.eta != 0, repaint=rp)
         init, n1, n2 = drawn[:3]
-        if rp:
-            drp = engine.to_device(drawn[3])
-            keep.append(drp)
-            d.noise_rp_dev = drp.ptr
-        di, d2 = engine.to_device(init), engine.to_device(n2)
-        keep += [di, d2]
-        d.noise_init_dev, d.noise_n2_dev = di.ptr, d2.ptr
-        if n1 is not None:
-            d1 = engine.to_device(n1)
-            keep.append(d1)
-            d.noise_n1_dev = d1.ptr
-    elif noise_source != "device":
-        raise ValueError("noise_source must be 'host' or 'device'")
-    d.seed, d.image_offset = seed, image_offset
-    d.use_graph, d.skip_dead_final_eval = int(use_graph), int(skip_dead_final_eval)
-    d.generate_mode = GENERATE_MODES[cfg.generate_mode]
-    d.first_order = 0 if cfg.sub_1_analytic else 1
-    if out_f32 is None:
-        out_f32 = engine.empty((B, 3, H, W))
-    if out_u8 is None and return_u8:
-        out_u8 = engine.empty((B, H, W, 3), np.uint8)
-    armed = _arm(engine, progress, cfg, steps, B, H, W, mask is not None)
+        d.noise_rp_dev = _ptr(_dev(engine, drawn[3] if rp else None, None, keep))
+        d.noise_init_dev, d.noise_n2_dev = _dev(engine, init, None, keep).ptr, _dev(engine, n2, None, keep).ptr
+        d.noise_n1_dev = _ptr(_dev(engine, n1, None, keep))
+    out_f32, out_u8 = _outputs(engine, B, H, W, out_f32, out_u8, return_u8)
     if table is None and index is None:
-        engine._check(engine.lib.dpir_run_loop(engine.h, C.byref(d), arr, len(steps), _ptr(out_f32), _ptr(out_u8)))
+        call = lambda: engine.lib.dpir_run_loop(engine.h, C.byref(d), arr, len(steps), _ptr(out_f32), _ptr(out_u8))
     else:
-        engine._check(engine.lib.dpir_run_loop_per_image(
+        call = lambda: engine.lib.dpir_run_loop_per_image(
             engine.h, C.byref(d), arr, len(steps), None if table is None else table.ctypes.data_as(C.POINTER(_lib.ImageStep)),
-            None if index is None else index.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(out_f32), _ptr(out_u8)))
-    if armed:
-        armed.finish()
+            None if index is None else index.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(out_f32), _ptr(out_u8))
+    _call_loop(engine, progress, cfg, steps, B, H, W, mask is not None, call)
     if _cache is not None:
         _cache["keep"] = keep
     else:
@@ -524,47 +543,20 @@ def _restore_inpaint_resample(engine, cfg, y, mask, labels, noise_source, noise_
         raise EngineError("inpainting needs a mask")
     dt, rows, arr = _inpaint_rows(cfg)
     keep = []
-
-    def dev(a, dtype=np.float32):
-        if a is None:
-            return None
-        if isinstance(a, np.ndarray):
-            a = engine.to_device(a, dtype)
-        keep.append(a)
-        return a
-    y, mask = dev(y), dev(mask, np.uint8)
+    y, mask = _dev(engine, y, np.float32, keep), _dev(engine, mask, np.uint8, keep)
     B, _, H, W = y.shape
-    d = _lib.LoopDesc()
-    d.task, d.B, d.H, d.W, d.sf = TASKS["inpaint"], B, H, W, 1
-    d.guidance = cfg.guidance_scale
-    d.sa_start, d.s1m_start = [float(v) for v in (start_coefficients(cfg, dt) if _start is None else _start)]
-    d.y_dev, d.mask_dev = _ptr(y), _ptr(mask)
-    lab = None
-    if labels is not None:
-        lab = np.ascontiguousarray(labels, dtype=np.int64)
-        d.labels_host = lab.ctypes.data
+    d, lab = _loop_desc(cfg, B, H, W, 1, start_coefficients(cfg, dt) if _start is None else _start, y, None, mask, labels, seed, image_offset,
+                        use_graph, skip_dead_final_eval)
     nback = None
-    if noise_source == "host":
+    if _host_noise(noise_source, noise_fn, predrawn):
         if predrawn is None:
-            if noise_fn is None:
-                raise EngineError("noise_source='host' needs noise_fn")
             predrawn = draw_inpaint_host_noise(noise_fn, cfg, rows, B, H, W)
-        dn = {k_: dev(v) for k_, v in predrawn.items()}
+        dn = {k_: _dev(engine, v, np.float32, keep) for k_, v in predrawn.items()}
         d.noise_init_dev, d.noise_n1_dev, d.noise_n2_dev, d.noise_rp_dev = _ptr(dn["init"]), _ptr(dn["n1"]), _ptr(dn["n2"]), _ptr(dn["rp"])
         nback = dn["back"]
-    elif noise_source != "device":
-        raise ValueError("noise_source must be 'host' or 'device'")
-    d.seed, d.image_offset = seed, image_offset
-    d.use_graph, d.skip_dead_final_eval = int(use_graph), int(skip_dead_final_eval)
-    d.generate_mode = GENERATE_MODES[cfg.generate_mode]
-    if out_f32 is None:
-        out_f32 = engine.empty((B, 3, H, W))
-    if out_u8 is None and return_u8:
-        out_u8 = engine.empty((B, H, W, 3), np.uint8)
-    armed = _arm(engine, progress, cfg, rows, B, H, W, True)
-    engine._check(engine.lib.dpir_run_inpaint_loop(engine.h, C.byref(d), arr, len(rows), _ptr(nback), _ptr(out_f32), _ptr(out_u8)))
-    if armed:
-        armed.finish()
+    out_f32, out_u8 = _outputs(engine, B, H, W, out_f32, out_u8, return_u8)
+    _call_loop(engine, progress, cfg, rows, B, H, W, True,
+               lambda: engine.lib.dpir_run_inpaint_loop(engine.h, C.byref(d), arr, len(rows), _ptr(nback), _ptr(out_f32), _ptr(out_u8)))
     if _cache is not None:
         _cache["keep"] = keep
     else:
@@ -572,15 +564,33 @@ def _restore_inpaint_resample(engine, cfg, y, mask, labels, noise_source, noise_
     return (out_f32, out_u8) if return_u8 else out_f32
 
 
-def _restore_deblur_grad(engine, cfg, y, k, labels, noise_source, noise_fn, seed, image_offset, skip_dead_final_eval, out_f32, out_u8, return_u8,
-                         progress=None):
-    """driver 'main_ddpir_deblur', generate_mode DPS_y0 / DPS_yt / DiffPIR with sub_1_analytic false: dpir_run_deblur_grad_loop.  Host noise is
-    drawn batch-shaped in the loop's order (dps_host_noise_shapes); image n uses slice n."""
+def draw_grad_host_noise(noise_fn: Callable, cfg: LoopConfig, steps, B: int, H: int, W: int):
+    """Host noise of the gradient-mode loops, consumed in the order of dps_host_noise_shapes; image n uses slice n of every batch-shaped draw.
+    DPS_y0 / DPS_yt: dict(init [B,3,H,W], ps [n_steps,B,3,H,W], yt [n_steps,B,3,H/sf,W/sf] (DPS_yt; zeros where a step has no y_t draw) or None);
+    the first-order data step of the deblurring program: dict(init, n1, n2) of draw_host_noise (no re-noising in the DPS modes, main_ddpir.py:448)."""
+    if cfg.generate_mode == "DiffPIR":
+        init, n1, n2 = draw_host_noise(noise_fn, steps, (B, 3, H, W), cfg.eta != 0)
+        return dict(init=init, n2=n2, n1=n1)
+    shapes = iter(dps_host_noise_shapes(cfg, steps, B, H, W))
+    draw = lambda: np.asarray(noise_fn(next(shapes)), dtype=np.float32)
+    yt_mode = cfg.generate_mode == "DPS_yt"
+    init, ps, yt = draw(), [], []
+    for st in steps:
+        ps.append(draw())
+        yt.append(draw() if yt_mode and not st["last"] else np.zeros((B, 3, H // cfg.sf, W // cfg.sf), np.float32))
+    return dict(init=init, ps=np.stack(ps), yt=np.stack(yt) if yt_mode else None)
+
+
+def _restore_grad(engine, cfg, y, k, labels, noise_source, noise_fn, seed, image_offset, skip_dead_final_eval, out_f32, out_u8, return_u8, progress=None):
+    """The gradient modes: generate_mode DPS_y0 / DPS_yt of driver 'main_ddpir' (task sr; main_ddpir.py:370-373, 433-445: dpir_run_dps_loop over
+    the Resizer) and DPS_y0 / DPS_yt / DiffPIR with sub_1_analytic false of driver 'main_ddpir_deblur' (dpir_run_deblur_grad_loop over the
+    reflect-padded blur, k [B,1,K,K]).  One loop body in the engine; the driver picks the entry and the initialisation (start_coefficients)."""
     from .schedule import DiffusionTables
+    deblur = cfg.driver == "main_ddpir_deblur"
     variant = {"DPS_y0": 0, "DPS_yt": 1, "DiffPIR": 2}[cfg.generate_mode]
     if variant == 0 and not engine.grad:
         raise EngineError("generate_mode DPS_y0 needs Engine.enable_grad() before the model is loaded")
-    if k is None:
+    if deblur and k is None:
         raise EngineError("the deblurring program needs the PSFs k [B,1,K,K]")
     dt, steps, arr = _steps(cfg)
     dtab = DiffusionTables.make(cfg.num_train_timesteps)
@@ -588,122 +598,26 @@ def _restore_deblur_grad(engine, cfg, y, k, labels, noise_source, noise_fn, seed
     for i, st in enumerate(steps):
         coefs[i].pc1, coefs[i].pc2, coefs[i].min_log, coefs[i].max_log = [float(v) for v in dtab.dps_coef(st["t"])]
         coefs[i].sa_prev, coefs[i].s1m_prev = [float(v) for v in dtab.ddim_coef(st["t"])]
-    yd = engine.to_device(y, np.float32) if isinstance(y, np.ndarray) else y
-    kd = engine.to_device(k, np.float32) if isinstance(k, np.ndarray) else k
-    B, _, H, W = yd.shape
-    shape = (B, 3, H, W)
-    d = _lib.LoopDesc()
-    d.task, d.B, d.H, d.W, d.sf = TASKS["deblur"], B, H, W, 1
-    d.kh, d.kw = kd.shape[2], kd.shape[3]
-    d.sa_start, d.s1m_start = [float(v) for v in start_coefficients(cfg, dt)]
-    d.y_dev, d.k_dev = _ptr(yd), _ptr(kd)
-    lab = None
-    if labels is not None:
-        lab = np.ascontiguousarray(labels, dtype=np.int64)
-        d.labels_host = lab.ctypes.data
-    keep = [yd, kd]
-    nps = nyt = None
-    if noise_source == "host":
-        if noise_fn is None:
-            raise EngineError("noise_source='host' needs noise_fn")
-        if variant == 2:
-            init, n1, n2 = draw_host_noise(noise_fn, steps, shape, cfg.eta != 0)
-            keep += [engine.to_device(init), engine.to_device(n2)]
-            d.noise_init_dev, d.noise_n2_dev = keep[-2].ptr, keep[-1].ptr
-            if n1 is not None:
-                keep.append(engine.to_device(n1))
-                d.noise_n1_dev = keep[-1].ptr
-        else:
-            init = np.asarray(noise_fn(shape), dtype=np.float32)
-            ps, yt = [], []
-            for st in steps:
-                ps.append(np.asarray(noise_fn(shape), dtype=np.float32))
-                yt.append(np.asarray(noise_fn(shape), dtype=np.float32) if variant == 1 and not st["last"] else None)
-            di, nps = engine.to_device(init), engine.to_device(np.stack(ps))
-            keep += [di, nps]
-            if variant == 1:
-                nyt = engine.to_device(np.stack([np.zeros(shape, np.float32) if a is None else a for a in yt]))
-                keep.append(nyt)
-            d.noise_init_dev = di.ptr
-    elif noise_source != "device":
-        raise ValueError("noise_source must be 'host' or 'device'")
-    d.seed, d.image_offset = seed, image_offset
-    d.skip_dead_final_eval = int(skip_dead_final_eval)
-    d.generate_mode = GENERATE_MODES[cfg.generate_mode]
-    d.first_order = 1 if variant == 2 else 0
-    d.ddim_sample = 1 if cfg.ddim_sample else 0
-    if out_f32 is None:
-        out_f32 = engine.empty(shape)
-    if out_u8 is None and return_u8:
-        out_u8 = engine.empty((B, H, W, 3), np.uint8)
-    armed = _arm(engine, progress, cfg, steps, B, H, W, False)
-    engine._check(engine.lib.dpir_run_deblur_grad_loop(engine.h, C.byref(d), arr, coefs, len(steps), variant, float(cfg.lambda_),
-                                                       _ptr(nps), _ptr(nyt), _ptr(out_f32), _ptr(out_u8)))
-    engine.sync()
-    if armed:
-        armed.finish()
-    return (out_f32, out_u8) if return_u8 else out_f32
-
-
-def _restore_dps(engine, cfg, y, labels, noise_source, noise_fn, seed, image_offset, skip_dead_final_eval, out_f32, out_u8, return_u8, progress=None):
-    """generate_mode 'DPS_y0' / 'DPS_yt' (main_ddpir.py:370-373, 433-445): dpir_run_dps_loop.  Host noise order: init, then per step the
-    p_sample draw and (DPS_yt, non-final steps) the y_t draw; there is no re-noising in these modes (main_ddpir.py:448)."""
-    from .schedule import DiffusionTables
-    yt_mode = cfg.generate_mode == "DPS_yt"
-    if not yt_mode and not engine.grad:
-        raise EngineError("generate_mode DPS_y0 needs Engine.enable_grad() before the model is loaded")
-    dt, steps, arr = _steps(cfg)
-    dtab = DiffusionTables.make(cfg.num_train_timesteps)
-    coefs = (_lib.DpsCoef * len(steps))()
-    for i, st in enumerate(steps):
-        coefs[i].pc1, coefs[i].pc2, coefs[i].min_log, coefs[i].max_log = [float(v) for v in dtab.dps_coef(st["t"])]
-        coefs[i].sa_prev, coefs[i].s1m_prev = [float(v) for v in dtab.ddim_coef(st["t"])]
-    yd = engine.to_device(y, np.float32) if isinstance(y, np.ndarray) else y
-    B, _, h, w = yd.shape
+    if deblur and cfg.sf != 1:
+        cfg = replace(cfg, sf=1)                    # the deblurring program has no scale factor: the key is ignored
+    keep = []
+    y, k = _dev(engine, y, np.float32, keep), _dev(engine, k, np.float32, keep)
+    B, _, h, w = y.shape
     H, W = h * cfg.sf, w * cfg.sf
-    d = _lib.LoopDesc()
-    d.task = cfg.engine_task()
-    d.B, d.H, d.W, d.sf = B, H, W, cfg.sf
-    t_start = t_start_of(cfg, dt.reduced)
-    d.sa_start, d.s1m_start = float(dt.sqrt_ac[t_start]), float(dt.sqrt_1m_ac[t_start])
-    d.y_dev = _ptr(yd)
-    lab = None
-    if labels is not None:
-        lab = np.ascontiguousarray(labels, dtype=np.int64)
-        d.labels_host = lab.ctypes.data
-    keep = [yd]
+    d, lab = _loop_desc(cfg, B, H, W, cfg.sf, start_coefficients(cfg, dt), y, k, None, labels, seed, image_offset, False, skip_dead_final_eval)
     nps = nyt = None
-    if noise_source == "host":
-        if noise_fn is None:
-            raise EngineError("noise_source='host' needs noise_fn")
-        init = np.asarray(noise_fn((B, 3, H, W)), dtype=np.float32)
-        ps, yt = [], []
-        for st in steps:
-            ps.append(np.asarray(noise_fn((B, 3, H, W)), dtype=np.float32))
-            yt.append(np.asarray(noise_fn((B, 3, h, w)), dtype=np.float32) if yt_mode and not st["last"] else np.zeros((B, 3, h, w), np.float32))
-        di, nps = engine.to_device(init), engine.to_device(np.stack(ps))
-        keep += [di, nps]
-        if yt_mode:
-            nyt = engine.to_device(np.stack(yt))
-            keep.append(nyt)
-        d.noise_init_dev = di.ptr
-    elif noise_source != "device":
-        raise ValueError("noise_source must be 'host' or 'device'")
-    d.seed, d.image_offset = seed, image_offset
-    d.skip_dead_final_eval = int(skip_dead_final_eval)
-    d.generate_mode = GENERATE_MODES[cfg.generate_mode]
-    # config.ddim_sample reaches model_fn(..., 'pred_x_prev_and_start') (main_ddpir.py:371-373): xt is then ddim_sample(eta=0)'s sample
-    d.ddim_sample = 1 if cfg.ddim_sample else 0
-    if out_f32 is None:
-        out_f32 = engine.empty((B, 3, H, W))
-    if out_u8 is None and return_u8:
-        out_u8 = engine.empty((B, H, W, 3), np.uint8)
-    armed = _arm(engine, progress, cfg, steps, B, H, W, False)
-    engine._check(engine.lib.dpir_run_dps_loop(engine.h, C.byref(d), arr, coefs, len(steps), 1 if yt_mode else 0, float(cfg.lambda_),
-                                               _ptr(nps), _ptr(nyt), 1.0, _ptr(out_f32), _ptr(out_u8)))
+    if _host_noise(noise_source, noise_fn):
+        dn = {k_: _dev(engine, v, None, keep) for k_, v in draw_grad_host_noise(noise_fn, cfg, steps, B, H, W).items()}
+        d.noise_init_dev, d.noise_n1_dev, d.noise_n2_dev = _ptr(dn["init"]), _ptr(dn.get("n1")), _ptr(dn.get("n2"))
+        nps, nyt = dn.get("ps"), dn.get("yt")
+    out_f32, out_u8 = _outputs(engine, B, H, W, out_f32, out_u8, return_u8)
+    head = (engine.h, C.byref(d), arr, coefs, len(steps), variant, float(cfg.lambda_), _ptr(nps), _ptr(nyt))
+    if deblur:
+        call = lambda: engine.lib.dpir_run_deblur_grad_loop(*head, _ptr(out_f32), _ptr(out_u8))
+    else:
+        call = lambda: engine.lib.dpir_run_dps_loop(*head, 1.0, _ptr(out_f32), _ptr(out_u8))
+    _call_loop(engine, progress, cfg, steps, B, H, W, False, call)
     engine.sync()
-    if armed:
-        armed.finish()
     return (out_f32, out_u8) if return_u8 else out_f32
 
 

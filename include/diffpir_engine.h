@@ -386,7 +386,10 @@ typedef struct dpir_dps_coef {
  *   x = xt - d norm / d xt * lambda * norm / rho_t * 0.35   -- differentiated w.r.t. xt itself, no network backward (gradient mode not needed).
  * d / steps_host as in dpir_run_loop (task DPIR_TASK_SR_BLUR or _SR_CUBIC; k / mask / n1 / n2 unused); coefs_host [n_steps];
  * noise_ps_dev: host-fed p_sample noise [n_steps, B,3,H,W] in step order or NULL -> device Philox (stream 4*(step+1));
- * noise_yt_dev (variant 1): host-fed y_t noise [n_steps, B,3,H/sf,W/sf] or NULL -> Philox (stream 4*(step+1)+1). */
+ * noise_yt_dev (variant 1): host-fed y_t noise [n_steps, B,3,H/sf,W/sf] or NULL -> Philox (stream 4*(step+1)+1).
+ * This entry and dpir_run_deblur_grad_loop below are ONE loop body over a measurement operator (here Resizer(1/sf)); what is said here of the
+ * steps, the dead final step (skip_dead_final_eval), the noise layouts, the Philox streams (init: 0, rows keyed by image_offset) and the
+ * progressive strip holds for both.  A steps table in which a non-final step follows a final one is DPIR_ERR_INVALID. */
 int dpir_run_dps_loop(dpir_engine* e, const dpir_loop_desc* d, const dpir_step* steps_host, const dpir_dps_coef* coefs_host, int n_steps,
                       int variant, float lambda_, const float* noise_ps_dev, const float* noise_yt_dev, float step_scale,
                       float* out_f32_dev, uint8_t* out_u8_dev);
@@ -441,7 +444,9 @@ int dpir_blur_reflect_adjoint(dpir_engine* e, const float* g_dev, const float* k
  * norm_out_dev [B] (may be NULL), norm_grad_out_dev[n] = d norm_n / d x_n.  through_network and its tape preconditions as dpir_grad_and_value. */
 int dpir_grad_and_value_blur(dpir_engine* e, int through_network, const float* x_hat_dev, const float* measurement_dev, const float* k_dev, int kh, int kw,
                              float* norm_grad_out_dev, float* norm_out_dev, int B, int H, int W);
-/* The loop of main_ddpir_deblur.py:257-360 in its gradient modes, task DPIR_TASK_DEBLUR, sf 1, k_dev required:
+/* The loop of main_ddpir_deblur.py:257-360 in its gradient modes, task DPIR_TASK_DEBLUR, sf 1, k_dev required: the body of dpir_run_dps_loop
+ * over the operator Tx.  What differs: the measurement (y in [0,1]), the norm (each image's own, no collective), the initial x (y itself,
+ * not its bicubic up-sampling), the full-size y_t draw, a unit DPS_y0 step, and variant 2:
  *   variant 0 'DPS_y0' (:323-327): xt, x0 = p_sample(x);  x = xt - d || y - Tx(x0) || / d x  (through the denoiser; gradient mode), no re-noising;
  *   variant 1 'DPS_yt' (:329-336): y_t = sa_t (2y-1) + s1m_t n;  x = xt - d || (y_t/2+.5) - Tx(xt) || / d xt * lambda * norm / rho_t * 0.35, no re-noising;
  *   variant 2 first-order data step (sub_1_analytic false, :305-314): x0 = pred_xstart;  x0 <- x0 - d || y - Tx(x0) || / d x0 * norm / rho_t, then the

@@ -70,6 +70,52 @@ def test_draw_order_matches_the_restatement(kw):
         ([(2, 3, 64, 64)] + ([(2, 3, 16, 16)] if not s["last"] else []) for s in s2), []) and n_re > 0
 
 
+def _grad_mode_configs():
+    for sf in (2, 4):
+        for mode in ("DPS_y0", "DPS_yt"):
+            yield f"sr_x{sf}_{mode}", dict(task="sr", sf=sf, sr_mode="cubic", generate_mode=mode)
+    for eta in (0.0, 0.5):
+        for name, kw in (("DPS_y0", dict(generate_mode="DPS_y0")), ("DPS_yt", dict(generate_mode="DPS_yt")),
+                         ("first_order", dict(generate_mode="DiffPIR", sub_1_analytic=False))):
+            yield f"deblur_{name}_eta{eta}", dict(driver="main_ddpir_deblur", task="deblur", eta=eta, **kw)
+
+
+@pytest.mark.parametrize("iters", [dict(iter_num=4), dict(iter_num=600, skip_type="quad")], ids=["4", "600quad"])
+@pytest.mark.parametrize("name,kw", list(_grad_mode_configs()), ids=[n for n, _ in _grad_mode_configs()])
+def test_grad_mode_drawer_follows_dps_host_noise_shapes(name, kw, iters):
+    """draw_grad_host_noise asks noise_fn for exactly the shapes of dps_host_noise_shapes, in its order, and returns what the loops are fed:
+    one p_sample draw per step, the y_t draws (zeros where a step has none) or the re-noise draws of the non-final steps."""
+    Bn, size = 2, 16
+    cfg = restore.LoopConfig(**kw, **iters)
+    cfg.check_supported()
+    _, steps, _ = restore._steps(cfg)
+    if iters["iter_num"] == 600:
+        assert sum(s["last"] for s in steps) == 2           # the quad schedule repeats its final timestep
+    asked, count = [], [0]
+
+    def noise_fn(shape):
+        asked.append(tuple(shape))
+        count[0] += 1
+        return np.full(shape, count[0], np.float32)          # draw number, to see where each draw lands
+    got = restore.draw_grad_host_noise(noise_fn, cfg, steps, Bn, size, size)
+    assert asked == restore.dps_host_noise_shapes(cfg, steps, Bn, size, size)
+    full, n_re = (Bn, 3, size, size), sum(1 for s in steps if not s["last"])
+    assert got["init"].shape == full and (got["init"] == 1).all()
+    if cfg.generate_mode == "DiffPIR":
+        assert set(got) == {"init", "n1", "n2"} and got["n2"].shape == (n_re,) + full
+        assert (got["n1"] is None) == (cfg.eta == 0) and (got["n1"] is None or got["n1"].shape == (n_re,) + full)
+        assert [float(got["n2"][j, 0, 0, 0, 0]) for j in range(n_re)] == [4.0 + 3 * j for j in range(n_re)]
+        return
+    assert set(got) == {"init", "ps", "yt"} and got["ps"].shape == (len(steps),) + full
+    if cfg.generate_mode == "DPS_y0":
+        assert got["yt"] is None
+        assert [float(v) for v in got["ps"][:, 0, 0, 0, 0]] == [2.0 + i for i in range(len(steps))]
+        return
+    assert got["yt"].shape == (len(steps), Bn, 3, size // cfg.sf, size // cfg.sf)
+    assert [float(v) for v in got["ps"][:n_re, 0, 0, 0, 0]] == [2.0 + 2 * i for i in range(n_re)]
+    assert [float(v) for v in got["yt"][:, 0, 0, 0, 0]] == [3.0 + 2 * i for i in range(n_re)] + [0.0] * (len(steps) - n_re)
+
+
 @pytest.mark.skipif(not ref_import.available(), reason="the reference tree is not present")
 def test_statements_against_the_live_reference():
     """The helper's operator == utils_deblur.Blurkernel's depthwise reflect-padded convolution with the same weights, and its (norm_grad, norm)
