@@ -242,6 +242,10 @@ SIGNATURES = {
     "dpir_lpips": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dpir_lpips_keep_taps": (C.c_int, [C.c_void_p, C.c_int]),
     "dpir_lpips_read_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "dpir_fid_load": (C.c_int, [C.c_void_p, C.POINTER(Tensor), C.c_int]),
+    "dpir_fid_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "dpir_fid_keep_taps": (C.c_int, [C.c_void_p, C.c_int]),
+    "dpir_fid_read_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "dpir_run_loop": (C.c_int, [C.c_void_p, C.POINTER(LoopDesc), C.POINTER(Step), C.c_int, C.c_void_p, C.c_void_p]),
     "dpir_run_loop_per_image": (C.c_int, [C.c_void_p, C.POINTER(LoopDesc), C.POINTER(Step), C.c_int, C.POINTER(ImageStep), C.POINTER(C.c_int64),
                                           C.c_void_p, C.c_void_p]),

@@ -7,6 +7,7 @@
 #include "inpaint.h"
 #include "progress.h"
 #include "lpips.h"
+#include "fid.h"
 #include <math.h>
 #include <string.h>
 #include <stdlib.h>
@@ -227,6 +228,7 @@ void dpir_destroy(dpir_engine* e) {
     if (e->range_ctr) (void)hipFree(e->range_ctr);
     if (e->progress_premix) (void)hipFree(e->progress_premix);
     lpips_free(e);
+    fid_free(e);
     (void)hipStreamDestroy(e->stream);
     delete e;
 }
@@ -732,6 +734,43 @@ int dpir_lpips_read_tap(dpir_engine* e, int k, float* host_dst, size_t cap, size
     if (!host_dst) return DPIR_OK;
     if (cap < *numel_out) return fail(e, invalid("dpir_lpips_read_tap: destination too small"));
     return dpir_d2h(e, host_dst, e->lpips->tap[k], sizeof(float) * *numel_out);
+}
+
+int dpir_fid_load(dpir_engine* e, const dpir_tensor* weights, int n) {
+    if (!e || !weights || n <= 0) return fail(e, invalid("dpir_fid_load: null argument"));
+    (void)hipSetDevice(e->device);
+    API_TRY(e, fid_load(e, weights, n));
+    return DPIR_OK;
+}
+
+int dpir_fid_features(dpir_engine* e, const uint8_t* img_u8, const float* img_f32, int B, int H, int W, float* feat_host) {
+    if (!e || !feat_host) return fail(e, invalid("dpir_fid_features: null argument"));
+    if ((img_u8 != nullptr) == (img_f32 != nullptr)) return fail(e, invalid("dpir_fid_features: exactly one of img_u8_dev and img_f32_dev must be given"));
+    API_TRY(e, check_shape("dpir_fid_features", B, H, W));
+    if (!e->fid || !e->fid->loaded) return fail(e, Status{DPIR_ERR_STATE, "dpir_fid_features: no FID Inception weights loaded (dpir_fid_load)"});
+    (void)hipSetDevice(e->device);
+    {
+        ProfScope ps(&e->prof, PC_ELEM);
+        API_TRY(e, fid_run(e, img_u8, img_f32, B, H, W));
+    }
+    return dpir_d2h(e, feat_host, e->fid->feat, sizeof(float) * (size_t)B * kFidFeat);
+}
+
+int dpir_fid_keep_taps(dpir_engine* e, int on) {
+    if (!e) return DPIR_ERR_INVALID;
+    e->fid_keep_taps = on != 0;
+    return DPIR_OK;
+}
+
+int dpir_fid_read_tap(dpir_engine* e, int k, float* host_dst, size_t cap, size_t* numel_out) {
+    if (!e || !numel_out) return fail(e, invalid("dpir_fid_read_tap: null argument"));
+    if (k < 0 || k >= kFidTaps) return fail(e, invalid("dpir_fid_read_tap: tap index must be 0..13"));
+    if (!e->fid || e->fid->tap_numel[k] == 0)
+        return fail(e, Status{DPIR_ERR_STATE, "dpir_fid_read_tap: nothing kept (dpir_fid_keep_taps before dpir_fid_features; tap 13, the features, needs only a call)"});
+    *numel_out = e->fid->tap_numel[k];
+    if (!host_dst) return DPIR_OK;
+    if (cap < *numel_out) return fail(e, invalid("dpir_fid_read_tap: destination too small"));
+    return dpir_d2h(e, host_dst, k == kFidTaps - 1 ? e->fid->feat : e->fid->tap[k], sizeof(float) * *numel_out);
 }
 
 }  // extern "C"

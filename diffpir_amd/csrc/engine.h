@@ -84,6 +84,7 @@ struct Tape {
 };
 
 struct LpipsState;       // lpips.h: VGG16 trunk + head weights, the chunk arena and the kept taps
+struct FidState;         // fid.h: the FID Inception-v3 layers, its op list, the chunk arena and the kept taps
 
 struct ResizerTab { int in_len = 0, out_len = 0, taps = 0; float* w = nullptr; int* idx = nullptr; };
 
@@ -158,6 +159,8 @@ struct dpir_engine {
     float* progress_premix = nullptr; size_t progress_premix_bytes = 0;
     dpir::LpipsState* lpips = nullptr;           // dpir_lpips_load (lpips.hip); its arena is its own, NOT `ws`: growing that would orphan the step graphs
     bool lpips_keep_taps = false;                // dpir_lpips_keep_taps: the next dpir_lpips calls keep their five feature maps for dpir_lpips_read_tap
+    dpir::FidState* fid = nullptr;               // dpir_fid_load (fid.hip); its arena is its own too
+    bool fid_keep_taps = false;                  // dpir_fid_keep_taps: the next dpir_fid_features calls keep their 13 block outputs for dpir_fid_read_tap
     void* comm = nullptr; int comm_world = 1, comm_rank = 0;     // RCCL communicator (comm.cpp), or null
 
     dpir::Status resizer(int in_len, int sf, dpir::ResizerTab* out);

@@ -1,8 +1,8 @@
 """Degradation synthesis and metrics on the device: the steps either side of the restoration loop.
 
 `degrade` mirrors CustomDataset.__getitem__'s arithmetic (main_ddpir.py:84-114) for a batch of uint8 ground-truth images;
-`metrics` mirrors main_ddpir.py:482-517 (PSNR and PSNR on the Y channel), `lpips` main_ddpir.py:489-493.  All are thin wrappers over
-dpir_degrade / dpir_metrics / dpir_lpips; PSF and mask GENERATION (a few hundred scalar operations per image under the numpy RNG) stays on the host so that
+`metrics` mirrors main_ddpir.py:482-517 (PSNR and PSNR on the Y channel), `lpips` main_ddpir.py:489-493; `fid_features` gives the Inception features of the FID column (README.md:119-141).  All are thin wrappers over
+dpir_degrade / dpir_metrics / dpir_lpips / dpir_fid_features; PSF and mask GENERATION (a few hundred scalar operations per image under the numpy RNG) stays on the host so that
 kernels and masks remain bit-identical to the reference's.
 """
 from __future__ import annotations
@@ -71,4 +71,19 @@ def lpips(engine: Engine, x0, gt):
         raise ValueError(f"lpips: ground truth {gt.dtype} {tuple(gt.shape)} does not go with x0 {tuple(x0.shape)} (uint8 [B,H,W,3] or float32 [B,3,H,W])")
     out = np.empty(B, np.float32)
     engine._check(engine.lib.dpir_lpips(engine.h, _ptr(x0), _ptr(gt) if u8 else None, None if u8 else _ptr(gt), B, H, W, out.ctypes.data))
+    return out
+
+
+def fid_features(engine: Engine, img):
+    """FID Inception-v3 `pool3` features as a float32 array [B, 2048] (dpir_fid_features; needs engine.load_fid).  img: uint8 [B,H,W,3]
+    (what dpir_finalize writes; the ground truth) or float32 [B,3,H,W] in [0,1]; a DeviceArray or numpy."""
+    if isinstance(img, np.ndarray):
+        img = engine.to_device(np.ascontiguousarray(img))
+    u8 = np.dtype(img.dtype) == np.uint8
+    shape = tuple(img.shape)
+    if len(shape) != 4 or shape[3 if u8 else 1] != 3 or not (u8 or np.dtype(img.dtype) == np.float32):
+        raise ValueError(f"fid_features: image {img.dtype} {shape} is neither uint8 [B,H,W,3] nor float32 [B,3,H,W]")
+    B, H, W = (shape[0], shape[1], shape[2]) if u8 else (shape[0], shape[2], shape[3])
+    out = np.empty((B, 2048), np.float32)
+    engine._check(engine.lib.dpir_fid_features(engine.h, _ptr(img) if u8 else None, None if u8 else _ptr(img), B, H, W, out.ctypes.data))
     return out

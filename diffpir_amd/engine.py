@@ -266,6 +266,35 @@ class Engine:
         self._check(self.lib.dpir_lpips_read_tap(self.h, int(k), out.ctypes.data, n.value, C.byref(n)))
         return out
 
+    # ---- FID (csrc/fid.hip)
+    def load_fid(self, state_dict):
+        """FID Inception-v3 (dpir_fid_load).  state_dict: pytorch-fid's raw layout (<layer>.conv.weight, <layer>.bn.*) or the folded
+        canonical keys (fid.canonical)."""
+        from . import fid as fd
+        sd = fd.canonical(state_dict)
+        arr = (_lib.Tensor * len(sd))()
+        for i, (k, a) in enumerate(sd.items()):
+            arr[i].name = k.encode()
+            arr[i].data = a.ctypes.data
+            arr[i].ndim = a.ndim
+            for d in range(a.ndim):
+                arr[i].shape[d] = a.shape[d]
+        self._check(self.lib.dpir_fid_load(self.h, arr, len(sd)))
+        self.fid_loaded = True
+
+    fid_loaded = False
+
+    def fid_keep_taps(self, on=True):
+        self._check(self.lib.dpir_fid_keep_taps(self.h, 1 if on else 0))
+
+    def fid_read_tap(self, k: int) -> np.ndarray:
+        """Tap k (0..12: the stem's two pools and the 11 Mixed outputs; 13: the features) of the last dpir_fid_features call, flat."""
+        n = C.c_size_t()
+        self._check(self.lib.dpir_fid_read_tap(self.h, int(k), None, 0, C.byref(n)))
+        out = np.empty(n.value, np.float32)
+        self._check(self.lib.dpir_fid_read_tap(self.h, int(k), out.ctypes.data, n.value, C.byref(n)))
+        return out
+
     def unet_forward(self, x, t, y=None, out=None):
         B, _, H, W = x.shape
         t = np.ascontiguousarray(t, dtype=np.int64)

@@ -11,7 +11,9 @@ the per-image degradation recipe (main_ddpir.py:46-117) and the batch PSNR log l
 the loop body is one engine call (restore.restore_batch), images are read / written with PIL when available (cv2
 is not installed here), LPIPS is computed by the engine (dpir_lpips) from the two weight files under <cwd>/model_zoo when `calc_LPIPS`
 is set and they are there (one WARNING and no LPIPS otherwise: never a metric on synthetic weights), and the batch's LPIPS is the mean over
-its images (the reference keeps image 0's score times the batch size, main_ddpir.py:491: the same thing at batch_size 1).  With no
+its images (the reference keeps image 0's score times the batch size, main_ddpir.py:491: the same thing at batch_size 1).  `calc_FID: true` (an engine
+key: the reference leaves FID to pytorch-fid on the saved images) accumulates the FID Inception features of every restored batch and of the ground
+truth (dpir_fid_features) and logs the Frechet distance per sweep point, when model_zoo holds pytorch-fid's weight file.  With no
 dataset / checkpoint on disk it falls back to synthetic ground truth and synthetic weights, saying so in the log.
 """
 from __future__ import annotations
@@ -25,7 +27,7 @@ import time
 import numpy as np
 import yaml
 
-from . import restore, synth, script_util, utils_model, weights, degrade as dgr, lpips as lpips_host
+from . import restore, synth, script_util, utils_model, weights, degrade as dgr, lpips as lpips_host, fid as fid_host
 from .engine import Engine
 from .utils_inpaint import mask_generator
 
@@ -122,6 +124,9 @@ def check_batch_sweeps(config):
                          "sweep point up front (about 8 GB for the super-resolution sweep)")
     if progress_options(config)[0]:
         raise ValueError("engine_batch_sweeps with save_progressive / log_process: the strips' file names carry one lambda, a batch holds several")
+    if bool(config.get("calc_FID", False)):
+        raise ValueError("engine_batch_sweeps with calc_FID: a batch mixes the images of several sweep points, FID is one number per point's whole set "
+                         "(run the sweep point by point: engine_batch_sweeps: false)")
     restore.check_per_image(loop_config(config, *sweeps(config)[0]), restore.PerImage(lambda_=[], zeta=[]))
 
 
@@ -141,6 +146,33 @@ def setup_lpips(eng, config) -> bool:
                     config.get("lpips_lin_path", "lpips_vgg.pth"), config.get("cwd", ""))
         return False
     return True
+
+
+def setup_fid(eng, config, n_images) -> bool:
+    """calc_FID: load the FID Inception-v3 once.  False -- after ONE warning -- when the weight file is not under <cwd>/model_zoo or the test
+    set has fewer than 2 images (no covariance); False without a word when the key is off.  The run then continues exactly as without the key."""
+    if not bool(config.get("calc_FID", False)):
+        return False
+    if n_images < 2:
+        log.warning("calc_FID: FID is not computed -- the test set has %d image(s), a covariance needs at least 2", n_images)
+        return False
+    path = fid_host.find_weight_file(config)
+    try:
+        if not os.path.exists(path):
+            raise FileNotFoundError("weight file not found")
+        eng.load_fid(fid_host.load_weights(path))
+    except (FileNotFoundError, KeyError) as ex:
+        log.warning("calc_FID: FID is not computed -- %s.  It needs %s (pytorch-fid's FID Inception weights, YAML key fid_inception_path) under "
+                    "cwd=%r; see INTEGRATION.md", ex, os.path.join("model_zoo", config.get("fid_inception_path", fid_host.DEFAULT_FILE)), config.get("cwd", ""))
+        return False
+    return True
+
+
+def fid_rows(eng, img_u8_dev, n_local, n_b, ddist, rank, world):
+    """float64 [n_b, 2048]: the FID Inception features of the batch's images (this rank's shard through dpir_fid_features, then gathered the way
+    the metric rows are)."""
+    local = dgr.fid_features(eng, img_u8_dev).astype(np.float64) if n_local else np.zeros((0, fid_host.FEATURES))
+    return ddist.all_gather_results(local.reshape(-1, fid_host.FEATURES), n_b, rank, world, engine=eng)
 
 
 def metric_rows(eng, out_f32, gt_dev, with_lpips):
@@ -463,6 +495,8 @@ def main(argv=None):
     with_lpips = setup_lpips(eng, config)
     ncol = 3 if with_lpips else 2
     imgs, names = load_images(config, args.synthetic)
+    with_fid = setup_fid(eng, config, len(imgs))
+    fid_gt, fids = {}, []                  # ground-truth feature rows per batch (computed at the first sweep point, reused by the others); FID per point
     use_graph = bool(config.get("engine_graph", True))
     noise = config.get("engine_noise", "device")
     host_gen = None
@@ -487,6 +521,7 @@ def main(argv=None):
         if rank == 0:
             log.info("eta:%s, zeta:%s, lambda:%s, guidance_scale:%s", config.eta, zeta, lambda_, config.guidance_scale)
         psnrs, psnrs_y, lps, t0, n = [], [], [], time.time(), 0
+        fid_out = fid_host.FidStats()
         for i0 in range(0, len(imgs), config.batch_size):
             gt = imgs[i0:i0 + config.batch_size]                           # uint8 [n,H,W,3]
             n_b, H, W = gt.shape[0], gt.shape[1], gt.shape[2]
@@ -543,6 +578,10 @@ def main(argv=None):
                 per_img = metric_rows(eng, out_f32, ops["gt"], with_lpips)         # dpir_metrics: per-image PSNR / PSNR-Y; dpir_lpips
                 if pg is not None:
                     emit_progress(config, pg, names[i0 + lo:i0 + hi], lambda_, per_img[:, 0].astype(np.float32))
+            if with_fid:
+                if i0 not in fid_gt:
+                    fid_gt[i0] = fid_rows(eng, ops["gt"] if hi > lo else None, hi - lo, n_b, ddist, rank, world)
+                fid_out.add(fid_rows(eng, u8_local, hi - lo, n_b, ddist, rank, world))
             u8 = ddist.all_gather_results(u8_local, n_b, rank, world, engine=eng)           # the one collective of the path
             allm = ddist.all_gather_results(per_img.reshape(-1, ncol), n_b, rank, world, engine=eng)   # per-image PSNR [/ LPIPS] rows (host numpy)
             p, p_y = float(np.mean(allm[:, 0])), float(np.mean(allm[:, 1]))
@@ -562,7 +601,17 @@ def main(argv=None):
             if with_lpips:
                 log.info("-----------> Average LPIPS of (%s) scale factor: (%d), sigma: (%.3f): %.4f",
                          config.testset_name, config.sf, config.noise_level_model, sum(lps) / n)
+        if with_fid:
+            gt_stats = fid_host.FidStats()
+            for key in sorted(fid_gt):
+                gt_stats.add(fid_gt[key])
+            fids.append(fid_host.frechet_distance(fid_out.mu, fid_out.sigma, gt_stats.mu, gt_stats.sigma))
+            if rank == 0:
+                log.info("-----------> FID of (%s) scale factor: (%d), sigma: (%.3f): %.4f",
+                         config.testset_name, config.sf, config.noise_level_model, fids[-1])
         results.append(sum(psnrs) / n)
+    if fids and rank == 0:
+        log.info("-----------> Average FID of (%s) over %d sweep point(s): %.4f", config.testset_name, len(fids), sum(fids) / len(fids))
     ddist.shutdown()
     eng.close()
     return results

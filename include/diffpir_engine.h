@@ -527,6 +527,30 @@ int dpir_lpips(dpir_engine* e, const float* x0_dev, const uint8_t* gt_u8_dev, co
 int dpir_lpips_keep_taps(dpir_engine* e, int on);
 int dpir_lpips_read_tap(dpir_engine* e, int k, float* host_dst, size_t cap_floats, size_t* numel_out);
 
+/* ---- FID (calc_FID; the FID column of the paper's tables, reference README.md:119-141) ------ */
+/* The `pool3` features of the FID Inception-v3 as pytorch-fid defines them (README.md:119-141 reports FID beside PSNR and LPIPS; the reference
+ * computes it with pytorch-fid on saved images).  Entry: v = u8 / 255, bilinear resize to 299 x 299 (align_corners = False, no antialias), 2 v - 1.
+ * Network: 94 BasicConv layers (convolution without bias, eval-mode BatchNorm with eps 1e-3 folded in by the host, ReLU) in the stem and the
+ * blocks Mixed_5b/5c/5d, 6a, 6b..6e, 7a, 7b/7c; avg-pools 3x3 s1 p1 that do not count the padding; Mixed_7c's pool branch is a max-pool;
+ * the features are the mean over the 8 x 8 positions (float64, rounded once).  Mean, covariance and the Frechet distance are the host's
+ * (diffpir_amd/fid.py).  dpir_fid_load copies and packs the weights (caller keeps the host arrays).  Keys: "<layer>.weight" [Cout,Cin,KH,KW]
+ * and "<layer>.bias" [Cout], BatchNorm already folded; DPIR_ERR_INVALID naming the first missing / mis-shaped key.  A second load replaces
+ * the first.  Independent of dpir_load_unet and dpir_set_precision: the network always runs the exact-fp32 MFMA convolution, whose
+ * accumulators are added to a float64 running sum every 64 products. */
+int dpir_fid_load(dpir_engine* e, const dpir_tensor* weights, int n_weights);
+/* Exactly one image pointer: img_u8_dev uint8 [B,H,W,3] (what dpir_finalize writes, what a saved PNG holds -- pytorch-fid reads PNGs) or
+ * img_f32_dev float32 [B,3,H,W] in [0,1].  feat_host: HOST array of B * 2048 floats (syncs).  An image's features have the same bits
+ * wherever it sits in a batch, for every B, chunk size and repeat (no atomics, no split-K; every sum has one order).  The images run in
+ * chunks of 16 through an engine-owned arena (about 250 MB); env DPIR_FID_CHUNK=<images> forces a smaller chunk -- chunking changes no bit.
+ * DPIR_ERR_STATE without a prior dpir_fid_load; DPIR_ERR_INVALID for B < 1, both pointers or neither. */
+int dpir_fid_features(dpir_engine* e, const uint8_t* img_u8_dev, const float* img_f32_dev, int B, int H, int W, float* feat_host);
+/* Parity taps (pytorch-fid's block boundaries): with keep on, every dpir_fid_features call keeps 13 tensors and dpir_fid_read_tap copies tap k
+ * of the last call to host: k = 0, 1 the stem behind its two max-pools [B,64,73,73], [B,192,35,35]; 2..4 Mixed_5b/5c/5d [B,256|288|288,35,35];
+ * 5..9 Mixed_6a..6e [B,768,17,17]; 10 Mixed_7a [B,1280,8,8]; 11, 12 Mixed_7b/7c [B,2048,8,8]; k = 13 the features [B,2048] (kept always).
+ * host_dst NULL: only numel_out is written. */
+int dpir_fid_keep_taps(dpir_engine* e, int on);
+int dpir_fid_read_tap(dpir_engine* e, int k, float* host_dst, size_t cap_floats, size_t* numel_out);
+
 /* ---- instrumentation --------------------------------------------------------------------- */
 /* Kernel-time accounting with HIP events on the engine stream.  class ids: 0 conv3x3, 1 conv1x1,
  * 2 groupnorm-stats, 3 attention, 4 fft-prox, 5 elementwise/other, 6 whole unet forward.
