@@ -7,23 +7,9 @@
 // LDS-DMA copies straight into MFMA B-operand order.  Bytes per element: 4 read + 4 written.
 #include "common.h"
 #include "elem.h"
+#include "conv_epilogue.h"
 
 namespace dpir {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float silu_a(float v) {
-    float e = __builtin_amdgcn_exp2f(v * -1.4426950408889634f);
-    return v * __builtin_amdgcn_rcpf(1.0f + e);
-}
-
-// f16 operand range guard.  The split clamps to +-65000 so that hi stays finite; a value that needed the clamp (or a NaN)
-// makes the result wrong, so it is COUNTED: one atomic per wave that saw one (none in the normal case), read back by
-// dpir_sync / dpir_d2h, which then fail with DPIR_ERR_RANGE instead of returning a silently saturated image.
-__device__ __forceinline__ void range_report(bool bad, unsigned long long* ctr) {
-    const unsigned long long m = __ballot(bad);
-    if (m != 0ull && ctr && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(m)) atomicAdd(ctr, (unsigned long long)__builtin_popcountll(m));
-}
 
 // grid: (ceil(H*W/256), B*C8); MODE 0 plain, 1 nearest-up (source is H/2 x W/2), 2 avg-pool (source is 2H x 2W)
 template <int MODE>
@@ -51,14 +37,14 @@ __global__ __launch_bounds__(256) void act_split_kernel(CatSrc src, const float4
                 float v0 = plane[so], v1 = plane[so + 1], v2 = plane[so + Ws], v3 = plane[so + Ws + 1];
                 if (prm) {
                     v0 = (v0 - m.x) * m.y + m.z; v1 = (v1 - m.x) * m.y + m.z; v2 = (v2 - m.x) * m.y + m.z; v3 = (v3 - m.x) * m.y + m.z;
-                    if (m.w != 0.f) { v0 = silu_a(v0); v1 = silu_a(v1); v2 = silu_a(v2); v3 = silu_a(v3); }
+                    if (m.w != 0.f) { v0 = silu(v0); v1 = silu(v1); v2 = silu(v2); v3 = silu(v3); }
                 }
                 v = ((v0 + v1) + (v2 + v3)) * 0.25f;
             } else {
                 v = plane[so];
                 if (prm) {
                     v = (v - m.x) * m.y + m.z;
-                    if (m.w != 0.f) v = silu_a(v);
+                    if (m.w != 0.f) v = silu(v);
                 }
             }
         }
@@ -112,7 +98,7 @@ __global__ __launch_bounds__(256) void act_split4_kernel(CatSrc src, const float
                 float4 m = prm[(size_t)n * C + c];
                 v[j].x = (v[j].x - m.x) * m.y + m.z; v[j].y = (v[j].y - m.x) * m.y + m.z;
                 v[j].z = (v[j].z - m.x) * m.y + m.z; v[j].w = (v[j].w - m.x) * m.y + m.z;
-                if (m.w != 0.f) { v[j].x = silu_a(v[j].x); v[j].y = silu_a(v[j].y); v[j].z = silu_a(v[j].z); v[j].w = silu_a(v[j].w); }
+                if (m.w != 0.f) { v[j].x = silu(v[j].x); v[j].y = silu(v[j].y); v[j].z = silu(v[j].z); v[j].w = silu(v[j].w); }
             }
         }
     }
@@ -180,7 +166,6 @@ struct GnActK {
 template <int CQ>
 __device__ __forceinline__ void store_halves(_Float16* dst, const _Float16* v) {
     typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-    typedef _Float16 half4v __attribute__((ext_vector_type(4)));
     if constexpr (CQ == 4) { half4v t; t[0] = v[0]; t[1] = v[1]; t[2] = v[2]; t[3] = v[3]; *reinterpret_cast<half4v*>(dst) = t; }
     else if constexpr (CQ == 2) { half2v t; t[0] = v[0]; t[1] = v[1]; *reinterpret_cast<half2v*>(dst) = t; }
     else dst[0] = v[0];
@@ -298,12 +283,12 @@ __global__ __launch_bounds__(1024) void gn_act_small_kernel(GnActK p) {
             if (p.mode == 2) {
                 float v0 = plane[so], v1 = plane[so + 1], v2 = plane[so + p.Ws], v3 = plane[so + p.Ws + 1];
                 v0 = (v0 - mean) * a + b; v1 = (v1 - mean) * a + b; v2 = (v2 - mean) * a + b; v3 = (v3 - mean) * a + b;
-                if (p.act != 0.f) { v0 = silu_a(v0); v1 = silu_a(v1); v2 = silu_a(v2); v3 = silu_a(v3); }
+                if (p.act != 0.f) { v0 = silu(v0); v1 = silu(v1); v2 = silu(v2); v3 = silu(v3); }
                 v = ((v0 + v1) + (v2 + v3)) * 0.25f;
             } else {
                 v = plane[so];
                 v = (v - mean) * a + b;
-                if (p.act != 0.f) v = silu_a(v);
+                if (p.act != 0.f) v = silu(v);
             }
             bad |= !(fabsf(v) <= 65000.f);
             v = fminf(fmaxf(v, -65000.f), 65000.f);

@@ -22,51 +22,25 @@
 // co-blocks and gradient mode stay on launch_conv6 (plan_conv3, conv_plan.cpp).
 #include "common.h"
 #include "elem.h"
-#include "lds_dma.h"
-#include "conv6_params.h"
+#include "conv_epilogue.h"
 #include "conv11.h"
 #include <atomic>
-#include <type_traits>
 
 namespace dpir {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for11(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for11<I + 1, N>(f);
-    }
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_row_shr11(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-
 namespace c11 {
-constexpr int TW = 32, TH = 8, LW = TW + 2, LH = TH + 2;
-constexpr int PATCH = LH * LW;                      // entries (16 B = 8 channels of one position) per k-half
-constexpr int NPIECE = (2 * PATCH + 63) / 64;       // one-KiB DMA pieces per plane
+using G = TileGeo<0>;                               // conv7's 8 x 32 tile
+constexpr int LW = G::LW, NPIECE = G::NPIECE, XB = G::XB;
 constexpr int NXT = (NPIECE + 3) / 4;               // per wave and plane
 constexpr int NACT = 2 * NXT;                       // activation DMA instructions per wave and chunk (hi, lo)
-constexpr int XB = NPIECE * 1024;                   // bytes per plane and buffer
 constexpr int TAPS = 9;
 [[maybe_unused]] constexpr int STEPS = 9;            // pair steps per period of two chunks
-constexpr size_t LDS = (size_t)4 * XB;              // two buffers x (hi, lo); the epilogue slabs alias them
+constexpr size_t LDS = G::LDS;
 [[maybe_unused]] constexpr int AREC = 8 * 1024;                     // weight bytes per (pair step, co-block, wave co-half): 4 M-tiles x (hi, lo) x 1 KiB
 static_assert(NACT == 6, "two pieces per step in the first three steps of a window");
-static_assert(LDS >= 4 * 32 * 68 * 4, "epilogue slabs");
 // entry q of a period (0 .. 17): chunk parity q / 9 = patch buffer, tap q % 9 -> offset of the fragment read, in 16-byte entries
 constexpr int frag_off(int q) { return (q / TAPS) * (2 * XB / 16) + ((q % TAPS) / 3) * LW + (q % TAPS) % 3; }
 }  // namespace c11
-
-__device__ __forceinline__ float silu11(float v) {         // act.hip's silu_a
-    float e = __builtin_amdgcn_exp2f(v * -1.4426950408889634f);
-    return v * __builtin_amdgcn_rcpf(1.0f + e);
-}
 
 // EMIT: the fused hop to the next convolution of a ResBlock (Conv6Emit, conv7's contract).  Everything up to the epilogue is the same kernel;
 // workgroups keep their natural order (image-major, the co-block outside the tiles of an image), so that the workgroups that wait for one
@@ -75,6 +49,7 @@ template <bool EMIT>
 __global__ __launch_bounds__(256, 2) void conv11_mfma_kernel(Conv6K p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     using namespace c11;
+    constexpr int TW = G::TW, TH = G::TH, PATCH = G::PATCH;
     extern __shared__ __attribute__((aligned(16))) char smem11[];      // [2 buffers][hi|lo][XB]
 
     const int tid = threadIdx.x;
@@ -198,12 +173,12 @@ __global__ __launch_bounds__(256, 2) void conv11_mfma_kernel(Conv6K p) {
     auto period = [&](auto par_c, int per) __attribute__((always_inline)) {
         constexpr int PAR = decltype(par_c)::value;
         const int even_next = min(2 * per + 2, last_chunk);
-        static_for11<0, STEPS>([&](auto s_c) __attribute__((always_inline)) {
+        static_for<0, STEPS>([&](auto s_c) __attribute__((always_inline)) {
             constexpr int s = decltype(s_c)::value;
             constexpr int slot = (s + PAR) & 1;
             constexpr int sn = (s + 1) % STEPS;
             const half8* xp = xstep(s);
-            static_for11<0, 4>([&](auto j_c) __attribute__((always_inline)) {
+            static_for<0, 4>([&](auto j_c) __attribute__((always_inline)) {
                 constexpr int j = decltype(j_c)::value;
                 if (j < 3) {
                     read_b(xp, j + 1, (j + 1) & 1);
@@ -275,88 +250,12 @@ __global__ __launch_bounds__(256, 2) void conv11_mfma_kernel(Conv6K p) {
                 if (l15 == 0) { wl[64 + ch] = s1; wl[128 + ch] = s2; }
             }
         __builtin_amdgcn_wave_barrier();
-        // group sums in integers (the order of the additions is immaterial), one atomic instruction per workgroup: as conv7
-        const int cg = p.Cout >> 5;                           // channels per group: 4, 8 or 16
-        const int gpw = 64 / cg;                              // groups per wave: 16, 8 or 4
-        double* gsum = reinterpret_cast<double*>(reinterpret_cast<float*>(smem11) + 4 * 512);     // [cw 2][pw 2][16 groups][2] behind the per-wave areas
-        if (lane < gpw) {
-            double s1 = 0.0, s2 = 0.0;
-            for (int k = 0; k < cg; ++k) { s1 += (double)wl[64 + lane * cg + k]; s2 += (double)wl[128 + lane * cg + k]; }
-            gsum[((cw * 2 + pw) * 16 + lane) * 2] = s1;
-            gsum[((cw * 2 + pw) * 16 + lane) * 2 + 1] = s2;
-        }
-        __syncthreads();
-        const int gpb = 2 * gpw;                              // groups of this workgroup's 128 channels
-        long long* const accb = p.em.acc + ((size_t)n0 * 32 + (size_t)co_blk * gpb) * 2;
-        if (wave == 0) {
-            const int gl = lane >> 1, t = lane & 1;           // lane = (group of the block, S | SS)
-            long long r = 0;
-            if (gl < gpb) {
-                const int c2 = gl / gpw, g = gl - c2 * gpw;
-                const double v = gsum[((c2 * 2 + 0) * 16 + g) * 2 + t] + gsum[((c2 * 2 + 1) * 16 + g) * 2 + t];
-                // memory-side atomic that returns: once the result is back it has been performed (conv7.hip has the measurement)
-                r = __hip_atomic_fetch_add(accb + gl * 2 + t, __double2ll_rn(v * (t ? 4096.0 : 1048576.0)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-            asm volatile("s_waitcnt vmcnt(0)" : : "v"((int)r) : "memory");
-            if (lane == 0) {
-                unsigned* cp = p.em.cnt + (size_t)n0 * p.n_co_blocks + co_blk;
-                const unsigned old = __hip_atomic_fetch_add(cp, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                asm volatile("" : : "v"(old));
-                int spins = 0;
-                while (__hip_atomic_load(cp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) < (unsigned)(tiles_per_img + p.em.expect_extra)) {
-                    switch (p.em.sleep_sel) {          // the argument of s_sleep is an immediate
-                        case 0: __builtin_amdgcn_s_sleep(2); break;
-                        case 1: __builtin_amdgcn_s_sleep(8); break;
-                        case 3: __builtin_amdgcn_s_sleep(32); break;
-                        case 4: __builtin_amdgcn_s_sleep(64); break;
-                        case 6: __builtin_amdgcn_s_sleep(127); __builtin_amdgcn_s_sleep(127); break;
-                        case 7: __builtin_amdgcn_s_sleep(127); __builtin_amdgcn_s_sleep(127); __builtin_amdgcn_s_sleep(127); __builtin_amdgcn_s_sleep(127); break;
-                        case 2: __builtin_amdgcn_s_sleep(16); break;
-                        default: __builtin_amdgcn_s_sleep(127); break;
-                    }
-                    if (++spins > p.em.spin_limit) { atomicAdd(p.em.range_ctr, 1ull << 40); break; }      // never hang the GPU: report through the range guard
-                }
-            }
-        }
-        __syncthreads();
-        {
-            const int c = co_wave + lane;
-            const long long* ap = accb + (size_t)((cw * gpw) + lane / cg) * 2;
-            const double S = (double)__hip_atomic_load(ap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) * (1.0 / 1048576.0);
-            const double SS = (double)__hip_atomic_load(ap + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) * (1.0 / 4096.0);
-            const double cntd = (double)cg * HW;
-            const double mean = S / cntd;
-            double var = SS / cntd - mean * mean;
-            if (var < 0) var = 0;
-            const float rstd = (float)(1.0 / sqrt(var + 1e-5));
-            float a = rstd * p.em.gamma[c];
-            float b = p.em.beta[c];
-            if (p.em.film) {   // h = GN(h) * (1 + scale) + shift   (unet.py:250-251), gn_prm_kernel's arithmetic
-                const float* f = p.em.film + (p.em.fstep ? (size_t)p.em.fstep->i * p.em.frows : 0) + (size_t)n0 * p.em.film_stride + p.em.film_off;
-                const float sc = 1.0f + f[c];
-                const float sh = f[p.Cout + c];
-                a = a * sc;
-                b = b * sc + sh;
-            }
-            reinterpret_cast<float4*>(wl + 192)[lane] = make_float4((float)mean, a, b, 0.f);
-        }
-        __builtin_amdgcn_wave_barrier();
-        typedef _Float16 half4v __attribute__((ext_vector_type(4)));
-        typedef unsigned int u32x2e __attribute__((ext_vector_type(2)));
-        typedef unsigned int u32x4e __attribute__((ext_vector_type(4)));
+        hop_rendezvous<64>(p, reinterpret_cast<float*>(smem11), wl, wave, cw, pw, lane, n0, co_blk, co_wave, tiles_per_img, HW);
         const float4* tab = reinterpret_cast<const float4*>(wl + 192);
         bool bad = false;
         // A 16-byte plane entry = 8 channels of one pixel; this lane holds 4 of them (r = 0 .. 3 at 4 (l >> 4)), lane ^ 16 the other 4.  For a
         // pair of pixel rows (j, j + 1) v_permlane16_swap hands the even 16-lane rows both halves of row j and the odd ones both halves of
         // row j + 1: one 16-byte store per lane.
-        auto norm_split = [&](float x, const float4& t, _Float16& h, _Float16& l) __attribute__((always_inline)) {
-            float v = (x - t.x) * t.y + t.z;
-            v = silu11(v);
-            bad |= !(fabsf(v) <= 65000.f);
-            v = fminf(fmaxf(v, -65000.f), 65000.f);
-            h = (_Float16)v;
-            l = (_Float16)(v - (float)h);
-        };
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             float4 t4[4];
@@ -371,29 +270,26 @@ __global__ __launch_bounds__(256, 2) void conv11_mfma_kernel(Conv6K p) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         _Float16 th, tl;
-                        norm_split(acc[m][2 * (2 * jp) + cb][q], t4[q], th, tl); h0[q] = th; l0[q] = tl;
-                        norm_split(acc[m][2 * (2 * jp + 1) + cb][q], t4[q], th, tl); h1[q] = th; l1[q] = tl;
+                        norm_split(acc[m][2 * (2 * jp) + cb][q], t4[q], bad, th, tl); h0[q] = th; l0[q] = tl;
+                        norm_split(acc[m][2 * (2 * jp + 1) + cb][q], t4[q], bad, th, tl); h1[q] = th; l1[q] = tl;
                     }
-                    const u32x2e a_hh = __builtin_bit_cast(u32x2e, h0), b_hh = __builtin_bit_cast(u32x2e, h1);
-                    const u32x2e a_ll = __builtin_bit_cast(u32x2e, l0), b_ll = __builtin_bit_cast(u32x2e, l1);
-                    u32x4e eh, el;
+                    const u32x2 a_hh = __builtin_bit_cast(u32x2, h0), b_hh = __builtin_bit_cast(u32x2, h1);
+                    const u32x2 a_ll = __builtin_bit_cast(u32x2, l0), b_ll = __builtin_bit_cast(u32x2, l1);
+                    u32x4 eh, el;
                     {
                         const auto s0 = __builtin_amdgcn_permlane16_swap(a_hh.x, b_hh.x, false, false), s1 = __builtin_amdgcn_permlane16_swap(a_hh.y, b_hh.y, false, false);
                         eh.x = s0[0]; eh.y = s1[0]; eh.z = s0[1]; eh.w = s1[1];
                     }
                     const size_t eo = (((size_t)n0 * p.em.C8 + c8) * HW + (size_t)(ty0 + 4 * pw + 2 * jp + (rsub & 1)) * p.W + (tx0 + 16 * cb + l15)) << 4;
-                    *reinterpret_cast<u32x4e*>(p.em.hi + eo) = eh;
+                    *reinterpret_cast<u32x4*>(p.em.hi + eo) = eh;
                     {
                         const auto s0 = __builtin_amdgcn_permlane16_swap(a_ll.x, b_ll.x, false, false), s1 = __builtin_amdgcn_permlane16_swap(a_ll.y, b_ll.y, false, false);
                         el.x = s0[0]; el.y = s1[0]; el.z = s0[1]; el.w = s1[1];
-                        *reinterpret_cast<u32x4e*>(p.em.lo + eo) = el;
+                        *reinterpret_cast<u32x4*>(p.em.lo + eo) = el;
                     }
                 }
         }
-        {
-            const unsigned long long mk = __ballot(bad);
-            if (mk != 0ull && lane == (int)__builtin_ctzll(mk)) atomicAdd(p.em.range_ctr, (unsigned long long)__builtin_popcountll(mk));
-        }
+        range_report(bad, p.em.range_ctr);
         return;
     }
 
@@ -415,8 +311,6 @@ __global__ __launch_bounds__(256, 2) void conv11_mfma_kernel(Conv6K p) {
     const unsigned res_bytes = res_mode >= 0 ? 0xFFFFFFFFu : 0u;
     const void* const stat_base = do_stat ? (const void*)(p.stat + img0 * p.stat_slots) : (const void*)p.bias;
     const unsigned stat_bytes = do_stat ? 0xFFFFFFFFu : 0u;
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
     auto f4 = [](u32x4 v) { return make_float4(as_f32(v.x), as_f32(v.y), as_f32(v.z), as_f32(v.w)); };
 
     const __amdgpu_buffer_rsrc_t r_bias = rsrc_uniform(p.bias, (unsigned)p.Cout * 4u);
@@ -475,7 +369,7 @@ __global__ __launch_bounds__(256, 2) void conv11_mfma_kernel(Conv6K p) {
 
     float4 rv[2][8];
     load_res(0, rv[0]);
-    static_for11<0, 4>([&](auto q_c) __attribute__((always_inline)) {
+    static_for<0, 4>([&](auto q_c) __attribute__((always_inline)) {
         constexpr int q = decltype(q_c)::value;
         constexpr int i = q >> 1, jp = q & 1;
         const PassGeo g = geo(q);
@@ -515,10 +409,10 @@ __global__ __launch_bounds__(256, 2) void conv11_mfma_kernel(Conv6K p) {
             if (do_stat) {
                 float s1 = (v.x + v.y) + (v.z + v.w);
                 float s2 = (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-                s1 += dpp_row_shr11<0x111>(s1); s2 += dpp_row_shr11<0x111>(s2);
-                s1 += dpp_row_shr11<0x112>(s1); s2 += dpp_row_shr11<0x112>(s2);
-                s1 += dpp_row_shr11<0x114>(s1); s2 += dpp_row_shr11<0x114>(s2);
-                s1 += dpp_row_shr11<0x118>(s1); s2 += dpp_row_shr11<0x118>(s2);
+                s1 += dpp_row_shr<0x111>(s1); s2 += dpp_row_shr<0x111>(s2);
+                s1 += dpp_row_shr<0x112>(s1); s2 += dpp_row_shr<0x112>(s2);
+                s1 += dpp_row_shr<0x114>(s1); s2 += dpp_row_shr<0x114>(s2);
+                s1 += dpp_row_shr<0x118>(s1); s2 += dpp_row_shr<0x118>(s2);
                 u32x2 st;
                 st.x = as_u32(s1); st.y = as_u32(s2);
                 const bool wr = q4 == 15;

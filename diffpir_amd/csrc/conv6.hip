@@ -33,36 +33,13 @@
 //
 // Tile geometries (256 pixels): 8 rows x 32 columns (W >= 32), 16 x 16 (W >= 16), 4 images x 8 x 8 (W >= 8).
 #include "common.h"
-#include "lds_dma.h"
-#include "conv6_params.h"
+#include "conv_epilogue.h"
 #include <math.h>
 #include <stdlib.h>
-#include <type_traits>
 #include <vector>
 
 namespace dpir {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_row_shr6(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-
-template <int GEO> struct Geo6;
-template <> struct Geo6<0> { static constexpr int LTW = 5, LTH = 3, TI = 1; };   // 8 rows x 32 columns
-template <> struct Geo6<1> { static constexpr int LTW = 4, LTH = 4, TI = 1; };   // 16 x 16
-template <> struct Geo6<2> { static constexpr int LTW = 3, LTH = 3, TI = 4; };   // 4 images x 8 x 8
 
 // A/B switch of the chunk-boundary barrier (lds_dma.h barrier_lds_only against __syncthreads with its vmcnt(0))
 #ifndef DPIR_C6_LDS_BARRIER
@@ -92,15 +69,11 @@ __global__ __launch_bounds__(256, 2) void conv6_mfma_kernel(Conv6K p) {
     // The body uses the buffer-descriptor builtin type, which only exists in the DEVICE pass of hipcc; in the host pass an
     // (ill-formed) template body would silently drop the kernel's launch stub, so the host pass sees an empty body.
 #if defined(__HIP_DEVICE_COMPILE__)
-    using G = Geo6<GEO>;
-    constexpr int TW = 1 << G::LTW, TH = 1 << G::LTH, TI = G::TI;
-    constexpr int LW = TW + 2, LH = TH + 2;
-    constexpr int PATCH = TI * LH * LW;                 // patch positions = entries per k-half
-    constexpr int NPIECE = (2 * PATCH + 63) / 64;       // 1 KiB DMA pieces per plane (hi or lo)
+    using G = TileGeo<GEO>;
+    constexpr int TW = G::TW, TH = G::TH, TI = G::TI, LW = G::LW, LH = G::LH, PATCH = G::PATCH, NPIECE = G::NPIECE, XB = G::XB;
     constexpr int NXT = (NPIECE + 3) / 4;               // pieces per wave per plane
     constexpr int NPL = X1 ? 1 : 2;                     // operand planes (hi [, lo])
     constexpr int NACT = NPL * NXT;                     // activation DMA instructions per wave per chunk
-    constexpr int XB = NPIECE * 1024;                   // bytes per plane buffer
     constexpr int D = R - 1;                            // weight prefetch distance in taps
     constexpr int TAPS = 9;
     constexpr int GPI = (TW * TH) / 64;                 // 64-pixel groups per image inside one tile
@@ -341,8 +314,6 @@ __global__ __launch_bounds__(256, 2) void conv6_mfma_kernel(Conv6K p) {
     const unsigned res_bytes = res_mode >= 0 ? 0xFFFFFFFFu : 0u;
     const void* const stat_base = do_stat ? (const void*)(p.stat + img0 * p.stat_slots) : (const void*)p.bias;
     const unsigned stat_bytes = do_stat ? 0xFFFFFFFFu : 0u;
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
     auto f4 = [](u32x4 v) { return make_float4(as_f32(v.x), as_f32(v.y), as_f32(v.z), as_f32(v.w)); };
 
     float bv[8];
@@ -444,10 +415,10 @@ __global__ __launch_bounds__(256, 2) void conv6_mfma_kernel(Conv6K p) {
                 float s1 = (v.x + v.y) + (v.z + v.w);
                 float s2 = (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
                 // inclusive scan over the 16-lane DPP row (row_shr 1, 2, 4, 8, zero fill): lane 15 of the row ends with the total
-                s1 += dpp_row_shr6<0x111>(s1); s2 += dpp_row_shr6<0x111>(s2);
-                s1 += dpp_row_shr6<0x112>(s1); s2 += dpp_row_shr6<0x112>(s2);
-                s1 += dpp_row_shr6<0x114>(s1); s2 += dpp_row_shr6<0x114>(s2);
-                s1 += dpp_row_shr6<0x118>(s1); s2 += dpp_row_shr6<0x118>(s2);
+                s1 += dpp_row_shr<0x111>(s1); s2 += dpp_row_shr<0x111>(s2);
+                s1 += dpp_row_shr<0x112>(s1); s2 += dpp_row_shr<0x112>(s2);
+                s1 += dpp_row_shr<0x114>(s1); s2 += dpp_row_shr<0x114>(s2);
+                s1 += dpp_row_shr<0x118>(s1); s2 += dpp_row_shr<0x118>(s2);
                 // a 64-pixel group belongs to ONE image (GPI groups per image and tile); groups wholly outside the image store 0
                 u32x2 st;
                 st.x = as_u32(s1); st.y = as_u32(s2);
@@ -548,10 +519,7 @@ DeviceCaps device_caps() {
 
 template <int GEO, int R, bool X1>
 static Status launch6(hipStream_t s, Conv6K k, int blocks) {
-    using G = Geo6<GEO>;
-    constexpr int PATCH = G::TI * ((1 << G::LTH) + 2) * ((1 << G::LTW) + 2);
-    constexpr int NPIECE = (2 * PATCH + 63) / 64;
-    constexpr size_t LDS = (size_t)4 * NPIECE * 1024 + (size_t)4 * R * 2048;
+    constexpr size_t LDS = TileGeo<GEO>::LDS + (size_t)4 * R * 2048;      // the operand buffers + the four private weight rings
     static_assert(2 * LDS <= 160 * 1024, "two workgroups per CU");
     auto fn = conv6_mfma_kernel<GEO, R, X1>;
     static LdsAttrOnce attr_set;

@@ -1,4 +1,5 @@
-// Kernel parameter block shared by the two 3x3 f16 MFMA kernels (conv6.hip, conv7.hip); filled by launch_conv6.
+// Kernel parameter block shared by the 3x3 f16 MFMA kernels (conv6.hip, conv7.hip; conv11.hip and conv_up.hip fill their own).
+// What the kernels do with it behind their main loops is in conv_epilogue.h.
 #pragma once
 #include "common.h"
 namespace dpir {

@@ -20,32 +20,9 @@
 #include "common.h"
 #include <atomic>
 #include "elem.h"
-#include "lds_dma.h"
-#include "conv6_params.h"
-#include <type_traits>
+#include "conv_epilogue.h"
 
 namespace dpir {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for7(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for7<I + 1, N>(f);
-    }
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_row_shr7(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-
-template <int GEO> struct Geo7;
-template <> struct Geo7<0> { static constexpr int LTW = 5, LTH = 3, TI = 1; };   // 8 rows x 32 columns
-template <> struct Geo7<1> { static constexpr int LTW = 4, LTH = 4, TI = 1; };   // 16 x 16
-template <> struct Geo7<2> { static constexpr int LTW = 3, LTH = 3, TI = 4; };   // 4 images x 8 x 8
 
 // NARROW (8 x 32 geometry): a launch with at most 32 output channels (the 128 -> 6 output convolution, the 128 -> 3 dgrad of conv_in).  One
 // live co-tile: instead of two waves computing a dead second co-tile and two waves idling, all four waves take that co-tile for a
@@ -53,23 +30,16 @@ template <> struct Geo7<2> { static constexpr int LTW = 3, LTH = 3, TI = 4; };  
 // EMIT (8 x 32 geometry, whole K, full 128-channel blocks, tiles inside the image): the fused hop to the next convolution of a ResBlock,
 // see Conv6Emit.  Everything up to the epilogue is the same kernel; workgroups keep their natural order (image-major), so that the
 // <= 256 workgroups of an image are dispatched together and the wait below always ends.
-__device__ __forceinline__ float silu7(float v) {          // act.hip's silu_a
-    float e = __builtin_amdgcn_exp2f(v * -1.4426950408889634f);
-    return v * __builtin_amdgcn_rcpf(1.0f + e);
-}
 
 template <int GEO, bool X1, bool NARROW, bool EMIT>
 __global__ __launch_bounds__(256, 2) void conv7_mfma_kernel(Conv6K p) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    using G = Geo7<GEO>;
-    constexpr int TW = 1 << G::LTW, TH = 1 << G::LTH, TI = G::TI, LW = TW + 2, LH = TH + 2;
-    constexpr int PATCH = TI * LH * LW;                 // entries per k-half
-    constexpr int NPIECE = (2 * PATCH + 63) / 64;       // one-KiB DMA pieces per plane
+    using G = TileGeo<GEO>;
+    constexpr int TW = G::TW, TH = G::TH, TI = G::TI, LW = G::LW, LH = G::LH, PATCH = G::PATCH, NPIECE = G::NPIECE, XB = G::XB;
     constexpr int NXT = (NPIECE + 3) / 4;               // per wave and plane
     constexpr int NPL = X1 ? 1 : 2;                     // operand planes (hi [, lo])
     constexpr int NACT = NPL * NXT;                     // activation DMA instructions per wave and chunk
     static_assert(NACT <= 8, "the activation pieces must be older than the weights of taps 7 and 8");
-    constexpr int XB = NPIECE * 1024;
     constexpr int TAPS = 9;
     constexpr int CT = NARROW ? 1 : 2;                  // co-tiles (32 channels) per wave
     constexpr int TPG = NARROW ? 1 : 2;                 // pixel tiles (32 pixels) per group; a wave has two groups
@@ -225,7 +195,7 @@ __global__ __launch_bounds__(256, 2) void conv7_mfma_kernel(Conv6K p) {
     auto chunk_body = [&](auto more_c, int chunk, int it) __attribute__((always_inline)) {
         constexpr bool MORE = decltype(more_c)::value;
         const int cur = it & 1;
-        static_for7<0, TAPS>([&](auto tap_c) __attribute__((always_inline)) {
+        static_for<0, TAPS>([&](auto tap_c) __attribute__((always_inline)) {
             constexpr int tap = decltype(tap_c)::value;
             constexpr int slot = tap % 3;
             read_b(cur, tap, 1, 1);
@@ -280,91 +250,12 @@ __global__ __launch_bounds__(256, 2) void conv7_mfma_kernel(Conv6K p) {
                 if (l31 == 0) { wl[64 + ch] = s1; wl[128 + ch] = s2; }
             }
         __builtin_amdgcn_wave_barrier();
-        // GroupNorm needs GROUP sums only, and with integer accumulation the order of the additions is immaterial: fold the channels of a
-        // group and the two pixel halves of the workgroup here, so that ONE atomic instruction per workgroup (<= 32 groups x {S, SS}) is
-        // left.  (Per-channel atomics from every wave -- 512 per workgroup, 2 M per launch -- cost 0.8 ms per forward: profiles/r04.)
-        const int cg = p.Cout >> 5;                           // channels per group: 4, 8 or 16
-        const int gpw = 64 / cg;                              // groups per wave: 16, 8 or 4
-        double* gsum = reinterpret_cast<double*>(reinterpret_cast<float*>(smem7) + 4 * 512);     // [cw 2][pw 2][16 groups][2] behind the per-wave areas
-        if (lane < gpw) {
-            double s1 = 0.0, s2 = 0.0;
-            for (int k = 0; k < cg; ++k) { s1 += (double)wl[64 + lane * cg + k]; s2 += (double)wl[128 + lane * cg + k]; }
-            gsum[((cw * 2 + pw) * 16 + lane) * 2] = s1;
-            gsum[((cw * 2 + pw) * 16 + lane) * 2 + 1] = s2;
-        }
-        __syncthreads();
-        const int gpb = 2 * gpw;                              // groups of this workgroup's 128 channels
-        long long* const accb = p.em.acc + ((size_t)n0 * 32 + (size_t)co_blk * gpb) * 2;
-        if (wave == 0) {
-            const int gl = lane >> 1, t = lane & 1;           // lane = (group of the block, S | SS)
-            long long r = 0;
-            if (gl < gpb) {
-                const int c2 = gl / gpw, g = gl - c2 * gpw;
-                const double v = gsum[((c2 * 2 + 0) * 16 + g) * 2 + t] + gsum[((c2 * 2 + 1) * 16 + g) * 2 + t];
-                // memory-side atomic that returns: once the result is back it has been performed (an agent-scope release fence instead
-                // writes back the XCD's dirty L2 lines, i.e. everybody's plane stores: +1.5 ms per forward, profiles/r04)
-                r = __hip_atomic_fetch_add(accb + gl * 2 + t, __double2ll_rn(v * (t ? 4096.0 : 1048576.0)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-            asm volatile("s_waitcnt vmcnt(0)" : : "v"((int)r) : "memory");
-            if (lane == 0) {
-                unsigned* cp = p.em.cnt + (size_t)n0 * p.n_co_blocks + co_blk;
-                const unsigned old = __hip_atomic_fetch_add(cp, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                asm volatile("" : : "v"(old));
-                int spins = 0;
-                while (__hip_atomic_load(cp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) < (unsigned)(tiles_per_img + p.em.expect_extra)) {
-                    switch (p.em.sleep_sel) {          // the argument of s_sleep is an immediate
-                        case 0: __builtin_amdgcn_s_sleep(2); break;
-                        case 1: __builtin_amdgcn_s_sleep(8); break;
-                        case 3: __builtin_amdgcn_s_sleep(32); break;
-                        case 4: __builtin_amdgcn_s_sleep(64); break;
-                        case 6: __builtin_amdgcn_s_sleep(127); __builtin_amdgcn_s_sleep(127); break;
-                        case 7: __builtin_amdgcn_s_sleep(127); __builtin_amdgcn_s_sleep(127); __builtin_amdgcn_s_sleep(127); __builtin_amdgcn_s_sleep(127); break;
-                        case 2: __builtin_amdgcn_s_sleep(16); break;
-                        default: __builtin_amdgcn_s_sleep(127); break;
-                    }
-                    if (++spins > p.em.spin_limit) { atomicAdd(p.em.range_ctr, 1ull << 40); break; }      // never hang the GPU: report through the range guard
-                }
-            }
-        }
-        __syncthreads();
-        {
-            const int c = co_wave + lane;
-            const long long* ap = accb + (size_t)((cw * gpw) + lane / cg) * 2;
-            const double S = (double)__hip_atomic_load(ap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) * (1.0 / 1048576.0);
-            const double SS = (double)__hip_atomic_load(ap + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) * (1.0 / 4096.0);
-            const double cntd = (double)cg * HW;
-            const double mean = S / cntd;
-            double var = SS / cntd - mean * mean;
-            if (var < 0) var = 0;
-            const float rstd = (float)(1.0 / sqrt(var + 1e-5));
-            float a = rstd * p.em.gamma[c];
-            float b = p.em.beta[c];
-            if (p.em.film) {   // h = GN(h) * (1 + scale) + shift   (unet.py:250-251), gn_prm_kernel's arithmetic
-                const float* f = p.em.film + (p.em.fstep ? (size_t)p.em.fstep->i * p.em.frows : 0) + (size_t)n0 * p.em.film_stride + p.em.film_off;
-                const float sc = 1.0f + f[c];
-                const float sh = f[p.Cout + c];
-                a = a * sc;
-                b = b * sc + sh;
-            }
-            reinterpret_cast<float4*>(wl + 192)[lane] = make_float4((float)mean, a, b, 0.f);
-        }
-        __builtin_amdgcn_wave_barrier();
-        typedef _Float16 half4v __attribute__((ext_vector_type(4)));
-        typedef unsigned int u32x2e __attribute__((ext_vector_type(2)));
-        typedef unsigned int u32x4e __attribute__((ext_vector_type(4)));
+        hop_rendezvous<64>(p, reinterpret_cast<float*>(smem7), wl, wave, cw, pw, lane, n0, co_blk, co_wave, tiles_per_img, HW);
         const float4* tab = reinterpret_cast<const float4*>(wl + 192);
         bool bad = false;
         // A 16-byte plane entry = 8 channels of one pixel; this lane holds 4 of them (4 half .. 4 half + 3), lane ^ 32 the other 4.  For a pair
         // of pixel rows (j, j + 1) v_permlane32_swap hands the lower lanes both halves of row j and the upper lanes both halves of row
         // j + 1: one 16-byte store per lane (1 KiB per instruction) instead of two 8-byte ones.
-        auto norm_split = [&](float x, const float4& m, _Float16& h, _Float16& l) __attribute__((always_inline)) {
-            float v = (x - m.x) * m.y + m.z;
-            v = silu7(v);
-            bad |= !(fabsf(v) <= 65000.f);
-            v = fminf(fmaxf(v, -65000.f), 65000.f);
-            h = (_Float16)v;
-            l = (_Float16)(v - (float)h);
-        };
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -379,29 +270,26 @@ __global__ __launch_bounds__(256, 2) void conv7_mfma_kernel(Conv6K p) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         _Float16 th, tl;
-                        norm_split(acc[i][2 * jp][jb * 4 + q], m[q], th, tl); h0[q] = th; l0[q] = tl;
-                        norm_split(acc[i][2 * jp + 1][jb * 4 + q], m[q], th, tl); h1[q] = th; l1[q] = tl;
+                        norm_split(acc[i][2 * jp][jb * 4 + q], m[q], bad, th, tl); h0[q] = th; l0[q] = tl;
+                        norm_split(acc[i][2 * jp + 1][jb * 4 + q], m[q], bad, th, tl); h1[q] = th; l1[q] = tl;
                     }
-                    const u32x2e a_h = __builtin_bit_cast(u32x2e, h0), b_h = __builtin_bit_cast(u32x2e, h1);
-                    const u32x2e a_l = __builtin_bit_cast(u32x2e, l0), b_l = __builtin_bit_cast(u32x2e, l1);
-                    u32x4e eh, el;
+                    const u32x2 a_h = __builtin_bit_cast(u32x2, h0), b_h = __builtin_bit_cast(u32x2, h1);
+                    const u32x2 a_l = __builtin_bit_cast(u32x2, l0), b_l = __builtin_bit_cast(u32x2, l1);
+                    u32x4 eh, el;
                     {
                         const auto s0 = __builtin_amdgcn_permlane32_swap(a_h.x, b_h.x, false, false), s1 = __builtin_amdgcn_permlane32_swap(a_h.y, b_h.y, false, false);
                         eh.x = s0[0]; eh.y = s1[0]; eh.z = s0[1]; eh.w = s1[1];
                     }
                     const size_t eo = (((size_t)n0 * p.em.C8 + c8) * HW + (size_t)(ty0 + 4 * pw + 2 * jp + half) * p.W + (tx0 + l31)) << 4;
-                    *reinterpret_cast<u32x4e*>(p.em.hi + eo) = eh;
+                    *reinterpret_cast<u32x4*>(p.em.hi + eo) = eh;
                     if (!X1) {
                         const auto s0 = __builtin_amdgcn_permlane32_swap(a_l.x, b_l.x, false, false), s1 = __builtin_amdgcn_permlane32_swap(a_l.y, b_l.y, false, false);
                         el.x = s0[0]; el.y = s1[0]; el.z = s0[1]; el.w = s1[1];
-                        *reinterpret_cast<u32x4e*>(p.em.lo + eo) = el;
+                        *reinterpret_cast<u32x4*>(p.em.lo + eo) = el;
                     }
                 }
             }
-        {
-            const unsigned long long mk = __ballot(bad);
-            if (mk != 0ull && lane == (int)__builtin_ctzll(mk)) atomicAdd(p.em.range_ctr, (unsigned long long)__builtin_popcountll(mk));
-        }
+        range_report(bad, p.em.range_ctr);
         return;
     }
 
@@ -424,8 +312,6 @@ __global__ __launch_bounds__(256, 2) void conv7_mfma_kernel(Conv6K p) {
     const unsigned res_bytes = res_mode >= 0 ? 0xFFFFFFFFu : 0u;
     const void* const stat_base = do_stat ? (const void*)(p.stat + img0 * p.stat_slots) : (const void*)p.bias;
     const unsigned stat_bytes = do_stat ? 0xFFFFFFFFu : 0u;
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
     auto f4 = [](u32x4 v) { return make_float4(as_f32(v.x), as_f32(v.y), as_f32(v.z), as_f32(v.w)); };
 
     float bv[CT][8];
@@ -495,7 +381,7 @@ __global__ __launch_bounds__(256, 2) void conv7_mfma_kernel(Conv6K p) {
     float4 rv[2][8];
     load_res(0, rv[0]);
     constexpr int NPASS = CT * TPG;                          // passes of 32 co x 64 px
-    static_for7<0, NPASS>([&](auto q_c) __attribute__((always_inline)) {
+    static_for<0, NPASS>([&](auto q_c) __attribute__((always_inline)) {
         constexpr int q = decltype(q_c)::value;
         constexpr int i = q >> 1, jp = q & 1;
         const PassGeo g = geo(q);
@@ -528,10 +414,10 @@ __global__ __launch_bounds__(256, 2) void conv7_mfma_kernel(Conv6K p) {
             if (do_stat) {
                 float s1 = (v.x + v.y) + (v.z + v.w);
                 float s2 = (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-                s1 += dpp_row_shr7<0x111>(s1); s2 += dpp_row_shr7<0x111>(s2);
-                s1 += dpp_row_shr7<0x112>(s1); s2 += dpp_row_shr7<0x112>(s2);
-                s1 += dpp_row_shr7<0x114>(s1); s2 += dpp_row_shr7<0x114>(s2);
-                s1 += dpp_row_shr7<0x118>(s1); s2 += dpp_row_shr7<0x118>(s2);
+                s1 += dpp_row_shr<0x111>(s1); s2 += dpp_row_shr<0x111>(s2);
+                s1 += dpp_row_shr<0x112>(s1); s2 += dpp_row_shr<0x112>(s2);
+                s1 += dpp_row_shr<0x114>(s1); s2 += dpp_row_shr<0x114>(s2);
+                s1 += dpp_row_shr<0x118>(s1); s2 += dpp_row_shr<0x118>(s2);
                 u32x2 st;
                 st.x = as_u32(s1); st.y = as_u32(s2);
                 const bool wr = q4 == 15 && co < p.Cout && n0 + g.ti < p.B;
@@ -544,11 +430,7 @@ __global__ __launch_bounds__(256, 2) void conv7_mfma_kernel(Conv6K p) {
 
 template <int GEO, bool X1, bool NARROW = false, bool EMIT = false>
 static Status launch7(hipStream_t s, const Conv6K& k, int blocks) {
-    using G = Geo7<GEO>;
-    constexpr int PATCH = G::TI * ((1 << G::LTH) + 2) * ((1 << G::LTW) + 2);
-    constexpr int NPIECE = (2 * PATCH + 63) / 64;
-    constexpr size_t LDS = (size_t)4 * NPIECE * 1024;           // two buffers x (hi, lo); the epilogue slabs (34 KiB) alias them
-    static_assert(LDS >= 4 * 32 * 68 * 4, "epilogue slabs");
+    constexpr size_t LDS = TileGeo<GEO>::LDS;
     auto fn = conv7_mfma_kernel<GEO, X1, NARROW, EMIT>;
     static LdsAttrOnce attr_set;
     DPIR_HIP(attr_set.set(reinterpret_cast<const void*>(fn), (int)LDS));
@@ -556,11 +438,7 @@ static Status launch7(hipStream_t s, const Conv6K& k, int blocks) {
     return Status{};
 }
 
-KernelRef conv7_emit_kernel() {
-    using G = Geo7<0>;
-    constexpr int PATCH = G::TI * ((1 << G::LTH) + 2) * ((1 << G::LTW) + 2);
-    return KernelRef{reinterpret_cast<const void*>(conv7_mfma_kernel<0, false, false, true>), (size_t)4 * ((2 * PATCH + 63) / 64) * 1024};
-}
+KernelRef conv7_emit_kernel() { return KernelRef{reinterpret_cast<const void*>(conv7_mfma_kernel<0, false, false, true>), TileGeo<0>::LDS}; }
 
 // k as launch_conv6 fills it (the tiling of geometry(H, W)); blocks = pixel tiles x co-blocks x ksplit
 Status launch_conv7(hipStream_t s, const Conv6K& k, int blocks, bool x1) {

@@ -20,14 +20,11 @@
 // took 350-400 us per launch at B = 16 whatever was prefetched (profiles/r05/conv8_*_kernel_trace.txt).
 #include "common.h"
 #include "elem.h"
-#include "lds_dma.h"
+#include "conv_epilogue.h"
 #include <vector>
 #include <cmath>
 
 namespace dpir {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 struct Conv8K {
     const float* x;            // [B][C][H][W]
@@ -45,11 +42,6 @@ constexpr int C8_THREADS = 512;                            // 8 waves: one tile 
 constexpr int C8_NIT = (C8_ITEMS + C8_THREADS - 1) / C8_THREADS;   // per thread
 constexpr int C8_WFR = 18 * 64;                            // weight entries (half8) per K step
 static_assert(C8_TW == 32 && C8_TH == 8, "conv8_shape_ok (conv_plan.cpp) states this tile");
-
-__device__ __forceinline__ float silu8(float v) {          // act.hip's silu_a
-    float e = __builtin_amdgcn_exp2f(v * -1.4426950408889634f);
-    return v * __builtin_amdgcn_rcpf(1.0f + e);
-}
 
 template <bool X1>
 __global__ __launch_bounds__(C8_THREADS, 2) void conv8_fused_kernel(Conv8K p) {
@@ -150,7 +142,7 @@ __global__ __launch_bounds__(C8_THREADS, 2) void conv8_fused_kernel(Conv8K p) {
             for (int j = 0; j < 8; ++j) m[j] = s_prm[c0 + j];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                float t = silu8((v[it][j] - m[j].x) * m[j].y + m[j].z);
+                float t = silu((v[it][j] - m[j].x) * m[j].y + m[j].z);
                 t = inside ? t : 0.f;
                 bad |= !(fabsf(t) <= 65000.f);
                 t = fminf(fmaxf(t, -65000.f), 65000.f);

@@ -18,27 +18,10 @@
 // lane in flight in f16x3): at one wave per SIMD the kernel lives on L2 -> CU latency, not on the matrix pipe.
 #include "common.h"
 #include "elem.h"
-#include "lds_dma.h"
+#include "conv_epilogue.h"
 #include "conv9.h"
-#include <type_traits>
 
 namespace dpir {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for9(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for9<I + 1, N>(f);
-    }
-}
-
-__device__ __forceinline__ float silu9(float v) {          // act.hip's silu_a
-    float e = __builtin_amdgcn_exp2f(v * -1.4426950408889634f);
-    return v * __builtin_amdgcn_rcpf(1.0f + e);
-}
 
 constexpr int kC9WaveLds = 16384;                    // per wave: [2 buffers][hi | lo][4 KiB]
 constexpr int kC9RedStride = 68;                     // floats per channel row of the cross-wave sum
@@ -141,7 +124,7 @@ __global__ __launch_bounds__(256, 1) void conv9_image_kernel(Conv9K p) {
 #pragma unroll
             for (int q = 0; q < NACT; ++q) dma_x(chunk + 4, cur ^ 1, q);
         }
-        static_for9<0, TAPS>([&](auto tap_c) __attribute__((always_inline)) {
+        static_for<0, TAPS>([&](auto tap_c) __attribute__((always_inline)) {
             constexpr int tap = decltype(tap_c)::value;
             constexpr int set = tap == 0 ? 2 : (tap & 1);
             __builtin_amdgcn_sched_barrier(0);
@@ -175,7 +158,7 @@ __global__ __launch_bounds__(256, 1) void conv9_image_kernel(Conv9K p) {
     if (chunk < p.n_chunks) {
 #pragma unroll
         for (int q = 0; q < NACT; ++q) dma_x(chunk, 0, q);
-        static_for9<0, TAPS>([&](auto tap_c) __attribute__((always_inline)) { load_a(chunk, tap_c); });
+        static_for<0, TAPS>([&](auto tap_c) __attribute__((always_inline)) { load_a(chunk, tap_c); });
     }
     wait_vmcnt<0>();
     __syncthreads();
@@ -283,7 +266,7 @@ __global__ __launch_bounds__(256, 1) void conv9_image_kernel(Conv9K p) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             float x = (v[i] - meanf) * a + b;
-            x = silu9(x);
+            x = silu(x);
             bad |= !(fabsf(x) <= 65000.f);
             x = fminf(fmaxf(x, -65000.f), 65000.f);
             const _Float16 h = (_Float16)x;
@@ -292,14 +275,12 @@ __global__ __launch_bounds__(256, 1) void conv9_image_kernel(Conv9K p) {
         }
         __syncthreads();
         {
-            typedef unsigned int u32x4e __attribute__((ext_vector_type(4)));
             const int c8l = tid >> 6, px = tid & 63;          // one 16-byte plane entry (8 channels of one pixel) per thread
             const size_t eo = (((size_t)n * p.em.C8 + (cot * 4 + c8l)) * HW + px) << 4;
-            *reinterpret_cast<u32x4e*>(p.em.hi + eo) = *reinterpret_cast<const u32x4e*>(th + px * 32 + c8l * 8);
-            if (!X1) *reinterpret_cast<u32x4e*>(p.em.lo + eo) = *reinterpret_cast<const u32x4e*>(th + 2048 + px * 32 + c8l * 8);
+            *reinterpret_cast<u32x4*>(p.em.hi + eo) = *reinterpret_cast<const u32x4*>(th + px * 32 + c8l * 8);
+            if (!X1) *reinterpret_cast<u32x4*>(p.em.lo + eo) = *reinterpret_cast<const u32x4*>(th + 2048 + px * 32 + c8l * 8);
         }
-        const unsigned long long mk = __ballot(bad);
-        if (mk != 0ull && lane == (int)__builtin_ctzll(mk)) atomicAdd(p.em.range_ctr, (unsigned long long)__builtin_popcountll(mk));
+        range_report(bad, p.em.range_ctr);
     }
 #endif
 }

@@ -21,48 +21,23 @@
 #include "common.h"
 #include <atomic>
 #include "elem.h"
-#include "lds_dma.h"
-#include "conv6_params.h"
+#include "conv_epilogue.h"
 #include "conv_up.h"
 #include <math.h>
-#include <type_traits>
 
 namespace dpir {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for_u(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for_u<I + 1, N>(f);
-    }
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_row_shr_u(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-
-__device__ __forceinline__ float silu_u(float v) {          // act.hip's silu_a
-    float e = __builtin_amdgcn_exp2f(v * -1.4426950408889634f);
-    return v * __builtin_amdgcn_rcpf(1.0f + e);
-}
 
 // Conv6K as conv7 reads it, with H, W, tiles_x, tiles_y of the SOURCE image, n_co_blocks = 64-channel blocks and stat_slots of the output.
 // EMIT: the fused hop to conv2 (Conv6Emit), see the epilogue.
 template <bool X1, bool EMIT>
 __global__ __launch_bounds__(256, 2) void conv_up_kernel(Conv6K p) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    constexpr int TW = 32, TH = 8, LW = TW + 2, LH = TH + 2;
-    constexpr int PATCH = LH * LW;                      // entries per k-half
-    constexpr int NPIECE = (2 * PATCH + 63) / 64;       // one-KiB DMA pieces per plane
+    using G = TileGeo<0>;
+    constexpr int TW = G::TW, TH = G::TH, LW = G::LW, PATCH = G::PATCH, NPIECE = G::NPIECE, XB = G::XB;
     constexpr int NXT = (NPIECE + 3) / 4;               // per wave and plane
     constexpr int NPL = X1 ? 1 : 2;                     // operand planes (hi [, lo])
     constexpr int NACT = NPL * NXT;                     // activation DMA instructions per wave and chunk
     static_assert(NACT <= 6, "two activation pieces per unit in units 0 .. 2: older than the weights requested in units 4 and 5");
-    constexpr int XB = NPIECE * 1024;
     constexpr int UNITS = 6;
     extern __shared__ __attribute__((aligned(16))) char smem_u[];      // [2 buffers][hi|lo][XB]; the epilogue slabs alias it
 
@@ -216,7 +191,7 @@ __global__ __launch_bounds__(256, 2) void conv_up_kernel(Conv6K p) {
     auto chunk_body = [&](auto more_c, int chunk, int it) __attribute__((always_inline)) {
         constexpr bool MORE = decltype(more_c)::value;
         const int cur = it & 1;
-        static_for_u<0, UNITS>([&](auto unit_c) __attribute__((always_inline)) {
+        static_for<0, UNITS>([&](auto unit_c) __attribute__((always_inline)) {
             constexpr int u = decltype(unit_c)::value;
             read_b(cur, u, 1, 1);
             __builtin_amdgcn_sched_barrier(0);
@@ -254,15 +229,8 @@ __global__ __launch_bounds__(256, 2) void conv_up_kernel(Conv6K p) {
     // Accumulator layout: acc[b][j][r] of lane (l31, half) = channel 8 * (r >> 2) + 4 * half + (r & 3) of the wave's 32, output pixel
     // (2 * (ty0 + 4 pw + j) + a, 2 * (tx0 + l31) + b).
     if constexpr (EMIT) {
-        // ---- fused emission (Conv6Emit), conv7<EMIT>'s scheme: fixed-point group sums -> per-image accumulators, arrival counter, bounded
-        // spin, GroupNorm + FiLM + SiLU + f16 split of the wave's own accumulators into conv2's planes.
-        // Why the wait ends.  A workgroup waits only for the workgroups of its own (image, 64-channel block): 2 x tiles_per_img CONSECUTIVE
-        // ids (image-major order, no XCD renumbering), at most half of the workgroups the device holds at once (conv_up_supported).  The
-        // dispatcher hands out ids in increasing order, and nobody waits before having arrived.  Take the lowest set with a workgroup that
-        // has not arrived: every workgroup of a lower set has arrived and leaves without waiting for anything else; a member of the set that
-        // is not resident yet is preceded only by ids of that set or lower ones, and the resident members of the set occupy at most half
-        // of the slots, so it is dispatched as soon as a lower workgroup leaves (or at once) and arrives after a bounded amount of MFMA work.
-        // Should the assumption fail all the same, the spin is bounded and reports through the range guard (2^40), never a hang.
+        // ---- fused emission (Conv6Emit), conv7<EMIT>'s scheme: per-channel sums -> hop_rendezvous (one (image, 64-channel block): both row parities
+        // of every source tile) -> GroupNorm + FiLM + SiLU + f16 split of the wave's own accumulators into conv2's planes.
         __syncthreads();
         float* wl = reinterpret_cast<float*>(smem_u) + wave * 512;      // per-wave scratch: [0,32) bias, [64,96) S, [128,160) SS, [192,320) table
         const float osc = p.out_scale;
@@ -286,87 +254,12 @@ __global__ __launch_bounds__(256, 2) void conv_up_kernel(Conv6K p) {
             if (l31 == 0) { wl[64 + ch] = s1; wl[128 + ch] = s2; }
         }
         __builtin_amdgcn_wave_barrier();
-        const int cg = p.Cout >> 5;                           // channels per group: 4, 8, 16 or 32
-        const int gpw = 32 / cg;                              // groups per wave: 8, 4, 2 or 1
-        double* gsum = reinterpret_cast<double*>(reinterpret_cast<float*>(smem_u) + 4 * 512);     // [cw 2][pw 2][8 groups][2] behind the per-wave areas
-        if (lane < gpw) {
-            double s1 = 0.0, s2 = 0.0;
-            for (int k = 0; k < cg; ++k) { s1 += (double)wl[64 + lane * cg + k]; s2 += (double)wl[128 + lane * cg + k]; }
-            gsum[((cw * 2 + pw) * 8 + lane) * 2] = s1;
-            gsum[((cw * 2 + pw) * 8 + lane) * 2 + 1] = s2;
-        }
-        __syncthreads();
-        const int gpb = 2 * gpw;                              // groups of this workgroup's 64 channels
-        long long* const accb = p.em.acc + ((size_t)n0 * 32 + (size_t)cb * gpb) * 2;
-        if (wave == 0) {
-            const int gl = lane >> 1, t = lane & 1;           // lane = (group of the block, S | SS)
-            long long r = 0;
-            if (gl < gpb) {
-                const int c2 = gl / gpw, g = gl - c2 * gpw;
-                const double v = gsum[((c2 * 2 + 0) * 8 + g) * 2 + t] + gsum[((c2 * 2 + 1) * 8 + g) * 2 + t];
-                // memory-side atomic that returns: once the result is back it has been performed (conv7.hip)
-                r = __hip_atomic_fetch_add(accb + gl * 2 + t, __double2ll_rn(v * (t ? 4096.0 : 1048576.0)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-            asm volatile("s_waitcnt vmcnt(0)" : : "v"((int)r) : "memory");
-            if (lane == 0) {
-                unsigned* cp = p.em.cnt + (size_t)n0 * p.n_co_blocks + cb;
-                const unsigned old = __hip_atomic_fetch_add(cp, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                asm volatile("" : : "v"(old));
-                int spins = 0;
-                while (__hip_atomic_load(cp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) < (unsigned)(2 * tiles_per_img + p.em.expect_extra)) {
-                    switch (p.em.sleep_sel) {          // the argument of s_sleep is an immediate
-                        case 0: __builtin_amdgcn_s_sleep(2); break;
-                        case 1: __builtin_amdgcn_s_sleep(8); break;
-                        case 3: __builtin_amdgcn_s_sleep(32); break;
-                        case 4: __builtin_amdgcn_s_sleep(64); break;
-                        case 6: __builtin_amdgcn_s_sleep(127); __builtin_amdgcn_s_sleep(127); break;
-                        case 7: __builtin_amdgcn_s_sleep(127); __builtin_amdgcn_s_sleep(127); __builtin_amdgcn_s_sleep(127); __builtin_amdgcn_s_sleep(127); break;
-                        case 2: __builtin_amdgcn_s_sleep(16); break;
-                        default: __builtin_amdgcn_s_sleep(127); break;
-                    }
-                    if (++spins > p.em.spin_limit) { atomicAdd(p.em.range_ctr, 1ull << 40); break; }      // never hang the GPU: report through the range guard
-                }
-            }
-        }
-        __syncthreads();
-        if (lane < 32) {
-            const int c = co_wave + lane;
-            const long long* ap = accb + (size_t)((cw * gpw) + lane / cg) * 2;
-            const double S = (double)__hip_atomic_load(ap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) * (1.0 / 1048576.0);
-            const double SS = (double)__hip_atomic_load(ap + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) * (1.0 / 4096.0);
-            const double cntd = (double)cg * HWo;
-            const double mean = S / cntd;
-            double var = SS / cntd - mean * mean;
-            if (var < 0) var = 0;
-            const float rstd = (float)(1.0 / sqrt(var + 1e-5));
-            float a = rstd * p.em.gamma[c];
-            float b = p.em.beta[c];
-            if (p.em.film) {   // h = GN(h) * (1 + scale) + shift   (unet.py:250-251), gn_prm_kernel's arithmetic
-                const float* f = p.em.film + (p.em.fstep ? (size_t)p.em.fstep->i * p.em.frows : 0) + (size_t)n0 * p.em.film_stride + p.em.film_off;
-                const float sc = 1.0f + f[c];
-                const float sh = f[p.Cout + c];
-                a = a * sc;
-                b = b * sc + sh;
-            }
-            reinterpret_cast<float4*>(wl + 192)[lane] = make_float4((float)mean, a, b, 0.f);
-        }
-        __builtin_amdgcn_wave_barrier();
-        typedef _Float16 half4v __attribute__((ext_vector_type(4)));
-        typedef unsigned int u32x2e __attribute__((ext_vector_type(2)));
-        typedef unsigned int u32x4e __attribute__((ext_vector_type(4)));
+        hop_rendezvous<32>(p, reinterpret_cast<float*>(smem_u), wl, wave, cw, pw, lane, n0, cb, co_wave, 2 * tiles_per_img, HWo);
         const float4* tab = reinterpret_cast<const float4*>(wl + 192);
         bool bad = false;
         // A 16-byte plane entry = 8 channels of one pixel; this lane holds 4 of them (4 half .. 4 half + 3), lane ^ 32 the other 4, for BOTH
         // x-neighbours 2 x + 0 / 2 x + 1.  v_permlane32_swap hands the lower lanes both halves of the even pixel and the upper lanes both
         // halves of the odd one: one 16-byte store per lane, 1 KiB of one output row per instruction.
-        auto norm_split = [&](float x, const float4& m, _Float16& h, _Float16& l) __attribute__((always_inline)) {
-            float v = (x - m.x) * m.y + m.z;
-            v = silu_u(v);
-            bad |= !(fabsf(v) <= 65000.f);
-            v = fminf(fmaxf(v, -65000.f), 65000.f);
-            h = (_Float16)v;
-            l = (_Float16)(v - (float)h);
-        };
 #pragma unroll
         for (int jb = 0; jb < 4; ++jb) {
             float4 m[4];
@@ -379,29 +272,26 @@ __global__ __launch_bounds__(256, 2) void conv_up_kernel(Conv6K p) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     _Float16 th, tl;
-                    norm_split(acc[0][j][jb * 4 + q], m[q], th, tl); h0[q] = th; l0[q] = tl;
-                    norm_split(acc[1][j][jb * 4 + q], m[q], th, tl); h1[q] = th; l1[q] = tl;
+                    norm_split(acc[0][j][jb * 4 + q], m[q], bad, th, tl); h0[q] = th; l0[q] = tl;
+                    norm_split(acc[1][j][jb * 4 + q], m[q], bad, th, tl); h1[q] = th; l1[q] = tl;
                 }
-                const u32x2e e_h = __builtin_bit_cast(u32x2e, h0), o_h = __builtin_bit_cast(u32x2e, h1);
-                const u32x2e e_l = __builtin_bit_cast(u32x2e, l0), o_l = __builtin_bit_cast(u32x2e, l1);
-                u32x4e eh, el;
+                const u32x2 e_h = __builtin_bit_cast(u32x2, h0), o_h = __builtin_bit_cast(u32x2, h1);
+                const u32x2 e_l = __builtin_bit_cast(u32x2, l0), o_l = __builtin_bit_cast(u32x2, l1);
+                u32x4 eh, el;
                 {
                     const auto s0 = __builtin_amdgcn_permlane32_swap(e_h.x, o_h.x, false, false), s1 = __builtin_amdgcn_permlane32_swap(e_h.y, o_h.y, false, false);
                     eh.x = s0[0]; eh.y = s1[0]; eh.z = s0[1]; eh.w = s1[1];
                 }
                 const size_t eo = (((size_t)n0 * p.em.C8 + c8) * HWo + (size_t)(2 * (ty0 + 4 * pw + j) + par) * Wo + (2 * (tx0 + l31) + half)) << 4;
-                *reinterpret_cast<u32x4e*>(p.em.hi + eo) = eh;
+                *reinterpret_cast<u32x4*>(p.em.hi + eo) = eh;
                 if (!X1) {
                     const auto s0 = __builtin_amdgcn_permlane32_swap(e_l.x, o_l.x, false, false), s1 = __builtin_amdgcn_permlane32_swap(e_l.y, o_l.y, false, false);
                     el.x = s0[0]; el.y = s1[0]; el.z = s0[1]; el.w = s1[1];
-                    *reinterpret_cast<u32x4e*>(p.em.lo + eo) = el;
+                    *reinterpret_cast<u32x4*>(p.em.lo + eo) = el;
                 }
             }
         }
-        {
-            const unsigned long long mk = __ballot(bad);
-            if (mk != 0ull && lane == (int)__builtin_ctzll(mk)) atomicAdd(p.em.range_ctr, (unsigned long long)__builtin_popcountll(mk));
-        }
+        range_report(bad, p.em.range_ctr);
         return;
     }
 
@@ -417,8 +307,6 @@ __global__ __launch_bounds__(256, 2) void conv_up_kernel(Conv6K p) {
     float* const out_base = p.out + img0 * HWo;
     const void* const stat_base = do_stat ? (const void*)(p.stat + img0 * p.stat_slots) : (const void*)p.bias;
     const unsigned stat_bytes = do_stat ? 0xFFFFFFFFu : 0u;
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
     float bv[8];
     {
@@ -426,7 +314,7 @@ __global__ __launch_bounds__(256, 2) void conv_up_kernel(Conv6K p) {
 #pragma unroll
         for (int it = 0; it < 8; ++it) bv[it] = as_f32(__builtin_amdgcn_raw_buffer_load_b32(r_bias, (unsigned)(co_wave + it * 4 + rsub) * 4u, 0, 0));
     }
-    static_for_u<0, 4>([&](auto j_c) __attribute__((always_inline)) {
+    static_for<0, 4>([&](auto j_c) __attribute__((always_inline)) {
         constexpr int j = decltype(j_c)::value;
 #pragma unroll
         for (int b = 0; b < 2; ++b)
@@ -451,10 +339,10 @@ __global__ __launch_bounds__(256, 2) void conv_up_kernel(Conv6K p) {
             if (do_stat) {
                 float s1 = (v.x + v.y) + (v.z + v.w);
                 float s2 = (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-                s1 += dpp_row_shr_u<0x111>(s1); s2 += dpp_row_shr_u<0x111>(s2);
-                s1 += dpp_row_shr_u<0x112>(s1); s2 += dpp_row_shr_u<0x112>(s2);
-                s1 += dpp_row_shr_u<0x114>(s1); s2 += dpp_row_shr_u<0x114>(s2);
-                s1 += dpp_row_shr_u<0x118>(s1); s2 += dpp_row_shr_u<0x118>(s2);
+                s1 += dpp_row_shr<0x111>(s1); s2 += dpp_row_shr<0x111>(s2);
+                s1 += dpp_row_shr<0x112>(s1); s2 += dpp_row_shr<0x112>(s2);
+                s1 += dpp_row_shr<0x114>(s1); s2 += dpp_row_shr<0x114>(s2);
+                s1 += dpp_row_shr<0x118>(s1); s2 += dpp_row_shr<0x118>(s2);
                 u32x2 st;
                 st.x = as_u32(s1); st.y = as_u32(s2);
                 const bool wr = q4 == 15 && ok;
@@ -465,8 +353,7 @@ __global__ __launch_bounds__(256, 2) void conv_up_kernel(Conv6K p) {
 #endif
 }
 
-constexpr size_t kConvUpLds = (size_t)4 * ((2 * 10 * 34 + 63) / 64) * 1024;     // two buffers x (hi, lo); the epilogue slabs (34 KiB) alias them
-static_assert(kConvUpLds >= 4 * 32 * 68 * 4 && kConvUpLds >= 4 * 512 * 4 + 2 * 2 * 8 * 2 * 8, "epilogue slabs / hop scratch");
+constexpr size_t kConvUpLds = TileGeo<0>::LDS;      // the source tile is conv7's 8 x 32 one
 static_assert(2 * kConvUpLds <= 160 * 1024, "two workgroups per CU");
 
 template <bool X1, bool EMIT>

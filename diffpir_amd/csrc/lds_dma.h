@@ -1,5 +1,6 @@
-// LDS-DMA idioms shared by the f16 MFMA convolution kernels (conv5.hip, conv6.hip): buffer-descriptor loads straight into LDS and the
-// counted waits that order them.  Device pass only (the buffer-resource builtin type does not exist in hipcc's host pass).
+// LDS-DMA idioms shared by the f16 MFMA convolution kernels (conv5.hip; conv6 / 7 / 8 / 9 / 11 / conv_up through conv_epilogue.h):
+// buffer-descriptor loads straight into LDS and the counted waits that order them.
+// Device pass only (the buffer-resource builtin type does not exist in hipcc's host pass).
 #pragma once
 #if defined(__HIP_DEVICE_COMPILE__)
 namespace dpir {
