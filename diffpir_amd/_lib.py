@@ -308,6 +308,10 @@ def load_debug():
     d.dpir_debug_conv3_plan.restype = C.c_int
     d.dpir_debug_resblock_plan.argtypes = [C.POINTER(ResblockQuery), C.POINTER(ConvKnobs)] + [C.c_int] * 3 + [C.POINTER(ResblockPlan)]
     d.dpir_debug_resblock_plan.restype = C.c_int
+    d.dpir_debug_fft_plan.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_void_p]
+    d.dpir_debug_fft_plan.restype = C.c_int
+    d.dpir_debug_prox_layout.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int)] * 4 + [C.c_char_p, C.c_int]
+    d.dpir_debug_prox_layout.restype = C.c_int
     d.dpir_debug_attention.argtypes = [C.c_void_p, C.POINTER(AttentionDesc)]
     d.dpir_debug_attention.restype = C.c_int
     d.dpir_debug_groupnorm.argtypes = [C.c_void_p, C.POINTER(GroupNormDesc)]

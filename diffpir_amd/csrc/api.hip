@@ -208,7 +208,7 @@ int dpir_create(int device, dpir_engine** out) {
     if (hipMalloc((void**)&e->range_ctr, sizeof(unsigned long long)) != hipSuccess ||
         hipMemset(e->range_ctr, 0, sizeof(unsigned long long)) != hipSuccess) { (void)hipStreamDestroy(e->stream); delete e; return DPIR_ERR_NOMEM; }
     e->cus = prop.multiProcessorCount;
-    if (const char* ev = getenv("DPIR_PROX_MODE")) { const int m = atoi(ev); if (m == 0 || m == 1) e->prox_mode = m; }
+    if (const char* ev = getenv("DPIR_PROX_MODE")) { const int m = atoi(ev); if (m >= 0 && m <= 3) e->prox_mode = m; }
     *out = e;
     return DPIR_OK;
 }
@@ -435,7 +435,7 @@ int dpir_prox_read(dpir_engine* e, const dpir_prox* p, int which, void* host_dst
 }
 
 int dpir_set_prox_launch(dpir_engine* e, int mode) {
-    if (!e || (mode != 0 && mode != 1)) return fail(e, invalid("dpir_set_prox_launch: mode must be 0 or 1"));
+    if (!e || mode < 0 || mode > 3) return fail(e, invalid("dpir_set_prox_launch: mode must be 0, 1, 2 or 3"));
     (void)hipSetDevice(e->device);
     if (mode != e->prox_mode) { (void)hipStreamSynchronize(e->stream); e->invalidate_graphs(); }
     e->prox_mode = mode;

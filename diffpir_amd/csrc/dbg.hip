@@ -73,3 +73,40 @@ extern "C" int dpir_debug_victim_alu(dpir_engine* e, int mode, int blocks, int i
     (void)hipFree(d);
     return rc;
 }
+
+// The mixed-radix plan and the prox layout decision on their own (csrc/fft_plan.h, prox_layout_of / prox_check): no engine, no GPU.
+extern "C" int dpir_debug_fft_plan(int N, int sf, int* radices, int radix_cap, int* n_radices, int* perm) {
+    if (!n_radices) return DPIR_ERR_INVALID;
+    *n_radices = 0;
+    if (N < 2 || sf < 1 || N % sf) return DPIR_ERR_INVALID;
+    dpir::FftMixedPlan p;
+    if (!dpir::fft_plan_make(N, sf, &p)) return DPIR_ERR_UNSUPPORTED;
+    *n_radices = p.stages;
+    for (int i = 0; i < p.stages && radices && i < radix_cap; ++i) radices[i] = p.radix[i];
+    if (perm) {
+        std::vector<int> v;
+        dpir::fft_plan_perm(p, v);
+        for (int i = 0; i < N; ++i) perm[i] = v[i];
+    }
+    return DPIR_OK;
+}
+
+extern "C" int dpir_debug_prox_layout(int H, int W, int sf, int prox_mode, int* layout, int* strip_width, int* strip_count, int* strip_last,
+                                      char* msg, int msg_cap) {
+    if (!layout) return DPIR_ERR_INVALID;
+    const dpir::ProxLayout L = dpir::prox_layout_of(prox_mode, H, W, sf);
+    *layout = (int)L;
+    if (strip_width) *strip_width = 0;
+    if (strip_count) *strip_count = 0;
+    if (strip_last) *strip_last = 0;
+    const dpir::Status s = dpir::prox_check(L, sf, 1, H, W);
+    if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", s.msg.c_str());
+    if (!s.ok()) return s.code;
+    if (L == dpir::ProxLayout::FullDigitrev || L == dpir::ProxLayout::FullBitrev) {      // the column strips of the two full layouts (fft.hip: 16)
+        const dpir::FftStrips st = L == dpir::ProxLayout::FullDigitrev ? dpir::fft_strips(W, sf) : dpir::FftStrips{16, W / 16, 16};
+        if (strip_width) *strip_width = st.width;
+        if (strip_count) *strip_count = st.count;
+        if (strip_last) *strip_last = st.last;
+    }
+    return DPIR_OK;
+}

@@ -1,6 +1,7 @@
-// Declarations for the elem.hip / degrade.hip / fft.hip / fft2.hip / fft4.hip launchers (the FFT prox above them: prox.h).
+// Declarations for the elem.hip / degrade.hip / fft.hip / fft2.hip / fft4.hip / fft_mixed.hip launchers (the FFT prox above them: prox.h).
 #pragma once
 #include "common.h"
+#include "fft_plan.h"
 
 namespace dpir {
 
@@ -93,6 +94,17 @@ Status launch_ifft_rows_real(hipStream_t s, const FftPlan& pw, const float2* buf
 Status launch_psf_embed(hipStream_t s, const float* k, int kh, int kw, float2* otf, int B, int H, int W);
 Status launch_upsample_embed(hipStream_t s, const float* y, int sf, float2* out, int P, int h, int w);
 Status launch_precalc_finish(hipStream_t s, const float2* FB, float2* FBFy_inout, float* F2B, int B, int H, int W);
+
+// fft_mixed.hip: the same three passes with mixed-radix transforms, any H in [8, 1024] and W in [8, 2048] without a prime factor above 31, any sf <= 16
+// that divides both; full c2c planes, digit-reversed along both axes (fft_plan.h).  tw = W_N^m table (N entries, device)
+struct MixedFft { FftMixedPlan plan; const float2* tw = nullptr; };
+// rows forward in place; real_in != null: the row source is (real_in*pa+pb)*pm (sp: pm = sp->tau; pil with sp: the row's image's tau)
+Status launch_mixed_rows_fwd(hipStream_t s, const MixedFft& pw, float2* buf, const float* real_in, float pa, float pb, float pm, int P, int H, int W,
+                             const StepDev* sp = nullptr, const LoopDev* pil = nullptr);
+Status launch_mixed_cols(hipStream_t s, const MixedFft& ph, float2* buf, int P, int H, int W, int sf);         // columns forward only (pre_calculate)
+Status launch_mixed_cols_solve(hipStream_t s, const MixedFft& ph, float2* buf, const SolveArgs& a, int B, int H, int W);
+Status launch_mixed_rows_inv(hipStream_t s, const MixedFft& pw, const float2* buf, float* out, float scale, float oa, float ob, const float* blend_base,
+                             float g, int P, int H, int W);
 
 // fft2.hip: half-spectrum register FFT path (sf = 1, N = 64 / 256).  twN = W_N^m table (N entries, device)
 bool fft2_supported(int H, int W, int sf);

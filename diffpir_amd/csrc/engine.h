@@ -134,8 +134,10 @@ struct dpir_engine {
     }
     unsigned long long* range_ctr = nullptr;     // f16x3 operand range guard (act.hip range_report), device
     // how the half-spectrum data step is run (dpir_set_prox_launch; read by prox_layout only): 1 = wave-per-transform kernels on a column-major spectrum (fft4.hip;
-    // 256 x 256 and 512 x 512, default), 0 = the two-pass register kernels (fft2.hip; every other size always).  cus: CU count of the device.
-    int prox_mode = 1; int cus = 256;
+    // 256 x 256 and 512 x 512), 0 = the two-pass register kernels (fft2.hip; every other size always).  Bit 1 (modes 2 and 3; 3 is the default): what the
+    // power-of-two families refuse goes to the mixed-radix kernels (fft_mixed.hip); without it (modes 0 and 1) such shapes stay DPIR_ERR_UNSUPPORTED.
+    // cus: CU count of the device.
+    int prox_mode = 3; int cus = 256;
     // conv7's fused hop (Conv6Emit) is an inter-workgroup wait; when it times out (the GPU is shared with other engines / processes) the
     // engine does not fail: it switches the hop off for its lifetime and re-runs what the time-out invalidated -- the restoration loop
     // (dpir_run_loop) or the ONE eager forward issued since the last synchronisation (replay_last); see dpir_check_range

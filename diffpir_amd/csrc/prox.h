@@ -14,7 +14,8 @@ namespace dpir {
 enum class ProxLayout {
     FullBitrev,   // full c2c planes [H][W], bit-reversed along both axes (fft.hip: the general path)
     HalfRows,     // half spectrum, row-major [H][WP], WP = W/2 + 1 padded to the 16-column strip (fft2.hip)
-    HalfCols      // half spectrum, column-major [WP slots][H positions], no padding (fft4.hip: one wave per transform)
+    HalfCols,     // half spectrum, column-major [WP slots][H positions], no padding (fft4.hip: one wave per transform)
+    FullDigitrev  // full c2c planes [H][W], digit-reversed along both axes by the mixed-radix plans of H and W (fft_mixed.hip: any size, any sf)
 };
 // the half layouts store the columns alias-grouped when sf > 1: slot sf q + b holds alias b of fold group q (fft2.hip)
 
@@ -26,7 +27,8 @@ struct ProxState {   // dpir_prox
     float* invW = nullptr; // half layouts, sf > 1: alias mean of F2B [B][H/sf][W/sf/2+1]
     const int* slot_col = nullptr; const int* col_slot = nullptr;     // half layouts, sf > 1: device slot maps (engine-owned, ProxCache)
     const std::vector<int>* h_col_slot = nullptr;                     // host copy (prox_read)
-    bool half() const { return layout != ProxLayout::FullBitrev; }
+    const std::vector<int>* h_perm_h = nullptr; const std::vector<int>* h_perm_w = nullptr;   // FullDigitrev: stored position of frequency f (host, ProxCache)
+    bool half() const { return layout == ProxLayout::HalfRows || layout == ProxLayout::HalfCols; }
 };
 
 // Engine-owned tables of the prox kernels, built on first use and freed with the engine
@@ -34,7 +36,10 @@ struct ProxCache {
     struct SlotMap { int* slot_col = nullptr; int* col_slot = nullptr; std::vector<int> h_slot_col, h_col_slot; };
     std::map<int, float2*> tables;                                // W_N^m (N entries) [+ fft4_wave.h's per-lane constants]; fft.hip's plans read the first half
     std::map<std::tuple<int, int, ProxLayout>, SlotMap> maps;     // (N, sf, layout) -> alias-grouped column permutation of a half layout
+    struct Mixed { FftMixedPlan plan; std::vector<int> perm; };
+    std::map<std::pair<int, int>, Mixed> mixed;                   // (N, sf) -> radix list and storage permutation (fft_plan.h)
     Status plan(int N, FftPlan* out);
+    Status mixed_plan(int N, int sf, MixedFft* out, const std::vector<int>** perm = nullptr);
     Status table(int N, const float2** out);
     Status map(int N, int sf, ProxLayout layout, const SlotMap** out);
     void release();
@@ -44,6 +49,9 @@ int fft2_padded_width(int W);     // HalfRows: stored row length (fft2.hip's lau
 
 // The layout a (H, W, sf) problem is stored in on this engine (dpir_set_prox_launch picks between the two half layouts where both exist)
 ProxLayout prox_layout(const dpir_engine* e, int H, int W, int sf);
+// the same decision from the launch mode alone (dpir_engine::prox_mode), and the shape check that goes with it: no engine, no GPU
+ProxLayout prox_layout_of(int prox_mode, int H, int W, int sf);
+Status prox_check(ProxLayout layout, int sf, int B, int H, int W);
 // *st already fits (B, H, W, sf, layout), or it is released (after a stream synchronisation if it held spectra) and allocated anew; *reallocated tells which.
 // The shape checks come first: an unsupported shape leaves *st as it was.  A failed allocation leaves it released.
 Status prox_ensure(dpir_engine* e, int sf, int B, int H, int W, ProxState* st, bool* reallocated = nullptr);

@@ -1,7 +1,13 @@
 // FFT data step of the restoration (pre_calculate / data_solution, utils/utils_sisr.py:9-19, 65-95) above the kernel files: which layout the spectra
 // of a (H, W, sf) problem are stored in (prox_layout -- the one place that asks fft2_supported / fft4_supported / the engine's prox mode), their
 // allocation, the engine-owned tables, pre_calculate, the apply on each layout, the loop's fused step and the host reader.  The kernels live in
-// fft.hip (FullBitrev), fft2.hip (HalfRows) and fft4.hip (HalfCols); what the two half layouts share beyond the passes (slot map, alias fold) is here.
+// fft.hip (FullBitrev), fft2.hip (HalfRows), fft4.hip (HalfCols) and fft_mixed.hip (FullDigitrev); what the two half layouts share beyond the passes
+// (slot map, alias fold) is here.
+//
+// Shapes: 64^2, 256^2 and 512^2 at sf 1 / 2 / 4 take a half layout; every other power-of-two H in [16, 1024] x W in [16, 2048] at sf 1 / 2 / 4 / 8 /
+// 16 takes FullBitrev; whatever those three refuse -- H or W no power of two, or another sf -- takes, under launch modes 2 and 3 (3 is the default;
+// modes 0 and 1 keep refusing it with DPIR_ERR_UNSUPPORTED, dpir_set_prox_launch), FullDigitrev: H in [8, 1024], W in [8, 2048], no
+// prime factor above 31, any sf in [1, 16] that divides both (fft_plan.h).  Every shape the first three served keeps its layout and its kernels.
 #include "engine.h"
 #include "fft4_body.h"
 #include <math.h>
@@ -10,15 +16,20 @@
 namespace dpir {
 
 // ------------------------------------------------------------------------------------------ layout
-ProxLayout prox_layout(const dpir_engine* e, int H, int W, int sf) {
-    if (!fft2_supported(H, W, sf)) return ProxLayout::FullBitrev;
-    return e->prox_mode == 1 && fft4_supported(H, W, sf) ? ProxLayout::HalfCols : ProxLayout::HalfRows;
+static bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+ProxLayout prox_layout_of(int prox_mode, int H, int W, int sf) {
+    if (fft2_supported(H, W, sf)) return (prox_mode & 1) && fft4_supported(H, W, sf) ? ProxLayout::HalfCols : ProxLayout::HalfRows;
+    const bool sf_pow2 = sf == 1 || sf == 2 || sf == 4 || sf == 8 || sf == 16;
+    // bit 1 of the launch mode admits the mixed-radix layout; without it the generic power-of-two kernels are asked, and refuse, as before.
+    // prox_check refuses a non-divisor on every layout
+    return (pow2(H) && pow2(W) && sf_pow2) || !(prox_mode & 2) ? ProxLayout::FullBitrev : ProxLayout::FullDigitrev;
 }
+ProxLayout prox_layout(const dpir_engine* e, int H, int W, int sf) { return prox_layout_of(e->prox_mode, H, W, sf); }
 int fft2_padded_width(int W) { const int cs = 16; return (W / 2 + 1 + cs - 1) / cs * cs; }   // multiple of the column strip
 // ProxState::WP.  HalfCols: W/2 + 1 stored columns for sf = 1, sf * (W/sf/2 + 1) alias-grouped slots otherwise; the position of row u inside one: pos4(u) (fft4_body.h)
 static int stored_width(ProxLayout L, int W, int sf) {
     if (L == ProxLayout::HalfCols) return sf == 1 ? W / 2 + 1 : sf * (W / sf / 2 + 1);
-    return L == ProxLayout::HalfRows ? fft2_padded_width(W) : W;
+    return L == ProxLayout::HalfRows ? fft2_padded_width(W) : W;      // both full layouts store W columns
 }
 
 // sf > 1 on a half layout: slot -> (column | mirrored << 16) or -1 (padding), and column -> canonical slot, for `slots` stored columns
@@ -96,6 +107,21 @@ Status ProxCache::plan(int N, FftPlan* out) {
     return Status{};
 }
 
+Status ProxCache::mixed_plan(int N, int sf, MixedFft* out, const std::vector<int>** perm) {
+    auto it = mixed.find({N, sf});
+    if (it == mixed.end()) {
+        Mixed m;
+        if (!fft_plan_make(N, sf, &m.plan)) return Status{DPIR_ERR_UNSUPPORTED, "mixed fft: no plan for this length and sf"};
+        fft_plan_perm(m.plan, m.perm);
+        it = mixed.emplace(std::make_pair(N, sf), std::move(m)).first;
+    }
+    const float2* tw = nullptr;
+    DPIR_TRY(table(N, &tw));
+    out->plan = it->second.plan; out->tw = tw;
+    if (perm) *perm = &it->second.perm;
+    return Status{};
+}
+
 Status ProxCache::map(int N, int sf, ProxLayout layout, const SlotMap** out) {
     auto key = std::make_tuple(N, sf, layout);
     auto it = maps.find(key);
@@ -117,12 +143,18 @@ void ProxCache::release() {
 
 // ------------------------------------------------------------------------------------------ shape checks, allocation
 // The generic kernels (fft.hip) hold a 16-column strip of H + 1 rows in LDS: H <= 1024 (135 KB at 1024; 2048 would need 264 KB of the 160 KB per CU).
-static Status prox_check(ProxLayout layout, int sf, int B, int H, int W) {
+// The mixed-radix kernels (fft_mixed.hip) hold the same strip (at most 16 columns) and lift the power-of-two conditions: fft_mixed_refusal.
+Status prox_check(ProxLayout layout, int sf, int B, int H, int W) {
     if (B < 1) return invalid("pre_calculate: B must be >= 1");
     if (sf < 1 || H % sf || W % sf) return invalid("pre_calculate: image size not divisible by sf");
+    if (layout == ProxLayout::FullDigitrev) {
+        char msg[192];
+        bool unsupported = true;
+        if (fft_mixed_refusal(H, W, sf, &unsupported, msg, sizeof msg)) return Status{unsupported ? DPIR_ERR_UNSUPPORTED : DPIR_ERR_INVALID, msg};
+        return Status{};
+    }
     if (layout != ProxLayout::FullBitrev) return Status{};
     if (sf != 1 && sf != 2 && sf != 4 && sf != 8 && sf != 16) return Status{DPIR_ERR_UNSUPPORTED, "fft prox: sf must be 1, 2, 4, 8 or 16"};
-    auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
     if (!pow2(H) || !pow2(W) || H < 16 || W < 16 || H > 1024 || W > 2048)
         return Status{DPIR_ERR_UNSUPPORTED, "fft prox: H must be a power of two in [16, 1024] and W one in [16, 2048]"};
     return Status{};
@@ -148,6 +180,11 @@ static Status prox_alloc(dpir_engine* e, ProxState* st) {
         hipMalloc((void**)&st->F2B, B * hw * sizeof(float)) != hipSuccess ||
         hipMalloc((void**)&st->FBFy, 3 * B * hw * sizeof(float2)) != hipSuccess)
         return Status{DPIR_ERR_NOMEM, "pre_calculate: hipMalloc failed"};
+    if (st->layout == ProxLayout::FullDigitrev) {
+        MixedFft f;
+        DPIR_TRY(e->prox_cache.mixed_plan(st->H, st->sf, &f, &st->h_perm_h));
+        DPIR_TRY(e->prox_cache.mixed_plan(st->W, st->sf, &f, &st->h_perm_w));
+    }
     if (st->half() && st->sf > 1) {
         const ProxCache::SlotMap* m = nullptr;
         DPIR_TRY(e->prox_cache.map(st->W, st->sf, st->layout, &m));
@@ -229,6 +266,19 @@ Status prox_precalc(dpir_engine* e, const float* y, const float* k, int kh, int 
         if (sf > 1) DPIR_TRY(half_fold(s, *st));
         return Status{};
     }
+    if (st->layout == ProxLayout::FullDigitrev) {      // the same passes as below on the mixed-radix plans of H and W
+        MixedFft mh, mw;
+        DPIR_TRY(e->prox_cache.mixed_plan(H, sf, &mh));
+        DPIR_TRY(e->prox_cache.mixed_plan(W, sf, &mw));
+        DPIR_TRY(launch_psf_embed(s, k, kh, kw, st->FB, B, H, W));
+        DPIR_TRY(launch_mixed_rows_fwd(s, mw, st->FB, nullptr, 1.f, 0.f, 1.f, B, H, W));
+        DPIR_TRY(launch_mixed_cols(s, mh, st->FB, B, H, W, sf));
+        DPIR_TRY(launch_upsample_embed(s, y, sf, st->FBFy, B * 3, H / sf, W / sf));
+        DPIR_TRY(launch_mixed_rows_fwd(s, mw, st->FBFy, nullptr, 1.f, 0.f, 1.f, B * 3, H, W));
+        DPIR_TRY(launch_mixed_cols(s, mh, st->FBFy, B * 3, H, W, sf));
+        DPIR_TRY(launch_precalc_finish(s, st->FB, st->FBFy, st->F2B, B, H, W));
+        return Status{};
+    }
     FftPlan ph, pw;
     DPIR_TRY(e->prox_cache.plan(H, &ph));
     DPIR_TRY(e->prox_cache.plan(W, &pw));
@@ -261,6 +311,8 @@ static unsigned brev(unsigned v, int bits) {
 // where element (u, v) of a natural-order plane is stored inside its H * WP plane, and whether the stored value is its conjugate
 static size_t stored_index(const ProxState& st, int u, int v, bool* conj) {
     *conj = false;
+    if (st.layout == ProxLayout::FullDigitrev)      // digit-reversed along both axes (fft_plan.h): natural[u][v] = stored[perm_H(u)][perm_W(v)]
+        return (size_t)(*st.h_perm_h)[u] * st.W + (*st.h_perm_w)[v];
     if (!st.half())      // bit-reversed along both axes (fft.hip): natural[u][v] = stored[brev(u)][brev(v)]
         return (size_t)brev(u, ilog2u(st.H)) * st.W + brev(v, ilog2u(st.W));
     // natural[u][v] = stored[u][v] for v <= W/2, conj(stored[(H-u)%H][W-v]) beyond (Hermitian spectra of real signals)
@@ -322,19 +374,30 @@ Status prox_data_solution(dpir_engine* e, const ProxState& st, const float* x, f
     if (pil && !sp) return invalid("data_solution: the per-image form reads the device step block");
     if (st.half())
         return prox_passes(e, st, ProxPassArgs{x, pa, pb, alpha, sp, RowsFuse{nullptr, 0, pil}, out, oa, ob, (blend_base && g != 1.0f) ? blend_base : nullptr, g, RenoiseFuse{}});
-    FftPlan ph, pw;
-    DPIR_TRY(e->prox_cache.plan(st.H, &ph));
-    DPIR_TRY(e->prox_cache.plan(st.W, &pw));
     float2* buf = nullptr;
     DPIR_TRY(e->ws.getT("prox#buf", (size_t)st.B * 3 * st.H * st.W, &buf));
     hipStream_t s = e->stream;
+    const float scale_hw = 1.0f / ((float)st.H * (float)st.W);
+    if (st.layout == ProxLayout::FullDigitrev) {
+        MixedFft mh, mw;
+        DPIR_TRY(e->prox_cache.mixed_plan(st.H, st.sf, &mh));
+        DPIR_TRY(e->prox_cache.mixed_plan(st.W, st.sf, &mw));
+        ProfScope ps(&e->prof, PC_FFT);
+        DPIR_TRY(launch_mixed_rows_fwd(s, mw, buf, x, pa, pb, alpha, st.B * 3, st.H, st.W, sp, pil));
+        SolveArgs a{st.FB, st.F2B, st.FBFy, alpha, st.sf, sp};
+        a.pil = pil;
+        DPIR_TRY(launch_mixed_cols_solve(s, mh, buf, a, st.B, st.H, st.W));
+        return launch_mixed_rows_inv(s, mw, buf, out, scale_hw, oa, ob, blend_base, g, st.B * 3, st.H, st.W);
+    }
+    FftPlan ph, pw;
+    DPIR_TRY(e->prox_cache.plan(st.H, &ph));
+    DPIR_TRY(e->prox_cache.plan(st.W, &pw));
     ProfScope ps(&e->prof, PC_FFT);
     DPIR_TRY(launch_fft_rows_real3(s, pw, buf, x, pa, pb, alpha, st.B * 3, st.H, st.W, sp, pil));
     SolveArgs a{st.FB, st.F2B, st.FBFy, alpha, st.sf, sp};
     a.pil = pil;
     DPIR_TRY(launch_fft_cols_solve(s, ph, buf, a, st.B, st.H, st.W));
-    float scale = 1.0f / ((float)st.H * (float)st.W);
-    DPIR_TRY(launch_ifft_rows_real(s, pw, buf, out, scale, oa, ob, blend_base, g, st.B * 3, st.H, st.W));
+    DPIR_TRY(launch_ifft_rows_real(s, pw, buf, out, scale_hw, oa, ob, blend_base, g, st.B * 3, st.H, st.W));
     return Status{};
 }
 

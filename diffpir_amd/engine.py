@@ -172,8 +172,10 @@ class Engine:
 
     def set_prox_launch(self, mode):
         """'wave' / 1: wave-per-transform kernels on a column-major spectrum (csrc/fft4.hip, 256 x 256 and 512 x 512; default); 'launches' / 0: the two-pass register
-        kernels (csrc/fft2.hip).  Takes effect at the next pre_calculate / loop call."""
-        m = {"wave": 1, "launches": 0}.get(mode, mode)
+        kernels (csrc/fft2.hip).  'wave+anysize' / 3 (the engine's default) and 'launches+anysize' / 2: the same, plus the mixed-radix kernels
+        (csrc/fft_mixed.hip) for sizes that are no power of two and for any integer sf; 0 and 1 are the strict forms, under which such shapes are refused
+        as unsupported.  Takes effect at the next pre_calculate / loop call."""
+        m = {"wave": 1, "launches": 0, "wave+anysize": 3, "launches+anysize": 2}.get(mode, mode)
         self._check(self.lib.dpir_set_prox_launch(self.h, int(m)))
 
     def enable_grad(self, on=True):

@@ -1,6 +1,6 @@
 """YAML-driven batched driver with the reference's config surface (main_ddpir.py:127-169, 172-599), on the engine.
 
-    python -m diffpir_amd.main_ddpir --opt <config.yaml> [--synthetic N] [--device 0] [--num-gpus G]
+    python -m diffpir_amd.main_ddpir --opt <config.yaml> [--synthetic N] [--synthetic-size HxW] [--device 0] [--num-gpus G]
 
 --num-gpus G (or the YAML key `num_gpus`) re-launches the driver as G processes, one per GPU (torch.distributed.run); every batch
 is then block-partitioned over the ranks (dist.restore_sharded) and one all-gather of the uint8 results ends it.
@@ -266,22 +266,48 @@ def log_batch(number, psnr, lpips_score, ave_lpips):
         log.info("batch%4d--> PSNR: %.4fdB; LPIPS: %.4f; ave LPIPS: %.4f", number, psnr, lpips_score, ave_lpips)
 
 
-def load_images(config, n_synth):
-    """uint8 [N,H,W,3] (what util.imread_uint returns, main_ddpir.py:84) + names.  testsets/<testset_name>/*.png via PIL when
-    present, else synthetic."""
+def modcrop(img, sf):
+    """util.modcrop (utils_image.py:538, main_ddpir.py:82): the top-left H - H % sf by W - W % sf of an image [H,W] or [H,W,C] (here also a
+    stack [N,H,W,C]), copied."""
+    a = np.asarray(img)
+    if a.ndim not in (2, 3, 4):
+        raise ValueError(f"Wrong img ndim: [{a.ndim}].")
+    ax = 1 if a.ndim == 4 else 0
+    H, W = a.shape[ax], a.shape[ax + 1]
+    idx = [slice(None)] * a.ndim
+    idx[ax], idx[ax + 1] = slice(0, H - H % sf), slice(0, W - W % sf)
+    return np.copy(a[tuple(idx)])
+
+
+def parse_size(text):
+    """--synthetic-size: 'HxW' (or one number for a square) -> (H, W)"""
+    parts = str(text).lower().split("x")
+    if len(parts) not in (1, 2) or not all(p.strip().isdigit() for p in parts):
+        raise argparse.ArgumentTypeError(f"expected HxW, e.g. 192x320 (got {text!r})")
+    h, w = int(parts[0]), int(parts[-1])
+    if h < 1 or w < 1:
+        raise argparse.ArgumentTypeError(f"expected a positive HxW (got {text!r})")
+    return h, w
+
+
+def load_images(config, n_synth, synth_size=(256, 256)):
+    """uint8 [N,H,W,3] (what util.imread_uint returns, main_ddpir.py:84) + names, each image cropped to a multiple of sf (util.modcrop,
+    main_ddpir.py:82).  testsets/<testset_name>/*.png via PIL when present, else synthetic."""
+    sf = int(config.get("sf", 1) or 1)
     d = os.path.join(config.get("cwd", "") or "", "testsets", config.testset_name)
     paths = sorted(glob.glob(os.path.join(d, "*.png")) + glob.glob(os.path.join(d, "*.jpg")))
     if paths and not n_synth:
         try:
             from PIL import Image
-            imgs = [np.asarray(Image.open(p).convert("RGB"), np.uint8) for p in paths]
+            imgs = [modcrop(np.asarray(Image.open(p).convert("RGB"), np.uint8), sf) for p in paths]
             return np.stack(imgs), [os.path.basename(p) for p in paths]
         except Exception as ex:   # pragma: no cover
             log.warning("cannot read %s (%s); using synthetic images", d, ex)
     n = n_synth or 16
-    log.info("no dataset on disk: using %d synthetic 256x256 ground-truth images", n)
-    f = synth.smooth_images(n, 256, 256, 42)
-    return np.ascontiguousarray((f * 255.0).round().astype(np.uint8).transpose(0, 2, 3, 1)), [f"synth_{i:04d}.png" for i in range(n)]
+    sh, sw = synth_size
+    log.info("no dataset on disk: using %d synthetic %dx%d ground-truth images", n, sh, sw)
+    f = synth.smooth_images(n, sh, sw, 42)
+    return modcrop(np.ascontiguousarray((f * 255.0).round().astype(np.uint8).transpose(0, 2, 3, 1)), sf), [f"synth_{i:04d}.png" for i in range(n)]
 
 
 _MAT_CACHE = {}
@@ -452,6 +478,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--opt", type=str, required=True, help="Path to option YAML file.")
     ap.add_argument("--synthetic", type=int, default=0, help="use N synthetic images instead of the testset")
+    ap.add_argument("--synthetic-size", type=parse_size, default=(256, 256), metavar="HxW", help="size of the synthetic images (default 256x256)")
     ap.add_argument("--device", type=int, default=None, help="HIP ordinal (default: LOCAL_RANK, else 0)")
     ap.add_argument("--max-sweeps", type=int, default=0)
     ap.add_argument("--num-gpus", type=int, default=0, help="shard every batch over this many GPUs (one process per GPU)")
@@ -494,7 +521,7 @@ def main(argv=None):
 
     with_lpips = setup_lpips(eng, config)
     ncol = 3 if with_lpips else 2
-    imgs, names = load_images(config, args.synthetic)
+    imgs, names = load_images(config, args.synthetic, args.synthetic_size)
     with_fid = setup_fid(eng, config, len(imgs))
     fid_gt, fids = {}, []                  # ground-truth feature rows per batch (computed at the first sweep point, reused by the others); FID per point
     use_graph = bool(config.get("engine_graph", True))

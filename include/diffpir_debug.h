@@ -181,6 +181,16 @@ typedef struct dpir_debug_groupnorm_desc {
     uint64_t guard_bad_out;
 } dpir_debug_groupnorm_desc;
 int dpir_debug_groupnorm(dpir_engine* e, dpir_debug_groupnorm_desc* d);
+/* The plan of the mixed-radix FFT prox (csrc/fft_plan.h) on its own: no engine, no GPU.
+ * dpir_debug_fft_plan: the radix list of an N-point transform in forward order (up to radix_cap written, *n_radices = how many there are; the
+ *   trailing ones multiply to sf) and, when perm != NULL, perm[f] = the stored position of frequency f (N ints).  DPIR_ERR_INVALID when sf does not
+ *   divide N, DPIR_ERR_UNSUPPORTED when N has a prime factor above 31.
+ * dpir_debug_prox_layout: the layout dpir_prox_fft_precalc stores a (H, W, sf) problem in under launch mode prox_mode (dpir_set_prox_launch, 0 .. 3) --
+ *   0 FullBitrev, 1 HalfRows, 2 HalfCols, 3 FullDigitrev -- and, for the two full layouts, the column strips of the solve: strip_count strips of
+ *   strip_width columns over [0, W), the last one strip_last wide.  A shape no kernel serves returns the error code dpir_prox_fft_precalc returns
+ *   for it, with its text in msg (msg_cap bytes; may be NULL). */
+int dpir_debug_fft_plan(int N, int sf, int* radices, int radix_cap, int* n_radices, int* perm);
+int dpir_debug_prox_layout(int H, int W, int sf, int prox_mode, int* layout, int* strip_width, int* strip_count, int* strip_last, char* msg, int msg_cap);
 #ifdef __cplusplus
 }
 #endif

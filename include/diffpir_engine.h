@@ -144,10 +144,11 @@ int dpir_unet_read_tap(dpir_engine* e, const char* layer, float* host_dst, size_
 /* ---- data-fidelity operators ------------------------------------------------------------- */
 /* Replaces sr.pre_calculate(y, k, sf) (utils/utils_sisr.py:78-95): y_dev [B,3,H/sf,W/sf] in [0,1],
  * k_dev [B,1,kh,kw]; builds FB, F2B, FBFy (full c2c spectra of size HxW) in an engine-owned object.
- * Supported: 256 x 256 and 512 x 512 and 64 x 64 with sf 1, 2 or 4; otherwise H a power of two in [16, 1024], W one in [16, 2048] and
- * sf 1, 2, 4, 8 or 16 (the generic kernels of csrc/fft.hip: H is bounded by the LDS of their column pass).  Checked here before anything
- * is allocated or launched: DPIR_ERR_INVALID when sf does not divide H and W, B < 1, or the PSF is empty or larger than the image;
- * DPIR_ERR_UNSUPPORTED for any other sf or image size.  dpir_run_loop applies the same shape checks before it allocates the spectra (after
+ * Supported: 256 x 256 and 512 x 512 and 64 x 64 with sf 1, 2 or 4; H a power of two in [16, 1024], W one in [16, 2048] and sf 1, 2, 4, 8
+ * or 16 (the generic kernels of csrc/fft.hip: H is bounded by the LDS of their column pass); and, where H or W is no power of two or sf is
+ * another integer, any H in [8, 1024] and W in [8, 2048] without a prime factor above 31 with any sf in [1, 16] (the mixed-radix kernels of
+ * csrc/fft_mixed.hip; launch modes 2 and 3 of dpir_set_prox_launch, 3 being the default -- under modes 0 and 1 these shapes are DPIR_ERR_UNSUPPORTED).  Checked here before anything is allocated or launched: DPIR_ERR_INVALID when sf does not divide H and W, B < 1, or
+ * the PSF is empty or larger than the image; DPIR_ERR_UNSUPPORTED for any other sf or image size (the message names a prime factor above 31).  dpir_run_loop applies the same shape checks before it allocates the spectra (after
  * its own workspaces) and the PSF check before the first prox launch (after the loop's initialisation launches). */
 int dpir_prox_fft_precalc(dpir_engine* e, const float* y_dev, const float* k_dev, int kh, int kw,
                           int sf, int B, int H, int W, dpir_prox** out);
@@ -164,11 +165,14 @@ int dpir_prox_fft_apply(dpir_engine* e, const dpir_prox* p, float* x0_dev, float
  * (use_graph 0) or ONE captured graph of the n applies (use_graph 1: how dpir_run_loop replays the step; no host launch cost, no event record between
  * applies) -> device microseconds per apply, launch boundaries included.  x0 is overwritten n + 1 (+ n) times. */
 int dpir_prox_fft_apply_timed(dpir_engine* e, const dpir_prox* p, float* x0_dev, float tau, float guidance, int n, int use_graph, float* us_per_apply);
-/* Which kernels run the half-spectrum data_solution (utils/utils_sisr.py:65-75).  mode 1 (default; env DPIR_PROX_MODE=0 selects 0 at dpir_create), 256 x 256
+/* Which kernels run the half-spectrum data_solution (utils/utils_sisr.py:65-75).  mode 1 (and 3, the default), 256 x 256
  * and 512 x 512: one wave per 256- / 512-point transform (64 lanes x 4 / 8 points, permlane-swap / DPP register transposes, a wave-private LDS tile, no workgroup
  * barrier inside a transform) on a COLUMN-major half spectrum, csrc/fft4.hip.  mode 0, and every other size: the two-pass register kernels of csrc/fft2.hip (a thread holds
  * 16 points) on the row-major padded spectrum.  Same mathematics, results within a few 1e-6 of each other.  A dpir_prox keeps the layout of the mode it
- * was created in (dpir_prox_read returns natural order either way).  Drops the captured step graphs. */
+ * was created in (dpir_prox_read returns natural order either way).  Drops the captured step graphs.
+ * Modes 2 and 3 are 0 and 1 plus the mixed-radix kernels (csrc/fft_mixed.hip) for every shape the power-of-two families refuse: H or W no power of
+ * two, or sf not 1, 2, 4, 8 or 16.  3 is the default (env DPIR_PROX_MODE = 0 .. 3 at dpir_create).  Modes 0 and 1 are the strict forms: only the
+ * power-of-two families run and any other shape is DPIR_ERR_UNSUPPORTED, as it was before the mixed-radix kernels existed. */
 int dpir_set_prox_launch(dpir_engine* e, int mode);
 /* Replaces main_ddpir.py:392-394: x0_p = (m*(2y-1)+tau*x0)/(m+tau); x0 += g*(x0_p-x0).  mask u8 [B,3,H,W]. */
 int dpir_prox_mask(dpir_engine* e, float* x0_dev, const float* y_dev, const uint8_t* mask_dev,
