@@ -172,6 +172,13 @@ class GroupNormDesc(C.Structure):
                 [(n, C.c_int32) for n in ("ns_out", "reserved2")] + [("guard_bad_out", C.c_uint64)])
 
 
+class GradScaleDesc(C.Structure):
+    """dpir_debug_grad_scale_desc (include/diffpir_debug.h): the dgrad's per-image operand scale, for dpir_debug_grad_scale."""
+    _fields_ = ([("B", C.c_int32), ("C", C.c_int32), ("per_img", C.c_int64)] +
+                [(n, C.c_void_p) for n in ("x", "sn_out", "scal_out", "prm_out", "x_out")] +
+                [("parts_out", C.c_int32), ("reserved", C.c_int32), ("guard_bad_out", C.c_uint64)])
+
+
 PROF_CLASSES = 8
 PROF_NAMES = ["conv3x3", "conv1x1", "groupnorm_stats", "attention", "fft_prox", "elementwise", "unet_forward", "loop_graph"]
 
@@ -316,6 +323,10 @@ def load_debug():
     d.dpir_debug_attention.restype = C.c_int
     d.dpir_debug_groupnorm.argtypes = [C.c_void_p, C.POINTER(GroupNormDesc)]
     d.dpir_debug_groupnorm.restype = C.c_int
+    d.dpir_debug_range_counter.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
+    d.dpir_debug_range_counter.restype = C.c_int
+    d.dpir_debug_grad_scale.argtypes = [C.c_void_p, C.POINTER(GradScaleDesc)]
+    d.dpir_debug_grad_scale.restype = C.c_int
     for n in ("dpir_debug_conv_bench", "dpir_debug_victim", "dpir_debug_victim_alu", "dpir_debug_victim_fft_pk", "dpir_debug_victim_fft_nopk",
               "dpir_debug_conv7_check"):
         getattr(d, n).restype = C.c_int

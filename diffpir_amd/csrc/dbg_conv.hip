@@ -324,7 +324,7 @@ int dpir_debug_conv5_layer(dpir_engine* e, int B, int ca, int cb, int Cout, int 
         Conv5Args a5;
         a5.src = CatSrc{dxa, ca, cb ? dxb : nullptr, cb}; a5.prm = has_prm ? dprm : nullptr; a5.w16 = wp; a5.w16_scale = w16_scale;
         a5.bias = dbias; a5.out = dout; a5.res = res ? dres : nullptr; a5.B = B; a5.Cout = Cout; a5.H = H; a5.W = W;
-        a5.x1 = e->precision == 2; a5.force_tile = tile;
+        a5.x1 = e->precision == 2; a5.force_tile = tile; a5.range_ctr = e->range_ctr;
         *path_out = tile ? tile : (conv5_small_supported(B, ca, cb, Cout, H, W, has_prm) ? 2 : 1);
         st = launch_conv5(e->stream, a5);
     } else {

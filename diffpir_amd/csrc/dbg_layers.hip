@@ -2,6 +2,7 @@
 // (include/diffpir_debug.h: dpir_debug_attention, dpir_debug_groupnorm).  Part of libdiffpir_dbg.so, which links against the product
 // library: the entries upload the operands, call the product's launchers (launch_attention, launch_attention_bwd, launch_gn_stats,
 // launch_gn_prm, launch_gn_bwd) as unet.hip / unet_bwd.hip call them, and download the results.  No kernel lives here.
+// Also the two small entries of the operand-range tests: dpir_debug_range_counter and dpir_debug_grad_scale.
 //
 // Every buffer a kernel writes is allocated with GUARD floats of a fixed bit pattern on either side and is itself filled with the
 // pattern (a NaN: an element the kernel left out shows as a non-finite output); the guard words that changed are counted.  Operands
@@ -170,6 +171,51 @@ int dpir_debug_groupnorm(dpir_engine* e, dpir_debug_groupnorm_desc* d) {
     API_HIP(e, hipMemcpy(d->stats_out, stats, (size_t)B * 32 * 8, hipMemcpyDeviceToHost));
     if (ga) API_HIP(e, hipMemcpy(d->ga_out, ga, na * 4, hipMemcpyDeviceToHost));
     if (gb) API_HIP(e, hipMemcpy(d->gb_out, gb, nb * 4, hipMemcpyDeviceToHost));
+    unsigned long long bad = 0;
+    API_TRY(e, pool.count_bad(&bad));
+    d->guard_bad_out = bad;
+    return DPIR_OK;
+}
+
+// The engine's operand range guard word, read (and optionally zeroed) in stream order.  The layer probes synchronise without running the
+// guard (only dpir_sync / dpir_d2h check it, only a forward or a loop clears it): this is how a test reads the word behind one probe.
+int dpir_debug_range_counter(dpir_engine* e, unsigned long long* count, int clear) {
+    if (!e || !count) return DPIR_ERR_INVALID;
+    *count = 0;
+    if (!e->range_ctr) return fail(e, Status{DPIR_ERR_STATE, "range counter probe: the engine has no guard word"});
+    (void)hipSetDevice(e->device);
+    API_HIP(e, hipMemcpyAsync(count, e->range_ctr, sizeof(*count), hipMemcpyDeviceToHost, e->stream));
+    if (clear) API_HIP(e, hipMemsetAsync(e->range_ctr, 0, sizeof(*count), e->stream));
+    API_HIP(e, hipStreamSynchronize(e->stream));
+    return DPIR_OK;
+}
+
+// launch_grad_scale + launch_grad_unscale (grad.hip) on a host tensor, as unet_bwd.hip chains them around a dgrad convolution -- without the
+// convolution, so that what comes back is x[n] * (s_min / s_n).
+int dpir_debug_grad_scale(dpir_engine* e, dpir_debug_grad_scale_desc* d) {
+    if (!e || !d) return DPIR_ERR_INVALID;
+    d->guard_bad_out = 0; d->parts_out = 0;
+    const int B = d->B, C = d->C;
+    if (B <= 0 || C <= 0 || d->per_img <= 0 || !d->x || !d->sn_out || !d->scal_out || !d->prm_out || !d->x_out)
+        return fail(e, invalid("grad scale probe: bad descriptor"));
+    (void)hipSetDevice(e->device);
+    Pool pool(e->stream);
+    const size_t per = (size_t)d->per_img, n = (size_t)B * per;
+    const int parts = grad_scale_parts(B);
+    float *x = nullptr, *part = nullptr, *scal = nullptr, *sn = nullptr; float4* prm = nullptr;
+    API_TRY(e, pool.out(n, &x, d->x));
+    API_TRY(e, pool.out((size_t)B * parts, &part));
+    API_TRY(e, pool.out((size_t)2, &scal));
+    API_TRY(e, pool.out((size_t)2 * B, &sn));
+    API_TRY(e, pool.out((size_t)B * C, &prm));
+    API_TRY(e, launch_grad_scale(e->stream, x, B, per, part, scal, sn, prm, C));
+    API_TRY(e, launch_grad_unscale(e->stream, x, B, per, sn + B));
+    API_HIP(e, hipStreamSynchronize(e->stream));
+    API_HIP(e, hipMemcpy(d->sn_out, sn, (size_t)2 * B * 4, hipMemcpyDeviceToHost));
+    API_HIP(e, hipMemcpy(d->scal_out, scal, 8, hipMemcpyDeviceToHost));
+    API_HIP(e, hipMemcpy(d->prm_out, prm, (size_t)B * C * 16, hipMemcpyDeviceToHost));
+    API_HIP(e, hipMemcpy(d->x_out, x, n * 4, hipMemcpyDeviceToHost));
+    d->parts_out = parts;
     unsigned long long bad = 0;
     API_TRY(e, pool.count_bad(&bad));
     d->guard_bad_out = bad;

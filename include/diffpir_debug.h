@@ -181,6 +181,24 @@ typedef struct dpir_debug_groupnorm_desc {
     uint64_t guard_bad_out;
 } dpir_debug_groupnorm_desc;
 int dpir_debug_groupnorm(dpir_engine* e, dpir_debug_groupnorm_desc* d);
+/* The engine's f16 operand range guard word (DPIR_ERR_RANGE), read in stream order behind whatever was enqueued; clear != 0 zeroes it afterwards.
+ * *count is the WHOLE word: bits 0 .. 39 are the lanes that clamped a value (or saw a NaN) since the word was last cleared -- waves that share an
+ * operand may each count it, so only zero / non-zero is a contract --, bits 40 and up count the fused-hop time-outs (csrc/conv_epilogue.h).
+ * The layer probes above synchronise without checking or clearing the word; dpir_sync / dpir_d2h check it, a forward or a loop clears it. */
+int dpir_debug_range_counter(dpir_engine* e, unsigned long long* count, int clear);
+/* The dgrad's per-image operand scale (csrc/grad.hip launch_grad_scale, then launch_grad_unscale with the factors it made) on a host tensor
+ * x[B][per_img], for a table of C channels: sn_out[2B] = {s_n, then s_min / s_n}, scal_out[2] = {s_min, 1 / s_min}, prm_out[B][C][4] =
+ * {0, s_n, 0, 0} (s_min for an all-zero image), x_out[B][per_img] = x after the un-scale; parts_out = grad_scale_parts(B).  Guard words as for
+ * dpir_debug_attention. */
+typedef struct dpir_debug_grad_scale_desc {
+    int32_t B, C;
+    int64_t per_img;
+    const float* x;
+    float *sn_out, *scal_out, *prm_out, *x_out;
+    int32_t parts_out, reserved;
+    uint64_t guard_bad_out;
+} dpir_debug_grad_scale_desc;
+int dpir_debug_grad_scale(dpir_engine* e, dpir_debug_grad_scale_desc* d);
 /* The plan of the mixed-radix FFT prox (csrc/fft_plan.h) on its own: no engine, no GPU.
  * dpir_debug_fft_plan: the radix list of an N-point transform in forward order (up to radix_cap written, *n_radices = how many there are; the
  *   trailing ones multiply to sf) and, when perm != NULL, perm[f] = the stored position of frequency f (N ints).  DPIR_ERR_INVALID when sf does not

@@ -48,7 +48,10 @@ typedef enum dpir_status {
     DPIR_ERR_RANGE = -6      /* f16x3 mode: an activation left the f16 operand range (|v| > 65000) and was clamped; the
                               * result is wrong.  Reported by dpir_sync / dpir_d2h after the offending work; reload the
                               * weights with dpir_set_precision(e, 0).  Mirrors the reference's use_fp16 caveat
-                              * (guided_diffusion/unet.py:618-632, fp16_util.py:15-32) -- but loudly. */
+                              * (guided_diffusion/unet.py:618-632, fp16_util.py:15-32) -- but loudly.  The guard covers the
+                              * TOP of the range only: a raw operand below about 2^-7 leaves R x fp32 silently, with the
+                              * error max(2^-22 |v|, 2^-25) per value ("operand range of the f16
+                              * modes"; 2^-6: E = 1.1e-6, 2^-14: 2.7e-4 of a layer's budget, measured). */
 } dpir_status;
 
 typedef struct dpir_engine dpir_engine;   /* opaque */
