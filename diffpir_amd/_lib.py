@@ -58,6 +58,13 @@ class InpaintRow(C.Structure):
                 ("mix_next", C.c_int32), ("reserved", C.c_int32)]
 
 
+class AncestralRow(C.Structure):
+    """dpir_ancestral_row: one visited step of main_ddpir.py's loop under model_output_type pred_x_prev (schedule.build_ancestral_rows)."""
+    _fields_ = [("t", C.c_int32), ("nonzero", C.c_int32), ("mix_next", C.c_int32), ("reserved", C.c_int32),
+                ("c1", C.c_float), ("c2", C.c_float), ("pc1", C.c_float), ("pc2", C.c_float), ("min_log", C.c_float), ("max_log", C.c_float),
+                ("sa_prev", C.c_float), ("s1m_prev", C.c_float), ("sa_t", C.c_float), ("s1m_t", C.c_float), ("sa_n", C.c_float), ("s1m_n", C.c_float)]
+
+
 class ProgressDesc(C.Structure):
     """dpir_progress_desc: the progressive strip armed for the next whole-loop call (dpir_set_progress)."""
     _fields_ = [("panel_of_step_host", C.POINTER(C.c_int32)), ("n_entries", C.c_int32), ("n_panels", C.c_int32),
@@ -260,6 +267,9 @@ SIGNATURES = {
     "dpir_inpaint_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(InpaintRow), C.c_int, C.c_float,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "dpir_run_inpaint_loop": (C.c_int, [C.c_void_p, C.POINTER(LoopDesc), C.POINTER(InpaintRow), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dpir_ancestral_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(AncestralRow), C.c_int, C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "dpir_run_ancestral_loop": (C.c_int, [C.c_void_p, C.POINTER(LoopDesc), C.POINTER(AncestralRow), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dpir_prof_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "dpir_prof_reset": (C.c_int, [C.c_void_p]),
     "dpir_prof_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

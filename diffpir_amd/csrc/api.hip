@@ -5,6 +5,7 @@
 #include "grad.h"
 #include "blur.h"
 #include "inpaint.h"
+#include "ancestral.h"
 #include "progress.h"
 #include "lpips.h"
 #include "fid.h"
@@ -1229,6 +1230,168 @@ int dpir_run_inpaint_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_i
                           float* out_f32, uint8_t* out_u8) {
     ProgressOneShot one_shot{e};
     return run_with_hop_guard(e, [&] { return run_inpaint_loop_once(e, dd, rows, n_rows, noise_back, out_f32, out_u8); });
+}
+
+// ------------------------------------------------------------------------------------------ ancestral inpainting loops (main_ddpir.py, 'pred_x_prev')
+static AncestralRowDev ancestral_row_dev_of(const dpir_ancestral_row& r, int s) {
+    AncestralRowDev o{};
+    o.st = StepDev{r.t, 0, s, 0, r.c1, r.c2, 0.f, r.sa_t, r.s1m_t, 0.f, 0.f, 0.f, 0.f, 0.f};
+    o.s = s; o.nonzero = r.nonzero; o.mix_next = r.mix_next; o.emit = 0;
+    o.pc1 = r.pc1; o.pc2 = r.pc2; o.min_log = r.min_log; o.max_log = r.max_log;
+    o.sa_prev = r.sa_prev; o.s1m_prev = r.s1m_prev; o.sa_n = r.sa_n; o.s1m_n = r.s1m_n;
+    return o;
+}
+
+static const char* kNeedsLearnSigma = "p_sample needs a learn_sigma model (out_channels == 6): the learned-range variance is read from channels 3..5";
+
+int dpir_ancestral_step(dpir_engine* e, float* x, const float* out6, int out_ch, const float* y, const uint8_t* mask, const dpir_ancestral_row* row,
+                        int generate_mode, int ddim, const float* n_ps, const float* n_rp_next, uint64_t seed, int64_t image_offset, int step,
+                        float* x0_out, int B, int H, int W) {
+    if (!e || !x || !out6 || !row) return fail(e, invalid("dpir_ancestral_step: null argument"));
+    API_TRY(e, check_shape("dpir_ancestral_step", B, H, W));
+    if (generate_mode != 1 && generate_mode != 2) return fail(e, invalid("dpir_ancestral_step: generate_mode must be 1 (repaint) or 2 (vanilla)"));
+    if (generate_mode == 1 && (!y || !mask)) return fail(e, invalid("dpir_ancestral_step: repaint needs y and mask"));
+    if (step < 0) return fail(e, invalid("dpir_ancestral_step: step must be >= 0"));
+    const bool host = n_ps != nullptr;
+    if (!host && n_rp_next) return fail(e, invalid("dpir_ancestral_step: host noise needs n_ps (both null selects device noise)"));
+    if (host && generate_mode == 1 && row->mix_next && !n_rp_next) return fail(e, invalid("dpir_ancestral_step: the repaint mix needs n_repaint_next"));
+    if (out_ch != 6) return fail(e, Status{DPIR_ERR_UNSUPPORTED, std::string("dpir_ancestral_step: ") + kNeedsLearnSigma});
+    (void)hipSetDevice(e->device);
+    ProfScope ps(&e->prof, PC_ELEM);
+    AncestralStepArgs a{};
+    a.x = x; a.out6 = out6; a.y = y; a.mask = mask; a.mode = generate_mode; a.ddim = ddim ? 1 : 0;
+    a.device_noise = host ? 0 : 1; a.nps = n_ps; a.nrp_next = n_rp_next;
+    a.seed = seed; a.image_offset = image_offset; a.x0_out = x0_out; a.row = nullptr; a.row_val = ancestral_row_dev_of(*row, step); a.lp = nullptr;
+    a.B = B; a.HW = H * W; a.cus = e->cus;
+    API_TRY(e, launch_ancestral_step(e->stream, a));
+    return DPIR_OK;
+}
+
+static int run_ancestral_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_ancestral_row* rows, int n_rows, const float* noise_ps,
+                                   float* out_f32, uint8_t* out_u8) {
+    if (!e || !dd || !rows || n_rows <= 0) return fail(e, invalid("dpir_run_ancestral_loop: null argument"));
+    (void)hipSetDevice(e->device);
+    const dpir_loop_desc& d = *dd;
+    if (!e->net.loaded) return fail(e, Status{DPIR_ERR_STATE, "dpir_load_unet has not been called"});
+    API_TRY(e, check_shape("dpir_run_ancestral_loop", d.B, d.H, d.W));
+    if (d.task != DPIR_TASK_INPAINT || d.sf != 1)
+        return fail(e, invalid("dpir_run_ancestral_loop: task must be inpainting, sf 1 (main_ddpir.py:355-366 updates x from 'pred_x_prev' for inpainting only)"));
+    if (!d.y_dev || !d.mask_dev) return fail(e, invalid("dpir_run_ancestral_loop: y and mask are required"));
+    if (d.generate_mode != 1 && d.generate_mode != 2)
+        return fail(e, invalid("dpir_run_ancestral_loop: generate_mode must be 1 (repaint) or 2 (vanilla); DiffPIR with pred_x_prev reads an unbound tau at main_ddpir.py:417"));
+    if (e->net.desc.out_channels != 6) return fail(e, Status{DPIR_ERR_UNSUPPORTED, std::string("dpir_run_ancestral_loop: ") + kNeedsLearnSigma});
+    if ((e->net.desc.num_classes > 0) != (d.labels_host != nullptr)) return fail(e, invalid("labels iff class-conditional model"));
+    const int B = d.B, H = d.H, W = d.W;
+    const size_t total = (size_t)B * 3 * H * W;
+    const bool host = noise_ps != nullptr;
+    const bool repaint = d.generate_mode == 1;
+    for (int r = 0; r < n_rows; ++r)
+        if ((rows[r].mix_next != 0) != (r + 1 < n_rows)) return fail(e, invalid("dpir_run_ancestral_loop: mix_next must be 1 on every row but the last"));
+    if (host) {
+        if (!d.noise_init_dev) return fail(e, invalid("dpir_run_ancestral_loop: host noise needs noise_init_dev"));
+        if (repaint && !d.noise_rp_dev) return fail(e, invalid("dpir_run_ancestral_loop: repaint with host noise needs noise_rp_dev"));
+    } else if (d.noise_init_dev || d.noise_rp_dev) {
+        return fail(e, invalid("dpir_run_ancestral_loop: host noise needs noise_ps_dev (all null selects device noise)"));
+    }
+    API_TRY(e, progress_check(e, "dpir_run_ancestral_loop", n_rows, d));
+    // repaint: the fused pass mixes the next step's known region into x before x reaches memory, so the rows that own a panel also write the
+    // pre-mix x to a scratch image, which the snapshot then reads (as dpir_run_inpaint_loop)
+    const dpir_engine::Progress& pg = e->progress;
+    const bool premix = pg.armed && repaint;
+    if (premix && e->progress_premix_bytes < total * sizeof(float)) {
+        API_HIP(e, hipStreamSynchronize(e->stream));
+        if (e->progress_premix) (void)hipFree(e->progress_premix);
+        e->progress_premix = nullptr; e->progress_premix_bytes = 0;
+        API_HIP(e, hipMalloc((void**)&e->progress_premix, total * sizeof(float)));
+        e->progress_premix_bytes = total * sizeof(float);
+    }
+    range_clear(e);
+    LoopBufs b{};
+    AncestralRowDev *rows_dev = nullptr, *cur = nullptr;
+    AncestralLoopDev* lp = nullptr;
+    API_TRY(e, e->ws.getT("loop#x", total, &b.x));
+    API_TRY(e, e->ws.getT("loop#out6", (size_t)B * 6 * H * W, &b.out6));
+    API_TRY(e, e->ws.getT("loop#n2", total, &b.n2));        // the init draw and the first repaint mix (device noise); the steps draw in place
+    API_TRY(e, e->ws.getT("loop#t", (size_t)B, &b.t_dev));
+    API_TRY(e, e->ws.getT("ancestral#rows", (size_t)n_rows, &rows_dev));
+    API_TRY(e, e->ws.getT("ancestral#cur", (size_t)1, &cur));
+    API_TRY(e, e->ws.getT("ancestral#lp", (size_t)1, &lp));
+    API_TRY(e, upload_ints(e, "loop#y", d.labels_host, B, &b.y_dev));
+    const bool hoist_film = e->net.desc.num_classes == 0;
+    if (hoist_film) API_TRY(e, e->ws.getT("loop#film", (size_t)n_rows * e->net.film_rows, &b.film));
+    {
+        std::vector<AncestralRowDev> hr(n_rows);
+        for (int r = 0; r < n_rows; ++r) { hr[r] = ancestral_row_dev_of(rows[r], r); hr[r].emit = premix && pg.panel_of[r] >= 0; }
+        AncestralLoopDev hl{d.y_dev, d.mask_dev, noise_ps, d.noise_rp_dev, (unsigned long long)d.seed, (long long)d.image_offset,
+                            premix ? e->progress_premix : nullptr};
+        API_HIP(e, hipMemcpyAsync(rows_dev, hr.data(), sizeof(AncestralRowDev) * n_rows, hipMemcpyHostToDevice, e->stream));
+        API_HIP(e, hipMemcpyAsync(lp, &hl, sizeof(hl), hipMemcpyHostToDevice, e->stream));
+        API_HIP(e, hipStreamSynchronize(e->stream));
+    }
+    if (b.film) {   // one FiLM row per step
+        std::vector<int64_t> ts(n_rows);
+        for (int r = 0; r < n_rows; ++r) ts[r] = rows[r].t;
+        int* ts_dev = nullptr;
+        API_TRY(e, upload_ints(e, "loop#ts", ts.data(), n_rows, &ts_dev));
+        API_TRY(e, unet_film_table(e, ts_dev, n_rows, b.film));
+    }
+    ProxState none{};
+    API_TRY(e, loop_init(e, d, b, &none));                  // main_ddpir.py:312-315
+    hipStream_t s = e->stream;
+    if (repaint) {                                          // the first step's mix (:356-358); every later one is applied by the step before it
+        ProfScope ps(&e->prof, PC_ELEM);
+        const float* nr = d.noise_rp_dev;
+        if (!nr) { API_TRY(e, launch_randn(s, b.n2, d.seed, 3, d.image_offset, B, (size_t)3 * H * W)); nr = b.n2; }
+        API_TRY(e, launch_repaint_mix(s, b.x, d.y_dev, d.mask_dev, nr, rows[0].sa_t, rows[0].s1m_t, total));
+    }
+    // one 16-byte access per lane needs every tensor behind lp aligned; the decision is baked into a captured graph, so it is part of its key
+    auto al = [](const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) == 0; };
+    const bool aligned = al(d.y_dev, 15) && al(d.mask_dev, 3) && al(noise_ps, 15) && al(d.noise_rp_dev, 15);
+    AncestralStepArgs a{};
+    a.x = b.x; a.out6 = b.out6; a.mode = d.generate_mode; a.ddim = d.ddim_sample ? 1 : 0;
+    a.device_noise = host ? 0 : 1; a.row = cur; a.lp = lp; a.B = B; a.HW = H * W; a.cus = e->cus; a.scalar_only = aligned ? 0 : 1;
+    const StepDev* cur_st = &cur->st;
+    auto step = [&]() -> Status {
+        if (!b.film) hipLaunchKernelGGL(fill_t_kernel, dim3((B + 255) / 256), dim3(256), 0, s, b.t_dev, cur_st, B);
+        DPIR_TRY(unet_forward(e, b.x, b.t_dev, b.y_dev, b.out6, B, H, W, b.film, b.film ? cur_st : nullptr));
+        ProfScope ps(&e->prof, PC_ELEM);
+        return launch_ancestral_step(s, a);
+    };
+    hipGraphExec_t g = nullptr;
+    // the panel of row r - 1 when row r begins (or before finalize).  Repaint: a row that mixed the next one in left its own x in the scratch image
+    auto emit = [&](int r) -> Status {
+        return progress_emit(e, r, r >= 0 && premix && rows[r].mix_next ? e->progress_premix : b.x, d);
+    };
+    for (int r = 0; r < n_rows; ++r) {
+        API_TRY(e, emit(r - 1));
+        API_HIP(e, hipMemcpyAsync(cur, rows_dev + r, sizeof(AncestralRowDev), hipMemcpyDeviceToDevice, s));
+        if (!d.use_graph) { API_TRY(e, step()); continue; }
+        if (!g) {
+            dpir_engine::GraphKey k{};
+            k.task = d.task; k.B = B; k.H = H; k.W = W; k.sf = 1; k.generate_mode = d.generate_mode;
+            k.kind = (aligned ? 1 : 0) | (d.ddim_sample ? 2 : 0);
+            k.host_n2 = host; k.host_rp = d.noise_rp_dev != nullptr;
+            k.has_labels = d.labels_host != nullptr;
+            k.loop = 2;
+            bool ran = false;
+            if (int rc = cached_step_graph(e, k, step, nullptr, nullptr, &g, &ran)) return rc;
+            if (ran) continue;   // this step was executed eagerly
+        }
+        ProfScope ps(&e->prof, PC_LOOP);
+        API_HIP(e, hipGraphLaunch(g, s));
+    }
+    API_TRY(e, emit(n_rows - 1));
+    {
+        ProfScope ps(&e->prof, PC_ELEM);
+        API_TRY(e, launch_finalize(s, b.x, out_f32, out_u8, B, H * W));
+    }
+    return DPIR_OK;
+}
+
+int dpir_run_ancestral_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_ancestral_row* rows, int n_rows, const float* noise_ps,
+                            float* out_f32, uint8_t* out_u8) {
+    ProgressOneShot one_shot{e};
+    return run_with_hop_guard(e, [&] { return run_ancestral_loop_once(e, dd, rows, n_rows, noise_ps, out_f32, out_u8); });
 }
 
 // ------------------------------------------------------------------------------------------ gradient-mode plugs + DPS loop (8f-4)

@@ -408,6 +408,9 @@ int dpir_debug_conv3_layer(dpir_engine* e, dpir_debug_conv3_desc* d) {
         API_TRY(e, e->ws.getT("c3#partial", pcap, &partial));
         API_HIP(e, hipMemset(partial, 0xFF, pcap * 4));
     }
+    // hipMemset of device memory returns before the fill has run, and it runs on the null stream, which the engine's non-blocking stream does not
+    // wait for: without this the poison can land AFTER a kernel below has written (seen once: conv7's whole output NaN, operand planes poisoned late)
+    API_HIP(e, hipDeviceSynchronize());
 
     if (d->route == 8) {        // Fwd::conv's output-layer route
         if (e->precision == 0) return fail(e, invalid("conv3 layer: conv8 needs an f16 engine"));
@@ -461,6 +464,7 @@ int dpir_debug_conv3_layer(dpir_engine* e, dpir_debug_conv3_desc* d) {
     char* s16 = nullptr;
     API_TRY(e, e->ws.getT("c3#s16", 2 * plane, &s16));
     API_HIP(e, hipMemset(s16, 0xFF, 2 * plane));
+    API_HIP(e, hipDeviceSynchronize());        // the poison is in place before the prologue writes the planes (see above)
     if (d->prologue == 2) {     // Fwd::gn_conv's fused low-resolution prologue
         if (C % 16 || !gn_act_small_supported(C, Hs, Ws, mode)) return fail(e, Status{DPIR_ERR_UNSUPPORTED, "conv3 layer: gn_act_small refuses this shape"});
         float *dg = nullptr, *db = nullptr, *df = nullptr;
@@ -501,6 +505,7 @@ int dpir_debug_conv3_layer(dpir_engine* e, dpir_debug_conv3_desc* d) {
         API_TRY(e, e->ws.getT("c3#sp", (size_t)B * Cout, &sp));
         API_HIP(e, hipMemset(st, 0xFF, nst * 8));
         API_HIP(e, hipMemset(sp, 0xFF, (size_t)B * Cout * 16));
+        API_HIP(e, hipDeviceSynchronize());
     }
     a6.stat = st; a6.stat_plane = sp;
     Conv3Plan ran;
@@ -544,6 +549,7 @@ int dpir_debug_conv3_layer(dpir_engine* e, dpir_debug_conv3_desc* d) {
         API_HIP(e, hipMemset(dbias2, 0, (size_t)round_up(Co2, 64) * 4));
         API_HIP(e, hipMemcpy(dbias2, d->bias2, (size_t)Co2 * 4, hipMemcpyHostToDevice));
         API_HIP(e, hipMemset(dout2, 0xFF, no2 * 4));
+        API_HIP(e, hipDeviceSynchronize());
         GnActArgs ga;
         ga.src = CatSrc{dout, Cn, nullptr, 0}; ga.pend = pc; ga.gamma = dg; ga.beta = db;
         ga.silu = true; ga.mode = 0; ga.B = B; ga.Hs = H; ga.Ws = W;

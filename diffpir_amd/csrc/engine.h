@@ -119,7 +119,7 @@ struct dpir_engine {
         int32_t task, B, H, W, sf, in_iter, generate_mode, kind;      // kind: bit0 final step, bit1 eta draw
         int32_t host_n1, host_n2, host_rp, has_labels;
         float gamma, guidance;
-        int32_t loop, loop_pad;      // 0: dpir_run_loop's step, 1: dpir_run_inpaint_loop's sub-step (kind bit0: 16-byte accesses)
+        int32_t loop, loop_pad;      // 0: dpir_run_loop's step, 1: dpir_run_inpaint_loop's sub-step (kind bit0: 16-byte accesses), 2: dpir_run_ancestral_loop's step (kind bit0: 16-byte accesses, bit1: ddim)
         int32_t per_image, image_index;   // dpir_run_loop_per_image: a per-image scalar table / image-number table was given (per-image kernel instantiations)
         uint64_t ws_generation;
     };

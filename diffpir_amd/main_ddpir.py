@@ -581,6 +581,13 @@ def main(argv=None):
                 nf = lambda shape: torch.randn(tuple(shape), generator=host_gen).numpy()
                 full = restore.draw_inpaint_host_noise(nf, cfg, rows, n_b, H, W)
                 drawn = {k_: None if a is None else np.ascontiguousarray(a[lo:hi] if a.ndim == 4 else a[:, lo:hi]) for k_, a in full.items()}
+            elif noise == "host" and cfg.is_ancestral():
+                # model_output_type: pred_x_prev -- init, then per step [the repaint draw] and the sampler's draw (restore.ancestral_host_noise_shapes),
+                # batch-shaped; every rank draws the global batch and keeps its images
+                _, rows, _ = restore._ancestral_rows(cfg)
+                nf = lambda shape: torch.randn(tuple(shape), generator=host_gen).numpy()
+                full = restore.draw_ancestral_host_noise(nf, cfg, rows, n_b, H, W)
+                drawn = {k_: None if a is None else np.ascontiguousarray(a[lo:hi] if a.ndim == 4 else a[:, lo:hi]) for k_, a in full.items()}
             elif noise == "host":
                 # EVERY rank draws the global batch's noise, also a rank whose shard is empty (ragged last batch with fewer images
                 # than ranks): the shared generator must advance identically everywhere or later batches depend on the world size

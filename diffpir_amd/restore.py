@@ -100,6 +100,9 @@ class LoopConfig:
                 raise ValueError(f"main_ddpir_inpainting.py:227 `progress_seq = seq[::(len(seq)//10)]` raises for a schedule of {n} entries "
                                  "(fewer than 10): there is no behaviour to mirror")
             return
+        if self.model_output_type == "pred_x_prev":
+            self._check_ancestral()
+            return
         # ddim_sample is accepted: with model_output_type=pred_xstart it selects the same x0 prediction and the same number
         # of RNG draws as p_sample (utils_model.py:219-240; tests/golden/model_fn.npz).  iter_num_U > 1 cannot be mirrored:
         # the reference raises IndexError on `seq[i+1]` at its last step (main_ddpir.py:448-451 with u < iter_num_U-1).
@@ -119,6 +122,28 @@ class LoopConfig:
         elif self.generate_mode != "DiffPIR" and self.task != "inpaint":
             # main_ddpir.py:448: outside DiffPIR mode x is only re-noised for inpainting; other tasks would leave x untouched
             raise NotImplementedError("generate_mode repaint / vanilla are inpainting modes in the reference")
+
+    def is_ancestral(self) -> bool:
+        """driver main_ddpir with model_output_type pred_x_prev: the ancestral loops (dpir_run_ancestral_loop)."""
+        return self.driver == "main_ddpir" and self.model_output_type == "pred_x_prev"
+
+    def _check_ancestral(self):
+        """model_output_type pred_x_prev under driver main_ddpir (main_ddpir.py:355-366): task inpaint with generate_mode repaint (RePaint-style
+        ancestral sampling) or vanilla (plain DDPM ancestral sampling), iter_num_U 1.  Everything else has no behaviour to mirror."""
+        if self.task != "inpaint":
+            # main_ddpir.py:375 assigns the sample to x0, which nothing reads without 'pred_xstart' (:387, :448): x never changes
+            raise NotImplementedError("model_output_type=pred_x_prev: only task 'inpaint' updates x from the sample (main_ddpir.py:365-366); "
+                                      "for the other tasks the reference leaves x untouched")
+        if self.generate_mode == "DiffPIR":
+            raise NotImplementedError("model_output_type=pred_x_prev with generate_mode DiffPIR: the reference reads an unbound `tau` at "
+                                      "main_ddpir.py:417 (it is assigned in the pred_xstart branch only, :389)")
+        if self.generate_mode not in ("repaint", "vanilla"):
+            raise NotImplementedError("model_output_type=pred_x_prev runs generate_mode repaint / vanilla (the reference asserts the inpainting "
+                                      "modes at main_ddpir.py:154)")
+        if int(self.iter_num_U) != 1:
+            raise NotImplementedError("model_output_type=pred_x_prev with iter_num_U > 1: the reference reads an unbound `t_im1` at "
+                                      "main_ddpir.py:465 (it is assigned in the pred_xstart re-noise only, :451)")
+        # sub_1_analytic, lambda_, zeta, eta and guidance_scale are never read in these two modes (:384-445 has no branch for them)
 
 
 DRIVERS = ("main_ddpir", "main_ddpir_deblur", "main_ddpir_inpainting")
@@ -157,6 +182,9 @@ def check_per_image(cfg: "LoopConfig", per_image: PerImage):
         raise NotImplementedError(f"per_image: driver={cfg.driver!r} runs the standalone program's own loop, which has no per-image form")
     if cfg.generate_mode in ("DPS_y0", "DPS_yt"):
         raise NotImplementedError("per_image: the DPS modes have no per-image form")
+    if cfg.is_ancestral():
+        raise NotImplementedError("per_image: model_output_type=pred_x_prev reads none of lambda, zeta and the noise level inside the loop; there is "
+                                  "nothing to vary per image (dpir_run_ancestral_loop has no per-image form)")
     if not cfg.sub_1_analytic:
         raise NotImplementedError("per_image: sub_1_analytic=false normalises its step by one residual norm of the whole batch (main_ddpir.py:425-427)")
     if cfg.skip_noise_model_t and per_image.noise_level_img is not None:
@@ -427,6 +455,9 @@ def restore_batch(engine: Engine, cfg: LoopConfig, y, k=None, mask=None, labels=
     if cfg.driver == "main_ddpir_inpainting":
         return _restore_inpaint_resample(engine, cfg, y, mask, labels, noise_source, noise_fn, seed, image_offset, use_graph, skip_dead_final_eval,
                                          out_f32, out_u8, return_u8, _cache, predrawn, progress=progress)
+    if cfg.is_ancestral():
+        return _restore_ancestral(engine, cfg, y, mask, labels, noise_source, noise_fn, seed, image_offset, use_graph, out_f32, out_u8, return_u8,
+                                  _cache, predrawn, progress=progress)
     if cfg.driver == "main_ddpir_deblur" and (cfg.generate_mode != "DiffPIR" or not cfg.sub_1_analytic):
         if predrawn is not None or mask is not None or use_graph:
             raise NotImplementedError("the deblurring program's gradient modes take host noise through noise_fn, no mask and no step graph")
@@ -564,6 +595,61 @@ def _restore_inpaint_resample(engine, cfg, y, mask, labels, noise_source, noise_
     return (out_f32, out_u8) if return_u8 else out_f32
 
 
+def _ancestral_rows(cfg: LoopConfig):
+    from .schedule import DriverTables, build_ancestral_rows
+    t_start = None
+    if cfg.noise_init_img != "max":
+        t_start = t_start_of(cfg, DriverTables.make(cfg.beta_start, cfg.beta_end, cfg.num_train_timesteps).reduced)
+    return build_ancestral_rows(iter_num=cfg.iter_num, skip_type=cfg.skip_type, T=cfg.num_train_timesteps, beta_start=cfg.beta_start,
+                                beta_end=cfg.beta_end, t_start=t_start)
+
+
+def ancestral_host_noise_shapes(cfg: LoopConfig, rows, B: int, H: int, W: int):
+    """Shapes of the reference's randn_like draws under model_output_type pred_x_prev, in call order: init (main_ddpir.py:315), then per step
+    [the repaint mix, :357] and the sampler's draw (gaussian_diffusion.py:430 / :577; ddim consumes it too).  All batch-shaped."""
+    return [(B, 3, H, W)] * (1 + len(rows) * ((cfg.generate_mode == "repaint") + 1))
+
+
+def draw_ancestral_host_noise(noise_fn: Callable, cfg: LoopConfig, rows, B: int, H: int, W: int):
+    """Consume noise_fn in the order of ancestral_host_noise_shapes: dict(init [B,3,H,W]; ps [n_rows,B,3,H,W]; rp (repaint) likewise, or None)."""
+    shape, rp = (B, 3, H, W), cfg.generate_mode == "repaint"
+    draw = lambda: np.asarray(noise_fn(shape), dtype=np.float32)
+    out = dict(init=draw(), ps=np.empty((len(rows),) + shape, np.float32), rp=np.empty((len(rows),) + shape, np.float32) if rp else None)
+    for s in range(len(rows)):
+        if rp:
+            out["rp"][s] = draw()
+        out["ps"][s] = draw()
+    return out
+
+
+def _restore_ancestral(engine, cfg, y, mask, labels, noise_source, noise_fn, seed, image_offset, use_graph, out_f32, out_u8, return_u8, _cache,
+                       predrawn, progress=None):
+    """model_output_type 'pred_x_prev' of driver 'main_ddpir' (main_ddpir.py:355-366, task inpaint, generate_mode repaint / vanilla):
+    dpir_run_ancestral_loop, one fused data pass per step.  predrawn: the dict of draw_ancestral_host_noise (sharded runs)."""
+    if mask is None:
+        raise EngineError("inpainting needs a mask")
+    dt, rows, arr = _ancestral_rows(cfg)
+    keep = []
+    y, mask = _dev(engine, y, np.float32, keep), _dev(engine, mask, np.uint8, keep)
+    B, _, H, W = y.shape
+    d, lab = _loop_desc(cfg, B, H, W, 1, start_coefficients(cfg, dt), y, None, mask, labels, seed, image_offset, use_graph, False)
+    nps = None
+    if _host_noise(noise_source, noise_fn, predrawn):
+        if predrawn is None:
+            predrawn = draw_ancestral_host_noise(noise_fn, cfg, rows, B, H, W)
+        dn = {k_: _dev(engine, v, np.float32, keep) for k_, v in predrawn.items()}
+        d.noise_init_dev, d.noise_rp_dev = _ptr(dn["init"]), _ptr(dn["rp"])
+        nps = dn["ps"]
+    out_f32, out_u8 = _outputs(engine, B, H, W, out_f32, out_u8, return_u8)
+    _call_loop(engine, progress, cfg, rows, B, H, W, True,
+               lambda: engine.lib.dpir_run_ancestral_loop(engine.h, C.byref(d), arr, len(rows), _ptr(nps), _ptr(out_f32), _ptr(out_u8)))
+    if _cache is not None:
+        _cache["keep"] = keep
+    else:
+        engine.sync()
+    return (out_f32, out_u8) if return_u8 else out_f32
+
+
 def draw_grad_host_noise(noise_fn: Callable, cfg: LoopConfig, steps, B: int, H: int, W: int):
     """Host noise of the gradient-mode loops, consumed in the order of dps_host_noise_shapes; image n uses slice n of every batch-shaped draw.
     DPS_y0 / DPS_yt: dict(init [B,3,H,W], ps [n_steps,B,3,H,W], yt [n_steps,B,3,H/sf,W/sf] (DPS_yt; zeros where a step has no y_t draw) or None);
@@ -632,6 +718,8 @@ def restore_batch_stepwise(model, diffusion, cfg: LoopConfig, y, k=None, mask=No
     cfg.check_supported()
     if cfg.driver == "main_ddpir_inpainting":
         return _stepwise_inpaint_resample(model, diffusion, cfg, y, mask, noise_fn, labels, progress)
+    if cfg.is_ancestral():
+        return _stepwise_ancestral(model, diffusion, cfg, y, mask, noise_fn, labels, progress)
     dt, steps, arr = _steps(cfg)
     hp = None if progress is None else _HostProgress(progress, cfg, steps, y, mask)
     B, _, h, w = y.shape
@@ -770,6 +858,44 @@ def _stepwise_inpaint_resample(model, diffusion, cfg: LoopConfig, y, mask, noise
             eng._check(lib.dpir_ewise(hnd, 2, x.ptr, None, 0, float(np.float32(r["sae"])), x.ptr, numel))
             eng._check(lib.dpir_ewise(hnd, 2, nb.ptr, None, 0, float(np.float32(r["sb"])), nb.ptr, numel))
             eng._check(lib.dpir_ewise(hnd, 0, x.ptr, nb.ptr, numel, 0.0, x.ptr, numel))
+    if hp:
+        hp.take(len(rows) - 1, x)
+        hp.finish()
+    out = eng.empty(shape)
+    eng._check(lib.dpir_finalize(hnd, x.ptr, out.ptr, None, B, H, W))
+    eng.sync()
+    return out
+
+
+def _stepwise_ancestral(model, diffusion, cfg: LoopConfig, y, mask, noise_fn, labels, progress=None):
+    """main_ddpir.py:312-315, 341-366, 470 under model_output_type pred_x_prev over the drop-in plugs (dpir_repaint_mix, model_fn 'pred_x_prev' ->
+    dpir_p_sample): the unfused statement of dpir_run_ancestral_loop.  One host noise stream in call order: init, [mix], the sampler's draw."""
+    from . import utils_model
+    eng: Engine = model.engine
+    dt, rows, arr = _ancestral_rows(cfg)
+    hp = None if progress is None else _HostProgress(progress, cfg, rows, y, mask)
+    B, _, H, W = y.shape
+    shape = (B, 3, H, W)
+    lib, hnd = eng.lib, eng.h
+    x = eng.empty(shape)
+    xs = y.numpy() * mask.numpy().astype(np.float32)            # :314
+    sa0, s1m0 = start_coefficients(cfg, dt)
+    x.copy_from(sa0 * (np.float32(2) * xs - np.float32(1)) + s1m0 * np.asarray(noise_fn(shape), np.float32))    # :315
+    kwargs = {} if labels is None else {"y": labels}
+    utils_model.set_randn_like(lambda like: eng.to_device(np.asarray(noise_fn(like.shape), np.float32)))
+    try:
+        for s, r in enumerate(rows):
+            if hp:
+                hp.take(s - 1, x)                               # the panel of the step before, ahead of this step's mix
+            if cfg.generate_mode == "repaint":                  # :356-358
+                st = _lib.Step()
+                st.sa_t, st.s1m_t = r["sa_t"], r["s1m_t"]
+                nr = eng.to_device(np.asarray(noise_fn(shape), np.float32))
+                eng._check(lib.dpir_repaint_mix(hnd, x.ptr, _ptr(y), _ptr(mask), C.byref(st), nr.ptr, B, H, W))
+            x = utils_model.model_fn(x, noise_level=dt.reduced[r["t"]] * 255, model_out_type="pred_x_prev", model_diffusion=model,
+                                     diffusion=diffusion, ddim_sample=cfg.ddim_sample, alphas_cumprod=dt.alphas_cumprod, **kwargs)    # :365-366
+    finally:
+        utils_model.set_randn_like(None)
     if hp:
         hp.take(len(rows) - 1, x)
         hp.finish()

@@ -222,6 +222,38 @@ def build_image_table(*, lambda_, zeta, sigma, **kw):
     return first, table
 
 
+def build_ancestral_rows(*, iter_num: int, skip_type: str = "quad", T: int = 1000, beta_start=0.0001, beta_end=0.02, t_start: int = None):
+    """One row per visited step of main_ddpir.py:341-470 under model_output_type pred_x_prev, task inpaint, generate_mode repaint / vanilla,
+    iter_num_U 1: returns (DriverTables, list of python dicts, ctypes AncestralRow array).  seq, t_i and the `t_i > t_start` skip are
+    build_steps' (:327-347).  A step is x = model_fn(x, 'pred_x_prev') and nothing else, so a row holds p_sample's coefficients at t_i as
+    utils_model.model_fn forms them for dpir_p_sample (DiffusionTables.c1c2 / dps_coef / ddim_coef: float64 tables cast to float32), the mix
+    pair (sa, s1m)[t_i] of :356-358 from the driver's float32 tables, and the next row's pair for the mix the fused pass applies ahead of the
+    next denoiser call.  There is no `last` flag: the final step is live (t = 0: nonzero = 0).  rhos (:284) are never read in these modes."""
+    dt = DriverTables.make(beta_start, beta_end, T)
+    dtab = DiffusionTables.make(T)
+    if t_start is None:
+        t_start = T - 1
+    seq = make_seq(T, iter_num, skip_type)
+    t_list = [find_nearest(dt.reduced, dt.reduced[T - 1 - s]) for s in seq]
+    rows = []
+    for i, t_i in enumerate(t_list):
+        if t_i > t_start:
+            continue                                      # main_ddpir.py:346-347
+        c1, c2 = dtab.c1c2(t_i)
+        pc1, pc2, min_log, max_log = dtab.dps_coef(t_i)
+        sa_prev, s1m_prev = dtab.ddim_coef(t_i)
+        rows.append(dict(t=t_i, nonzero=int(t_i != 0), mix_next=0, reserved=0, c1=float(c1), c2=float(c2), pc1=float(pc1), pc2=float(pc2),
+                         min_log=float(min_log), max_log=float(max_log), sa_prev=float(sa_prev), s1m_prev=float(s1m_prev),
+                         sa_t=float(dt.sqrt_ac[t_i]), s1m_t=float(dt.sqrt_1m_ac[t_i]), sa_n=0.0, s1m_n=0.0, seq_i=i, seq=seq[i]))
+    for r, nxt in zip(rows[:-1], rows[1:]):
+        r.update(mix_next=1, sa_n=nxt["sa_t"], s1m_n=nxt["s1m_t"])
+    arr = (_lib.AncestralRow * len(rows))()
+    for i, r in enumerate(rows):
+        for f, _ in _lib.AncestralRow._fields_:
+            setattr(arr[i], f, r[f])
+    return dt, rows, arr
+
+
 def build_inpaint_rows(*, iter_num: int, iter_num_U: int, sigma: float, lambda_: float, zeta: float, eta: float = 0.0,
                        skip_type: str = "quad", T: int = 1000, beta_start=0.0001, beta_end=0.02, t_start: int = None):
     """One row per sub-step (i, u) of the standalone inpainting program (main_ddpir_inpainting.py:200-300), model_out_type pred_xstart:

@@ -352,14 +352,14 @@ int dpir_progress_snapshot(dpir_engine* e, const float* x_dev, const float* y_de
  * main_ddpir_inpainting.py:217-228 (diffpir_amd/schedule.py progress_panels computes panel_of_step_host from those recipes). */
 typedef struct dpir_progress_desc {
     const int32_t* panel_of_step_host;   /* [n_entries]: the panel taken after step i (dpir_run_loop, dpir_run_dps_loop, dpir_run_deblur_grad_loop) or
-                                          * after row r (dpir_run_inpaint_loop: the last sub-step of the timestep), or -1 for none.  Copied. */
+                                          * after row r (dpir_run_inpaint_loop: the last sub-step of the timestep; dpir_run_ancestral_loop), or -1 for none.  Copied. */
     int32_t n_entries;                   /* must equal the loop call's n_steps / n_rows */
     int32_t n_panels;
     float* strip_f32; uint8_t* strip_u8; /* as dpir_progress_snapshot, for the loop's B, H, W; any may be NULL */
     float* masked_f32; uint8_t* masked_u8;   /* inpainting loops only (the descriptor's y_dev and mask_dev) */
     float* minmax_dev;
 } dpir_progress_desc;
-/* Arms the NEXT call of dpir_run_loop / dpir_run_inpaint_loop / dpir_run_dps_loop / dpir_run_deblur_grad_loop on this engine, and only that call: the
+/* Arms the NEXT call of dpir_run_loop / dpir_run_inpaint_loop / dpir_run_ancestral_loop / dpir_run_dps_loop / dpir_run_deblur_grad_loop on this engine, and only that call: the
  * arming is cleared when the call returns, whether it succeeded or not.  NULL disarms.  A step skipped by skip_dead_final_eval still yields its
  * panel (the unchanged x).  The snapshots are launched on the engine stream between the steps, outside the captured step graphs: an armed
  * call replays the same graphs as an unarmed one and computes the same result; an unarmed call launches nothing new.  The loop call returns
@@ -464,6 +464,53 @@ int dpir_grad_and_value_blur(dpir_engine* e, int through_network, const float* x
  * and the Philox streams as dpir_run_dps_loop.  Eager launches (no step graph); single GPU. */
 int dpir_run_deblur_grad_loop(dpir_engine* e, const dpir_loop_desc* d, const dpir_step* steps_host, const dpir_dps_coef* coefs_host, int n_steps,
                               int variant, float lambda_, const float* noise_ps_dev, const float* noise_yt_dev, float* out_f32_dev, uint8_t* out_u8_dev);
+
+/* ---- ancestral inpainting loops (main_ddpir.py:341-470, model_output_type 'pred_x_prev') ------ */
+/* task 'inpaint' with generate_mode 'repaint' (RePaint-style ancestral sampling) or 'vanilla' (plain DDPM ancestral sampling, the body of
+ * p_sample_loop) and iter_num_U 1: per visited timestep [the repaint mix, :356-358 ->] x = model_fn(x, 'pred_x_prev') (:365-366), i.e.
+ * diffusion.p_sample(clip_denoised=True) with the learned-range variance or, with ddim_sample, diffusion.ddim_sample(eta=0).  Nothing else
+ * happens in a step (:384-445 has no branch for these modes, the re-noise at :448 requires 'pred_xstart', the set-back at :462 requires
+ * u < iter_num_U - 1), and the final step is LIVE: x is replaced by the sample at t_i there too (t = 0: nonzero = 0).
+ * One row per visited step, all computed on the host (diffpir_amd/schedule.py build_ancestral_rows). */
+typedef struct dpir_ancestral_row {
+    int32_t t;            /* t_i: UNet timestep */
+    int32_t nonzero;      /* t != 0: p_sample's nonzero_mask (gaussian_diffusion.py:431-433) */
+    int32_t mix_next;     /* 1: a next row exists (generate_mode repaint applies its mix at the end of this step) */
+    int32_t reserved;
+    float c1, c2;         /* sqrt_recip_alphas_cumprod[t], sqrt_recipm1_alphas_cumprod[t]: eps -> x0 (gaussian_diffusion.py:328-333) */
+    float pc1, pc2, min_log, max_log;   /* as dpir_dps_coef */
+    float sa_prev, s1m_prev;            /* ddim_sample(eta = 0) only, as dpir_dps_coef */
+    float sa_t, s1m_t;    /* sqrt_alphas_cumprod / sqrt_1m_alphas_cumprod at t_i (driver's float32 tables): the mix ahead of the FIRST row */
+    float sa_n, s1m_n;    /* the same pair at the NEXT row's t_i (repaint mix of the next step, :356-358) */
+} dpir_ancestral_row;
+
+/* The data side of one step in one pass, in place on x_dev [B,3,H,W], behind the network call:
+ *   x0 = clamp(c1 x - c2 eps, -1, 1)  [-> x0_out_dev when given];  eps = out6[:, 0:3], v = out6[:, 3:6];
+ *   p_sample:  mean = pc1 x0 + pc2 x;  lv = frac max_log + (1 - frac) min_log, frac = (v + 1) / 2;  x = mean + nonzero expf(0.5 lv) n;
+ *   ddim != 0: x = x0 sa_prev + s1m_prev (c1 x - x0) / c2   (eta = 0: the sampler's draw is multiplied by 0 and not read);
+ *   generate_mode 1 (repaint) and mix_next: x = (sa_n (2y-1) + s1m_n n_repaint_next) mask + (1 - mask) x.
+ * Every expression is psample_kernel's / repaint_mix_kernel's, operation for operation: the pass equals dpir_p_sample's arithmetic followed by
+ * dpir_repaint_mix bit for bit.  out6_dev [B,out_channels,H,W] is the UNet's output; out_channels must be 6 (a learn_sigma model), else
+ * DPIR_ERR_UNSUPPORTED.  generate_mode: 1 repaint (y_dev in [0,1] and mask_dev uint8 {0,1} required) or 2 vanilla (both unused, may be NULL).
+ * Noise: n_ps_dev non-NULL -> host-fed tensors [B,3,H,W] (n_repaint_next_dev needed when the mix applies); n_ps_dev NULL -> Philox in place,
+ * keyed by (seed, image_offset + b) exactly as dpir_randn would produce them: stream 4 (step + 1) for the sampler's draw (as dpir_run_dps_loop)
+ * and 3 + 4 (step + 1) for the next step's mix (as dpir_run_loop / dpir_inpaint_step); ddim and nonzero = 0 draw nothing for the sampler.
+ * Asynchronous on the engine stream: the row travels by value in the kernel arguments.  DPIR_ERR_INVALID before any launch: a NULL engine,
+ * x, out6 or row, y / mask missing in repaint mode, generate_mode not 1 or 2, step < 0, a bad shape (see the conventions above), host noise
+ * without n_repaint_next_dev where the mix applies, n_repaint_next_dev without n_ps_dev. */
+int dpir_ancestral_step(dpir_engine* e, float* x_dev, const float* out6_dev, int out_channels, const float* y_dev, const uint8_t* mask_dev,
+                        const dpir_ancestral_row* row, int generate_mode, int ddim, const float* n_ps_dev, const float* n_repaint_next_dev,
+                        uint64_t seed, int64_t image_offset, int step, float* x0_out_dev, int B, int H, int W);
+
+/* Runs init -> [the first row's repaint mix ->] n_rows x (UNet -> dpir_ancestral_step) -> finalize for one batch, one captured graph for
+ * every step (d->use_graph).  d as in dpir_run_loop with task DPIR_TASK_INPAINT, sf 1; read from it: generate_mode (1 or 2), ddim_sample,
+ * sa_start / s1m_start, y / mask / labels, seed / image_offset, noise_init_dev and noise_rp_dev.  Host-fed noise (parity mode; all NULL ->
+ * device Philox, init: stream 0): noise_ps_dev [n_rows,B,3,H,W] in step order selects it and then needs d->noise_init_dev [B,3,H,W] and, in
+ * repaint mode, d->noise_rp_dev [n_rows,B,3,H,W].  d->skip_dead_final_eval is ignored: the final evaluation is live.  A model without
+ * learn_sigma is DPIR_ERR_UNSUPPORTED.  Progress panels (dpir_set_progress): the panel of row r shows x after that row's sample, before the
+ * next row's mix.  Synchronisation and the fused-hop guard: as dpir_run_loop. */
+int dpir_run_ancestral_loop(dpir_engine* e, const dpir_loop_desc* d, const dpir_ancestral_row* rows_host, int n_rows, const float* noise_ps_dev,
+                            float* out_f32_dev, uint8_t* out_u8_dev);
 
 /* ---- multi-GPU: the one collective of the path ------------------------------ */
 /* One process and one engine per GPU; images are block-partitioned over ranks, no exchange inside the loop (the reference is
