@@ -252,6 +252,7 @@ SIGNATURES = {
     "dpir_comm_destroy": (C.c_int, [C.c_void_p]),
     "dpir_degrade": (C.c_int, [C.c_void_p, C.POINTER(DegradeDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dpir_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "dpir_metrics_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dpir_lpips_load": (C.c_int, [C.c_void_p, C.POINTER(Tensor), C.c_int]),
     "dpir_lpips": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dpir_lpips_keep_taps": (C.c_int, [C.c_void_p, C.c_int]),

@@ -9,6 +9,7 @@
 #include "progress.h"
 #include "lpips.h"
 #include "fid.h"
+#include "metrics8.h"
 #include <math.h>
 #include <string.h>
 #include <stdlib.h>
@@ -230,6 +231,7 @@ void dpir_destroy(dpir_engine* e) {
     if (e->progress_premix) (void)hipFree(e->progress_premix);
     lpips_free(e);
     fid_free(e);
+    if (e->metrics8_buf) (void)hipFree(e->metrics8_buf);
     (void)hipStreamDestroy(e->stream);
     delete e;
 }
@@ -696,6 +698,46 @@ int dpir_metrics(dpir_engine* e, const float* x0, const uint8_t* gt, int B, int 
         const double mse = h[i].x / cnt, mse_y = h[i].y / cnt;
         psnr_host[i] = mse == 0.0 ? INFINITY : (float)(20.0 * log10(2.0 / sqrt(mse + 1e-10)));
         if (psnr_y_host) psnr_y_host[i] = mse_y == 0.0 ? INFINITY : (float)(20.0 * log10(2.0 / sqrt(mse_y + 1e-10)));
+    }
+    return DPIR_OK;
+}
+
+int dpir_metrics_u8(dpir_engine* e, const uint8_t* est_u8, const float* est_f32, const uint8_t* gt, int B, int H, int W, int border, double* out_host) {
+    if (!e || !gt || !out_host) return fail(e, invalid("dpir_metrics_u8: null argument"));
+    if ((est_u8 != nullptr) == (est_f32 != nullptr)) return fail(e, invalid("dpir_metrics_u8: exactly one of est_u8_dev and est_f32_dev must be given"));
+    API_TRY(e, check_shape("dpir_metrics_u8", B, H, W));
+    if (border < 0) return fail(e, invalid("dpir_metrics_u8: border must be >= 0 (got " + std::to_string(border) + ")"));
+    if ((long long)H - 2LL * border < kM8Taps || (long long)W - 2LL * border < kM8Taps)
+        return fail(e, invalid("dpir_metrics_u8: H - 2 border and W - 2 border must be >= 11 (no valid SSIM window; got H " + std::to_string(H) + ", W " +
+                               std::to_string(W) + ", border " + std::to_string(border) + ")"));
+    (void)hipSetDevice(e->device);
+    const size_t tiles = (size_t)metrics8_tiles(H, W, border);
+    if (tiles * (size_t)B > 0x7fffffffULL) return fail(e, invalid("dpir_metrics_u8: B * tiles is out of range"));
+    const size_t need = ((size_t)B * tiles + (size_t)B) * sizeof(Metrics8Sums);
+    if (need > e->metrics8_bytes) {
+        API_HIP(e, hipStreamSynchronize(e->stream));
+        if (e->metrics8_buf) (void)hipFree(e->metrics8_buf);
+        e->metrics8_buf = nullptr; e->metrics8_bytes = 0;
+        if (hipMalloc(&e->metrics8_buf, need) != hipSuccess) { (void)hipGetLastError(); return fail(e, Status{DPIR_ERR_NOMEM, "dpir_metrics_u8: hipMalloc failed"}); }
+        e->metrics8_bytes = need;
+    }
+    Metrics8Sums* partial = reinterpret_cast<Metrics8Sums*>(e->metrics8_buf);
+    Metrics8Sums* sums = partial + (size_t)B * tiles;
+    {
+        ProfScope ps(&e->prof, PC_ELEM);
+        API_TRY(e, launch_metrics8(e->stream, est_u8, est_f32, gt, B, H, W, border, partial, sums));
+    }
+    std::vector<Metrics8Sums> h(B);
+    int rc = dpir_d2h(e, h.data(), sums, sizeof(Metrics8Sums) * B);
+    if (rc != DPIR_OK) return rc;
+    const double hc = H - 2 * border, wc = W - 2 * border;
+    const double n_y = hc * wc, n_rgb = 3.0 * n_y, v_y = (hc - kM8Halo) * (wc - kM8Halo), v_rgb = 3.0 * v_y;
+    for (int i = 0; i < B; ++i) {
+        // utils_image.calculate_psnr: inf when mse == 0, else 20 * log10(255 / sqrt(mse)), float64 from the exact integer sum
+        out_host[4 * i + 0] = h[i].sse == 0 ? (double)INFINITY : 20.0 * log10(255.0 / sqrt((double)h[i].sse / n_rgb));
+        out_host[4 * i + 1] = h[i].sse_y == 0 ? (double)INFINITY : 20.0 * log10(255.0 / sqrt((double)h[i].sse_y / n_y));
+        out_host[4 * i + 2] = h[i].ssim / v_rgb;
+        out_host[4 * i + 3] = h[i].ssim_y / v_y;
     }
     return DPIR_OK;
 }

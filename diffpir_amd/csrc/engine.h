@@ -163,6 +163,7 @@ struct dpir_engine {
     bool lpips_keep_taps = false;                // dpir_lpips_keep_taps: the next dpir_lpips calls keep their five feature maps for dpir_lpips_read_tap
     dpir::FidState* fid = nullptr;               // dpir_fid_load (fid.hip); its arena is its own too
     bool fid_keep_taps = false;                  // dpir_fid_keep_taps: the next dpir_fid_features calls keep their 13 block outputs for dpir_fid_read_tap
+    void* metrics8_buf = nullptr; size_t metrics8_bytes = 0;     // dpir_metrics_u8's per-tile partial sums and per-image sums: a plain allocation too
     void* comm = nullptr; int comm_world = 1, comm_rank = 0;     // RCCL communicator (comm.cpp), or null
 
     dpir::Status resizer(int in_len, int sf, dpir::ResizerTab* out);

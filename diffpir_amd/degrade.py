@@ -1,8 +1,8 @@
 """Degradation synthesis and metrics on the device: the steps either side of the restoration loop.
 
 `degrade` mirrors CustomDataset.__getitem__'s arithmetic (main_ddpir.py:84-114) for a batch of uint8 ground-truth images;
-`metrics` mirrors main_ddpir.py:482-517 (PSNR and PSNR on the Y channel), `lpips` main_ddpir.py:489-493; `fid_features` gives the Inception features of the FID column (README.md:119-141).  All are thin wrappers over
-dpir_degrade / dpir_metrics / dpir_lpips / dpir_fid_features; PSF and mask GENERATION (a few hundred scalar operations per image under the numpy RNG) stays on the host so that
+`metrics` mirrors main_ddpir.py:482-517 (PSNR and PSNR on the Y channel), `lpips` main_ddpir.py:489-493; `fid_features` gives the Inception features of the FID column (README.md:119-141); `metrics_u8` is the 8-bit protocol of the standalone programs (calculate_psnr / calculate_ssim on tensor2uint bytes, RGB and Y, main_ddpir_sisr.py:406, 459).  All are thin wrappers over
+dpir_degrade / dpir_metrics / dpir_lpips / dpir_fid_features / dpir_metrics_u8; PSF and mask GENERATION (a few hundred scalar operations per image under the numpy RNG) stays on the host so that
 kernels and masks remain bit-identical to the reference's.
 """
 from __future__ import annotations
@@ -72,6 +72,28 @@ def lpips(engine: Engine, x0, gt):
     out = np.empty(B, np.float32)
     engine._check(engine.lib.dpir_lpips(engine.h, _ptr(x0), _ptr(gt) if u8 else None, None if u8 else _ptr(gt), B, H, W, out.ctypes.data))
     return out
+
+
+def metrics_u8(engine: Engine, est, gt_u8, border: int = 0):
+    """Per-image (PSNR, PSNR-Y, SSIM, SSIM-Y) of the 8-bit result as four float64 arrays [B] (dpir_metrics_u8): util.calculate_psnr and
+    util.calculate_ssim on tensor2uint bytes and on their rgb2ycbcr Y byte, `border` pixels cropped from every side first.  est: uint8
+    [B,H,W,3] (what dpir_finalize writes) or float32 [B,3,H,W] in [0,1], un-clamped (quantised on the device to the same bytes); gt_u8:
+    uint8 [B,H,W,3]; DeviceArrays or numpy."""
+    if isinstance(est, np.ndarray):
+        est = engine.to_device(np.ascontiguousarray(est))
+    if isinstance(gt_u8, np.ndarray):
+        gt_u8 = engine.to_device(np.ascontiguousarray(gt_u8))
+    if np.dtype(gt_u8.dtype) != np.uint8 or len(tuple(gt_u8.shape)) != 4 or gt_u8.shape[3] != 3:
+        raise ValueError(f"metrics_u8: ground truth {gt_u8.dtype} {tuple(gt_u8.shape)} is not uint8 [B,H,W,3]")
+    B, H, W, _ = gt_u8.shape
+    u8 = np.dtype(est.dtype) == np.uint8
+    if tuple(est.shape) != ((B, H, W, 3) if u8 else (B, 3, H, W)) or not (u8 or np.dtype(est.dtype) == np.float32):
+        raise ValueError(f"metrics_u8: estimate {est.dtype} {tuple(est.shape)} does not go with the ground truth {tuple(gt_u8.shape)} "
+                         "(uint8 [B,H,W,3] or float32 [B,3,H,W])")
+    out = np.empty((B, 4), np.float64)
+    engine._check(engine.lib.dpir_metrics_u8(engine.h, _ptr(est) if u8 else None, None if u8 else _ptr(est), _ptr(gt_u8), B, H, W, int(border),
+                                             out.ctypes.data))
+    return out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy(), out[:, 3].copy()
 
 
 def fid_features(engine: Engine, img):

@@ -13,7 +13,9 @@ is not installed here), LPIPS is computed by the engine (dpir_lpips) from the tw
 is set and they are there (one WARNING and no LPIPS otherwise: never a metric on synthetic weights), and the batch's LPIPS is the mean over
 its images (the reference keeps image 0's score times the batch size, main_ddpir.py:491: the same thing at batch_size 1).  `calc_FID: true` (an engine
 key: the reference leaves FID to pytorch-fid on the saved images) accumulates the FID Inception features of every restored batch and of the ground
-truth (dpir_fid_features) and logs the Frechet distance per sweep point, when model_zoo holds pytorch-fid's weight file.  With no
+truth (dpir_fid_features) and logs the Frechet distance per sweep point, when model_zoo holds pytorch-fid's weight file.  `calc_SSIM: true`
+(an engine key, no weight file) adds the 8-bit protocol of the reference's standalone programs (dpir_metrics_u8): PSNR and SSIM of the uint8 result, RGB and
+Y, with the border cropped first (sf for task sr, else 0; `metrics_border` overrides), per batch and per sweep point.  With no
 dataset / checkpoint on disk it falls back to synthetic ground truth and synthetic weights, saying so in the log.
 """
 from __future__ import annotations
@@ -175,15 +177,45 @@ def fid_rows(eng, img_u8_dev, n_local, n_b, ddist, rank, world):
     return ddist.all_gather_results(local.reshape(-1, fid_host.FEATURES), n_b, rank, world, engine=eng)
 
 
-def metric_rows(eng, out_f32, gt_dev, with_lpips):
-    """float64 [n, 2 or 3]: per-image PSNR, PSNR-Y [, LPIPS] (dpir_metrics, dpir_lpips)."""
+def ssim_border(config):
+    """calc_SSIM (an engine key): None when it is off, else the border the 8-bit metrics crop first -- the reference's rule, sf for task sr and 0
+    otherwise (main_ddpir.py:552, 564, 573), unless the optional key metrics_border overrides it."""
+    if not bool(config.get("calc_SSIM", False)):
+        return None
+    override = config.get("metrics_border", None)
+    if override is not None:
+        return int(override)
+    return int(config.sf) if config.task == "sr" else 0
+
+
+U8_NAMES = ("PSNR(8-bit RGB)", "PSNR(8-bit Y)", "SSIM(RGB)", "SSIM(Y)")
+U8_UNITS = ("dB", "dB", "", "")
+
+
+def metric_rows(eng, out_f32, gt_dev, with_lpips, border=None):
+    """float64 [n, 2 or 3 (+ 4)]: per-image PSNR, PSNR-Y [, LPIPS] (dpir_metrics, dpir_lpips) and, with calc_SSIM (border not None), the four
+    8-bit columns PSNR, PSNR-Y, SSIM, SSIM-Y of dpir_metrics_u8 behind them."""
     cols = list(dgr.metrics(eng, out_f32, gt_dev))
     if with_lpips:
         cols.append(dgr.lpips(eng, out_f32, gt_dev))
+    if border is not None:
+        cols.extend(dgr.metrics_u8(eng, out_f32, gt_dev, border))
     return np.stack(cols, 1).astype(np.float64)
 
 
-def run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph, cache, with_lpips=False):
+def log_batch_u8(number, values):
+    """calc_SSIM: the batch's means of the four 8-bit columns, one line each, behind the batch line."""
+    for name, unit, v in zip(U8_NAMES, U8_UNITS, values):
+        log.info("batch%4d--> %s: %.4f%s", number, name, v, unit)
+
+
+def log_average_u8(config, sums, n):
+    for name, unit, v in zip(U8_NAMES, U8_UNITS, sums):
+        log.info("-----------> Average %s of (%s) scale factor: (%d), sigma: (%.3f): %.4f%s",
+                 name, config.testset_name, config.sf, config.noise_level_model, v / n, " dB" if unit else "")
+
+
+def run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph, cache, with_lpips=False, border=None):
     """The sweep loop of main() flattened into full batches (YAML `engine_batch_sweeps: true`): every batch holds batch_size (point, image) pairs
     and runs as ONE restore_batch call with per-image (lambda, zeta) and the images' global numbers as noise keys.  Each distinct image of a batch
     is degraded once, with the seed and image_offset the sequential driver uses, and its y / k / mask / ground-truth rows are gathered on the
@@ -193,7 +225,7 @@ def run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph,
     batches = flatten_sweeps(len(points), n_img, bs)
     cfg = loop_config(config, *points[0])
     values, t0 = [], time.time()
-    ncol = 3 if with_lpips else 2
+    ncol = (3 if with_lpips else 2) + (4 if border is not None else 0)
 
     def gather(parts, rows):
         """device rows: rows[j] = (part index, row inside it) -> one DeviceArray [len(rows), ...] (dpir_d2d per row), or None"""
@@ -227,7 +259,7 @@ def run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph,
             out_f32 = restore.restore_batch(eng, cfg, gather(ys, rows), k=gather(ks, rows), mask=gather(ms, rows), noise_source="device",
                                             seed=config.seed, use_graph=use_graph, out_u8=u8_local, _cache=cache,
                                             skip_dead_final_eval=bool(config.get("engine_skip_dead_final_eval", False)), per_image=pi)
-            per_img = metric_rows(eng, out_f32, gather(gts, rows), with_lpips)
+            per_img = metric_rows(eng, out_f32, gather(gts, rows), with_lpips, border)
         ddist.all_gather_results(u8_local, len(pairs), rank, world, engine=eng)           # the one collective of the path
         allm = ddist.all_gather_results(per_img.reshape(-1, ncol), len(pairs), rank, world, engine=eng)
         values.append([tuple(v) for v in allm])
@@ -236,7 +268,7 @@ def run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph,
     for (lambda_, zeta), per_point in zip(points, regroup_sweeps(batches, values, len(points), n_img)):
         if rank == 0:
             log.info("eta:%s, zeta:%s, lambda:%s, guidance_scale:%s", config.eta, zeta, lambda_, config.guidance_scale)
-        psnrs, psnrs_y, lps = [], [], []
+        psnrs, psnrs_y, lps, u8s = [], [], [], np.zeros(4)
         for i0 in range(0, n_img, bs):             # the sequential driver's batches of this point: the same averages, the same log lines
             chunk = np.asarray(per_point[i0:i0 + bs], np.float64)
             p, p_y = float(np.mean(chunk[:, 0])), float(np.mean(chunk[:, 1]))
@@ -246,6 +278,11 @@ def run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph,
                 lps.append(float(np.mean(chunk[:, 2])) * len(chunk))
             if rank == 0:
                 log_batch(i0 // bs + 1, p, lps[-1] / len(chunk) if with_lpips else None, sum(lps) / n_img)
+            if border is not None:
+                u8 = np.mean(chunk[:, -4:], axis=0)
+                u8s += u8 * len(chunk)
+                if rank == 0:
+                    log_batch_u8(i0 // bs + 1, u8)
         if rank == 0:
             log.info("-----------> Average PSNR(RGB) of (%s) scale factor: (%d), sigma: (%.3f): %.4f dB  [%.2f images/s on %d GPU(s)]",
                      config.testset_name, config.sf, config.noise_level_model, sum(psnrs) / n_img, len(points) * n_img / dt, world)
@@ -254,6 +291,8 @@ def run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph,
             if with_lpips:
                 log.info("-----------> Average LPIPS of (%s) scale factor: (%d), sigma: (%.3f): %.4f",
                          config.testset_name, config.sf, config.noise_level_model, sum(lps) / n_img)
+            if border is not None:
+                log_average_u8(config, u8s, n_img)
         results.append(sum(psnrs) / n_img)
     return results
 
@@ -520,7 +559,8 @@ def main(argv=None):
         model.load_state_dict(weights.synth_state_dict("ffhq" if config.model_name == "diffusion_ffhq_10m" else "imagenet256"))
 
     with_lpips = setup_lpips(eng, config)
-    ncol = 3 if with_lpips else 2
+    border = ssim_border(config)           # calc_SSIM: the 8-bit PSNR / SSIM columns (dpir_metrics_u8); None when off
+    ncol = (3 if with_lpips else 2) + (4 if border is not None else 0)
     imgs, names = load_images(config, args.synthetic, args.synthetic_size)
     with_fid = setup_fid(eng, config, len(imgs))
     fid_gt, fids = {}, []                  # ground-truth feature rows per batch (computed at the first sweep point, reused by the others); FID per point
@@ -541,13 +581,14 @@ def main(argv=None):
         ddist.check_dps_sharding(eng, loop_config(config, *sweeps(config)[0]), min(config.batch_size, len(imgs) - i0), world)
     points = sweeps(config)[:args.max_sweeps] if args.max_sweeps else sweeps(config)
     if batch_sweeps:
-        results = run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph, cache, with_lpips)
+        results = run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph, cache, with_lpips, border)
         points = []
     for si, (lambda_, zeta) in enumerate(points):
         cfg = loop_config(config, lambda_, zeta)
         if rank == 0:
             log.info("eta:%s, zeta:%s, lambda:%s, guidance_scale:%s", config.eta, zeta, lambda_, config.guidance_scale)
         psnrs, psnrs_y, lps, t0, n = [], [], [], time.time(), 0
+        u8s = np.zeros(4)
         fid_out = fid_host.FidStats()
         for i0 in range(0, len(imgs), config.batch_size):
             gt = imgs[i0:i0 + config.batch_size]                           # uint8 [n,H,W,3]
@@ -609,7 +650,7 @@ def main(argv=None):
                 out_f32 = restore.restore_batch(eng, cfg, y, k=ops.get("k"), mask=None if dps_mode else ops.get("mask"), noise_source=noise,
                                                 predrawn=drawn, noise_fn=dps_nf, seed=config.seed, image_offset=i0 + lo, use_graph=use_graph and not deb_grad, out_u8=u8_local, _cache=cache,
                                                 skip_dead_final_eval=bool(config.get("engine_skip_dead_final_eval", False)), progress=pg)
-                per_img = metric_rows(eng, out_f32, ops["gt"], with_lpips)         # dpir_metrics: per-image PSNR / PSNR-Y; dpir_lpips
+                per_img = metric_rows(eng, out_f32, ops["gt"], with_lpips, border)     # dpir_metrics: per-image PSNR / PSNR-Y; dpir_lpips; dpir_metrics_u8
                 if pg is not None:
                     emit_progress(config, pg, names[i0 + lo:i0 + hi], lambda_, per_img[:, 0].astype(np.float32))
             if with_fid:
@@ -626,6 +667,11 @@ def main(argv=None):
                 lps.append(float(np.mean(allm[:, 2])) * n_b)           # the mean over the batch's images (Q: the reference keeps image 0's)
             if rank == 0:
                 log_batch(i0 // config.batch_size + 1, p, lps[-1] / n_b if with_lpips else None, sum(lps) / len(imgs))
+            if border is not None:
+                u8 = np.mean(allm[:, -4:], axis=0)
+                u8s += u8 * n_b
+                if rank == 0:
+                    log_batch_u8(i0 // config.batch_size + 1, u8)
         dt = time.time() - t0
         if rank == 0:
             log.info("-----------> Average PSNR(RGB) of (%s) scale factor: (%d), sigma: (%.3f): %.4f dB  [%.2f images/s on %d GPU(s)]",
@@ -635,6 +681,8 @@ def main(argv=None):
             if with_lpips:
                 log.info("-----------> Average LPIPS of (%s) scale factor: (%d), sigma: (%.3f): %.4f",
                          config.testset_name, config.sf, config.noise_level_model, sum(lps) / n)
+            if border is not None:
+                log_average_u8(config, u8s, n)
         if with_fid:
             gt_stats = fid_host.FidStats()
             for key in sorted(fid_gt):

@@ -557,6 +557,28 @@ int dpir_degrade(dpir_engine* e, const dpir_degrade_desc* d, const uint8_t* gt_u
  * calculate_psnr_batch: it is within 2e-5 dB of the float64 value at every image size, which the float32 evaluation is not (1.7e-4 dB on
  * a 63-pixel image at 87 dB); the two agree to 2e-5 dB on the reference's fixture.  Identical images give +inf in both. */
 int dpir_metrics(dpir_engine* e, const float* x0_dev, const uint8_t* gt_u8_dev, int B, int H, int W, float* psnr_host, float* psnr_y_host);
+/* The 8-bit protocol of the reference's standalone programs: util.calculate_psnr(img_E, img_H, border=border) on tensor2uint bytes
+ * (main_ddpir_deblur.py:380, main_ddpir_inpainting.py:325, main_ddpir_sisr.py:406), the same on the Y channel through
+ * rgb2ycbcr(only_y=True) (main_ddpir_sisr.py:459; utils_image.py:446-467), and util.calculate_ssim (utils_image.py:616-661) on both;
+ * border = sf for super-resolution (main_ddpir.py:552, main_ddpir_sisr.py:166).  The estimate is exactly one of est_u8_dev, uint8 [B,H,W,3]
+ * (what dpir_finalize writes), and est_f32_dev, float32 [B,3,H,W] in [0,1] and NOT clamped, which is quantised as tensor2uint does (clamp,
+ * x 255.0 in float32, round half to even: dpir_finalize's bytes).  gt_u8_dev: uint8 [B,H,W,3].  `border` pixels are cropped from all four
+ * sides first.  out_host: HOST array [B][4] of doubles (syncs): psnr, psnr_y, ssim, ssim_y.
+ *   psnr    20 log10(255 / sqrt(mse)) in float64 from the exact integer sum of squared byte differences over the three channels
+ *           (utils_image.py:586-599); +inf when the sum is 0.
+ *   Y byte  rint(fma(b, 24.966, fma(g, 128.553, r * 65.481)) / 255.0 + 16.0) in float64, half to even: the summation order that equals
+ *           numpy's dot on all 194 byte triplets that are exact .5 ties.  psnr_y and ssim_y are the same measures on the Y bytes.
+ *   ssim    float64 throughout.  Window g[i] = exp(-(i - 5)^2 / (2 1.5^2)), 11 taps, normalised to sum 1 (cv2.getGaussianKernel(11, 1.5)),
+ *           its outer product applied as a correlation at the valid positions only ([5:-5, 5:-5]), evaluated separably; five maps per
+ *           plane (x, y, x^2, y^2, xy); C1 = (0.01 255)^2, C2 = (0.03 255)^2; the mean of
+ *           ((2 mu1 mu2 + C1)(2 s12 + C2)) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)) over all valid positions of all three channels (the
+ *           reference's loop over range(3) passes the whole H x W x 3 array each time: its mean of three equal numbers is that value).
+ * An image's four numbers have the same bits wherever it sits in a batch, for every B and on every repeat (per-tile partial sums reduced
+ * in a fixed order, no floating-point atomics); identical images give +inf and exactly 1.  DPIR_ERR_INVALID before anything is enqueued: a
+ * null argument, both estimates or neither, B < 1, border < 0, H - 2 border < 11 or W - 2 border < 11 (the reference takes the mean of an
+ * empty map there). */
+int dpir_metrics_u8(dpir_engine* e, const uint8_t* est_u8_dev, const float* est_f32_dev, const uint8_t* gt_u8_dev, int B, int H, int W, int border,
+                    double* out_host);
 
 /* ---- LPIPS (calc_LPIPS: main_ddpir.py:489-493, 532-535, 543-545) --------------------------- */
 /* Replaces loss_fn_vgg = lpips.LPIPS(net='vgg') and its call loss_fn_vgg(x_0*2-1, img_H/255*2-1) (LPIPS v0.1, eval, normalize=False, spatial=False):
