@@ -86,6 +86,11 @@ class DegradeDesc(C.Structure):
                 ("kh", C.c_int32), ("kw", C.c_int32), ("noise_level_img", C.c_float), ("seed", C.c_uint64), ("image_offset", C.c_int64)]
 
 
+class ResultDesc(C.Structure):
+    """dpir_result_desc: one batch's saved measurement and L / E / H strip (dpir_result_panels); mode 0 kernel-inset strip, 1 inpainting strip."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "H", "W", "sf", "kh", "kw", "mode")]
+
+
 class Conv3Desc(C.Structure):
     """dpir_debug_conv3_desc (include/diffpir_debug.h): one 3x3 layer for dpir_debug_conv3_layer."""
     _fields_ = ([(n, C.c_int32) for n in ("B", "ca", "cb", "Cout", "H", "W", "mode", "res_mode", "scaled", "prologue", "route", "split",
@@ -253,6 +258,7 @@ SIGNATURES = {
     "dpir_degrade": (C.c_int, [C.c_void_p, C.POINTER(DegradeDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dpir_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dpir_metrics_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "dpir_result_panels": (C.c_int, [C.c_void_p, C.POINTER(ResultDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dpir_lpips_load": (C.c_int, [C.c_void_p, C.POINTER(Tensor), C.c_int]),
     "dpir_lpips": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dpir_lpips_keep_taps": (C.c_int, [C.c_void_p, C.c_int]),

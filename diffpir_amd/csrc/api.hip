@@ -10,6 +10,7 @@
 #include "lpips.h"
 #include "fid.h"
 #include "metrics8.h"
+#include "results.h"
 #include <math.h>
 #include <string.h>
 #include <stdlib.h>
@@ -739,6 +740,26 @@ int dpir_metrics_u8(dpir_engine* e, const uint8_t* est_u8, const float* est_f32,
         out_host[4 * i + 2] = h[i].ssim / v_rgb;
         out_host[4 * i + 3] = h[i].ssim_y / v_y;
     }
+    return DPIR_OK;
+}
+
+int dpir_result_panels(dpir_engine* e, const dpir_result_desc* d, const float* y, const uint8_t* kv, const uint8_t* est, const uint8_t* gt,
+                       uint8_t* L_u8, uint8_t* leh_u8) {
+    if (!e || !d) return fail(e, invalid("dpir_result_panels: null argument"));
+    API_TRY(e, check_shape("dpir_result_panels", d->B, d->H, d->W, d->sf));
+    if (d->mode != 0 && d->mode != 1) return fail(e, invalid("dpir_result_panels: mode must be 0 (kernel-inset strip) or 1 (inpainting strip), got " + std::to_string(d->mode)));
+    if (d->mode == 1 && d->sf != 1) return fail(e, invalid("dpir_result_panels: the inpainting strip has sf 1 (got sf " + std::to_string(d->sf) + ")"));
+    if ((L_u8 || leh_u8) && !y) return fail(e, invalid("dpir_result_panels: an output needs y_dev"));
+    if (leh_u8 && (!est || !gt)) return fail(e, invalid("dpir_result_panels: the strip needs est_u8_dev and gt_u8_dev"));
+    const bool inset = kv && d->mode == 0;
+    if (inset && (d->kh < 1 || d->kw < 1)) return fail(e, invalid("dpir_result_panels: kh and kw must be >= 1 with kernel bytes"));
+    if (inset && (3LL * d->kh > d->H || 3LL * d->kw > d->W))
+        return fail(e, invalid("dpir_result_panels: the x 3 kernel inset must fit the image, 3 kh <= H and 3 kw <= W (got kh " + std::to_string(d->kh) + ", kw " +
+                               std::to_string(d->kw) + ", H " + std::to_string(d->H) + ", W " + std::to_string(d->W) + ")"));
+    (void)hipSetDevice(e->device);
+    ProfScope ps(&e->prof, PC_ELEM);
+    ResultArgs a{y, inset ? kv : nullptr, est, gt, L_u8, leh_u8, d->B, d->H, d->W, d->sf, inset ? d->kh : 0, inset ? d->kw : 0, e->cus};
+    API_TRY(e, launch_result_panels(e->stream, a));
     return DPIR_OK;
 }
 

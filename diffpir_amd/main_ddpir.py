@@ -15,7 +15,10 @@ its images (the reference keeps image 0's score times the batch size, main_ddpir
 key: the reference leaves FID to pytorch-fid on the saved images) accumulates the FID Inception features of every restored batch and of the ground
 truth (dpir_fid_features) and logs the Frechet distance per sweep point, when model_zoo holds pytorch-fid's weight file.  `calc_SSIM: true`
 (an engine key, no weight file) adds the 8-bit protocol of the reference's standalone programs (dpir_metrics_u8): PSNR and SSIM of the uint8 result, RGB and
-Y, with the border cropped first (sf for task sr, else 0; `metrics_border` overrides), per batch and per sweep point.  With no
+Y, with the border cropped first (sf for task sr, else 0; `metrics_border` overrides), per batch and per sweep point.
+`engine_save_results: true` (an engine key, default false) makes the driver honour the reference's `save_E` / `save_L` / `save_LEH`: the restored
+image, the measurement, the L / E / H strip and, for task deblur, the kernel picture are written under results/<result_name>/ with the reference's
+file names (result_file_names; dpir_result_panels builds the L and LEH bytes), encoded by a small thread pool while the next batch runs.  With no
 dataset / checkpoint on disk it falls back to synthetic ground truth and synthetic weights, saying so in the log.
 """
 from __future__ import annotations
@@ -24,6 +27,8 @@ import argparse
 import glob
 import logging
 import os
+import queue
+import threading
 import time
 
 import numpy as np
@@ -215,11 +220,12 @@ def log_average_u8(config, sums, n):
                  name, config.testset_name, config.sf, config.noise_level_model, v / n, " dB" if unit else "")
 
 
-def run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph, cache, with_lpips=False, border=None):
+def run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph, cache, with_lpips=False, border=None, names=None, rw=None):
     """The sweep loop of main() flattened into full batches (YAML `engine_batch_sweeps: true`): every batch holds batch_size (point, image) pairs
     and runs as ONE restore_batch call with per-image (lambda, zeta) and the images' global numbers as noise keys.  Each distinct image of a batch
     is degraded once, with the seed and image_offset the sequential driver uses, and its y / k / mask / ground-truth rows are gathered on the
-    device.  Logs and returns what the sequential loop does: one average PSNR per point, in the same order."""
+    device.  Logs and returns what the sequential loop does: one average PSNR per point, in the same order.  rw (engine_save_results): one E file
+    per (point, image) row -- the names carry lambda and zeta -- L and the kernel picture at each image's first point, the strip at its last."""
     n_img, bs = len(imgs), config.batch_size
     H, W = imgs.shape[1], imgs.shape[2]
     batches = flatten_sweeps(len(points), n_img, bs)
@@ -243,7 +249,7 @@ def run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph,
         wanted = {g for _, g in mine}
         u8_local = eng.empty((hi - lo, H, W, 3), np.uint8)
         per_img = np.zeros((0, ncol))
-        where, ys, ks, ms, gts = {}, [], [], [], []
+        where, ys, ks, ms, gts, khs = {}, [], [], [], [], []
         for g0, cnt in image_runs(list(dict.fromkeys(g for _, g in pairs))):
             k_all, mask_all = make_operators(config, cnt, g0, H, W)          # every rank draws every operator of the batch (seeded numpy)
             if not wanted & set(range(g0, g0 + cnt)):
@@ -252,17 +258,24 @@ def run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph,
                                  sr_mode=config.sr_mode, seed=config.seed + 1, image_offset=g0)
             for r in range(cnt):
                 where[g0 + r] = (len(ys), r)
-            ys.append(y); ks.append(ops.get("k")); ms.append(ops.get("mask")); gts.append(ops["gt"])
+            ys.append(y); ks.append(ops.get("k")); ms.append(ops.get("mask")); gts.append(ops["gt"]); khs.append(k_all)
         if mine:
             rows = [where[g] for _, g in mine]
             pi = restore.PerImage(lambda_=[points[s][0] for s, _ in mine], zeta=[points[s][1] for s, _ in mine], image_index=[g for _, g in mine])
-            out_f32 = restore.restore_batch(eng, cfg, gather(ys, rows), k=gather(ks, rows), mask=gather(ms, rows), noise_source="device",
+            y_rows, gt_rows = gather(ys, rows), gather(gts, rows)
+            out_f32 = restore.restore_batch(eng, cfg, y_rows, k=gather(ks, rows), mask=gather(ms, rows), noise_source="device",
                                             seed=config.seed, use_graph=use_graph, out_u8=u8_local, _cache=cache,
                                             skip_dead_final_eval=bool(config.get("engine_skip_dead_final_eval", False)), per_image=pi)
-            per_img = metric_rows(eng, out_f32, gather(gts, rows), with_lpips, border)
+            per_img = metric_rows(eng, out_f32, gt_rows, with_lpips, border)
+            if rw is not None:
+                save_results(eng, config, rw, [names[g] for _, g in mine], pi.lambda_, pi.zeta, y_rows, u8_local, gt_rows,
+                             None if khs[0] is None else np.stack([khs[q][r] for q, r in rows]),
+                             first=[s == 0 for s, _ in mine], last=[s == len(points) - 1 for s, _ in mine])
         ddist.all_gather_results(u8_local, len(pairs), rank, world, engine=eng)           # the one collective of the path
         allm = ddist.all_gather_results(per_img.reshape(-1, ncol), len(pairs), rank, world, engine=eng)
         values.append([tuple(v) for v in allm])
+    if rw is not None:
+        rw.drain()                         # the images/s figure includes saving
     dt = time.time() - t0
     results = []
     for (lambda_, zeta), per_point in zip(points, regroup_sweeps(batches, values, len(points), n_img)):
@@ -482,11 +495,161 @@ def progress_file_names(config, img_name, ext, lambda_, current_time, psnr):
     return (img_name + "_sigma_{:.3f}_process_lambda_{:.3f}_{}_psnr_{:.4f}{}".format(config.noise_level_img, lambda_, current_time, psnr, ext), None)
 
 
-def write_png(path, rgb_u8):
-    """uint8 [H,W,3] -> PNG through PIL (cv2, the reference's writer, is not a dependency)."""
+def write_png(path, img_u8):
+    """uint8 [H,W,3] (RGB) or [H,W] (mode L, one channel: the kernel picture) -> the image file `path` names through PIL (cv2, the reference's
+    writer, is not a dependency).  The format follows the extension, as with cv2.imwrite: only a lossless one (.png) gives back the bytes."""
     from PIL import Image
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-    Image.fromarray(np.ascontiguousarray(rgb_u8)).save(path)
+    Image.fromarray(np.ascontiguousarray(img_u8)).save(path)        # a 2-D uint8 array becomes mode L, [H,W,3] mode RGB
+
+
+def result_options(config):
+    """(save_E, save_L, save_LEH, kernel picture).  The engine key engine_save_results (default false) arms the reference's three switches
+    (main_ddpir.py:497, 510; main_ddpir_deblur.py:43-45): with it off all four are off, whatever the YAML's save_* keys say.  The kernel picture
+    (main_ddpir.py:299, main_ddpir_deblur.py:177) goes with task deblur whenever one of the three is on."""
+    if not bool(config.get("engine_save_results", False)):
+        return False, False, False, False
+    e, l, leh = bool(config.get("save_E", False)), bool(config.get("save_L", False)), bool(config.get("save_LEH", False))
+    return e, l, leh, config.task == "deblur" and (e or l or leh)
+
+
+def result_file_names(config, full_name, lambda_, zeta):
+    """(E, L, LEH, kernel picture) file names of one image, `full_name` being its file name with the extension; the kernel's is None unless the
+    task is deblur.
+      driver main_ddpir              main_ddpir.py:499, 511, 299 (imsave_batch puts its prefix in front of the whole file name, utils_image.py:168-173);
+                                     that program has no save_LEH: the strip takes the standalone programs' names, main_ddpir_deblur.py:421 for
+                                     deblur and sr, main_ddpir_inpainting.py:347 for inpaint
+      driver main_ddpir_deblur       main_ddpir_deblur.py:398, 424, 421, 177
+      driver main_ddpir_inpainting   main_ddpir_inpainting.py:341, 344, 347 (no underscore in front of the model name of the strip)"""
+    img_name, ext = os.path.splitext(full_name)
+    driver = config.get("driver", "main_ddpir")
+    kernel = f"motion_kernel_{img_name}{ext}" if config.task == "deblur" else None
+    if driver == "main_ddpir_inpainting" or (driver == "main_ddpir" and config.task == "inpaint"):
+        leh = img_name + config.model_name + "_LEH" + ext
+    else:
+        leh = img_name + "_LEH" + ext
+    if driver == "main_ddpir":
+        return (f"{config.model_name}_x{config.sf}_lambda{lambda_:.4f}_zeta{zeta:.4f}_" + full_name, f"LR_x{config.sf}_" + full_name, leh, kernel)
+    est = img_name + "_" + config.model_name + ext
+    return est, img_name + ("_L" if driver == "main_ddpir_inpainting" else "_LR") + ext, leh, kernel
+
+
+def kernel_picture(k):
+    """uint8 [kh,kw]: what cv2.imwrite makes of the float array k * 255. * 200 (main_ddpir.py:299, main_ddpir_deblur.py:177) -- saturate to
+    [0, 255], round half to even -- evaluated in float64 on the host.  One channel."""
+    return np.rint(np.clip(np.asarray(k, np.float64) * 255. * 200, 0, 255)).astype(np.uint8)
+
+
+class ResultWriter:
+    """A bounded pool of threads around write_png: the files of one batch are encoded while the next batch's loop runs.  The worker count is
+    fixed (at most 8, never derived from the machine's CPU count); the queue holds at most two batches of files and submit() blocks when it
+    is full.  drain() waits until everything submitted is on disk and re-raises the first error a worker met; close() ends the threads."""
+    MAX_WORKERS = 8
+
+    def __init__(self, files_per_batch, workers=4, writer=write_png):
+        self.writer = writer
+        self.q = queue.Queue(maxsize=max(1, 2 * int(files_per_batch)))
+        self.error, self.lock = None, threading.Lock()
+        self.threads = [threading.Thread(target=self._work, name=f"result-writer-{i}", daemon=True)
+                        for i in range(max(1, min(int(workers), self.MAX_WORKERS)))]
+        for t in self.threads:
+            t.start()
+
+    def _work(self):
+        while True:
+            item = self.q.get()
+            try:
+                if item is None:
+                    return
+                self.writer(*item)
+            except BaseException as ex:        # kept for drain(); the worker goes on so that the queue never stalls
+                with self.lock:
+                    if self.error is None:
+                        self.error = ex
+            finally:
+                self.q.task_done()
+
+    def submit(self, path, array):
+        self.q.put((path, array))
+
+    def drain(self):
+        self.q.join()
+        with self.lock:
+            err, self.error = self.error, None
+        if err is not None:
+            self.close()
+            raise err
+
+    def close(self):
+        for _ in self.threads:
+            self.q.put(None)
+        for t in self.threads:
+            t.join()
+        self.threads = []
+
+
+def emit_results(config, names, lambdas, zetas, est_u8=None, L_u8=None, leh_u8=None, k=None, submit=write_png, first=None, last=None):
+    """The files the reference saves after one batch (main_ddpir.py:299, 497-511; main_ddpir_deblur.py:177, 397-424;
+    main_ddpir_inpainting.py:340-347), for the rows of the batch: est_u8 [n,H,W,3], L_u8 [n,h,w,3], leh_u8 [n,H,3W,3] (degrade.result_panels),
+    k [n,1,kh,kw] host PSFs.  lambdas / zetas: one number, or one per row (engine_batch_sweeps).  first[j] / last[j] (default all true): row j is
+    its image's first / last sweep point -- L and the kernel picture are written at the first, the strip, whose name carries no lambda, at the
+    last, as the point-by-point driver leaves them.  Every file goes through submit(path, array).  Nothing is written, and submit is never
+    called, unless engine_save_results is on.  Returns the paths."""
+    save_E, save_L, save_LEH, save_k = result_options(config)
+    if not (save_E or save_L or save_LEH):
+        return []
+    n = len(names)
+    lambdas = [lambdas] * n if np.ndim(lambdas) == 0 else list(lambdas)
+    zetas = [zetas] * n if np.ndim(zetas) == 0 else list(zetas)
+    out_dir, paths = result_dir(config), []
+
+    def put(name, array):
+        paths.append(os.path.join(out_dir, name))
+        submit(paths[-1], array)
+    for j, full in enumerate(names):
+        e_name, l_name, leh_name, k_name = result_file_names(config, full, lambdas[j], zetas[j])
+        is_first, is_last = first is None or first[j], last is None or last[j]
+        if save_k and k is not None and is_first:
+            put(k_name, kernel_picture(np.asarray(k[j]).reshape(np.asarray(k[j]).shape[-2:])))
+        if save_E:
+            put(e_name, est_u8[j])
+        if save_L and is_first:
+            put(l_name, L_u8[j])
+        if save_LEH and is_last:
+            put(leh_name, leh_u8[j])
+    return paths
+
+
+def save_results(eng, config, rw, names, lambdas, zetas, y, est_u8_dev, gt_dev, k, first=None, last=None):
+    """One batch's saved files from the device arrays of its loop: the L and LEH bytes through degrade.result_panels (dpir_result_panels) when
+    asked for, E from the loop's out_u8, the kernel picture from the host PSFs; all handed to the writer pool."""
+    save_E, save_L, save_LEH, _ = result_options(config)
+    # L is used at an image's first sweep point only, the strip at its last: a batch of middle points computes and downloads neither
+    want_L = save_L and (first is None or any(first))
+    want_LEH = save_LEH and (last is None or any(last))
+    L = leh = None
+    if want_L or want_LEH:
+        # the PSFs are the strip's inset: without the strip they are not passed, and an image smaller than 3 x the kernel still gets its L
+        L, leh = dgr.result_panels(eng, y, est_u8_dev, gt_dev, k=k if want_LEH and config.task != "inpaint" else None, sf=config.sf,
+                                   mode="inpaint" if config.task == "inpaint" else "kernel", want_L=want_L, want_LEH=want_LEH)
+    return emit_results(config, names, lambdas, zetas, est_u8=est_u8_dev.numpy() if save_E else None, L_u8=L, leh_u8=leh, k=k, submit=rw.submit,
+                        first=first, last=last)
+
+
+def make_result_writer(config, H, W):
+    """None unless engine_save_results arms one of the save_* keys; else the writer pool, after the one refusal that can be made ahead of all
+    work: a strip whose x 3 kernel inset does not fit the image (the reference's slice assignment raises there, main_ddpir_deblur.py:418)."""
+    opts = result_options(config)
+    if not any(opts):
+        return None
+    if opts[2] and config.task in ("deblur", "sr"):
+        state = np.random.get_state()          # the Gaussian PSF recipe seeds and draws from numpy's global generator
+        k, _ = make_operators(config, 1, 0, H, W)
+        np.random.set_state(state)
+        if 3 * k.shape[2] > H or 3 * k.shape[3] > W:
+            raise ValueError(f"save_LEH: the kernel inset is 3 x {k.shape[2]} by 3 x {k.shape[3]} pixels, the images are {H} x {W} "
+                             "(main_ddpir_deblur.py:418 fails there too)")
+    return ResultWriter(config.batch_size * sum(bool(o) for o in opts))
 
 
 def emit_progress(config, pg, names, lambda_, psnrs, current_time=None, writer=write_png, logger=None):
@@ -580,8 +743,14 @@ def main(argv=None):
     for i0 in range(0, len(imgs), config.batch_size):
         ddist.check_dps_sharding(eng, loop_config(config, *sweeps(config)[0]), min(config.batch_size, len(imgs) - i0), world)
     points = sweeps(config)[:args.max_sweeps] if args.max_sweeps else sweeps(config)
+    try:
+        rw = make_result_writer(config, imgs.shape[1], imgs.shape[2])   # engine_save_results; None when off: nothing below touches a file
+    except ValueError:
+        ddist.shutdown()
+        eng.close()
+        raise
     if batch_sweeps:
-        results = run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph, cache, with_lpips, border)
+        results = run_batched_sweeps(eng, config, points, imgs, ddist, rank, world, use_graph, cache, with_lpips, border, names=names, rw=rw)
         points = []
     for si, (lambda_, zeta) in enumerate(points):
         cfg = loop_config(config, lambda_, zeta)
@@ -653,6 +822,8 @@ def main(argv=None):
                 per_img = metric_rows(eng, out_f32, ops["gt"], with_lpips, border)     # dpir_metrics: per-image PSNR / PSNR-Y; dpir_lpips; dpir_metrics_u8
                 if pg is not None:
                     emit_progress(config, pg, names[i0 + lo:i0 + hi], lambda_, per_img[:, 0].astype(np.float32))
+                if rw is not None:         # this rank's shard: names are disjoint across ranks, no collective
+                    save_results(eng, config, rw, names[i0 + lo:i0 + hi], lambda_, zeta, y, u8_local, ops["gt"], None if k_all is None else k_all[sl])
             if with_fid:
                 if i0 not in fid_gt:
                     fid_gt[i0] = fid_rows(eng, ops["gt"] if hi > lo else None, hi - lo, n_b, ddist, rank, world)
@@ -672,6 +843,8 @@ def main(argv=None):
                 u8s += u8 * n_b
                 if rank == 0:
                     log_batch_u8(i0 // config.batch_size + 1, u8)
+        if rw is not None:
+            rw.drain()                     # the images/s line includes saving; a later sweep point may write the same path again
         dt = time.time() - t0
         if rank == 0:
             log.info("-----------> Average PSNR(RGB) of (%s) scale factor: (%d), sigma: (%.3f): %.4f dB  [%.2f images/s on %d GPU(s)]",
@@ -694,6 +867,8 @@ def main(argv=None):
         results.append(sum(psnrs) / n)
     if fids and rank == 0:
         log.info("-----------> Average FID of (%s) over %d sweep point(s): %.4f", config.testset_name, len(fids), sum(fids) / len(fids))
+    if rw is not None:
+        rw.close()
     ddist.shutdown()
     eng.close()
     return results

@@ -580,6 +580,31 @@ int dpir_metrics(dpir_engine* e, const float* x0_dev, const uint8_t* gt_u8_dev, 
 int dpir_metrics_u8(dpir_engine* e, const uint8_t* est_u8_dev, const float* est_f32_dev, const uint8_t* gt_u8_dev, int B, int H, int W, int border,
                     double* out_host);
 
+/* ---- saved results (save_L / save_LEH) ------------------------------------------------------ */
+/* The bytes of the reference's saved measurement and of its L / E / H comparison strip for one batch, in one pass, asynchronous on the engine
+ * stream (like dpir_finalize).  Replaces
+ *   the measurement   util.single2uint(img_L) at its own h x w: main_ddpir.py:508-511, main_ddpir_deblur.py:423-424,
+ *                     main_ddpir_inpainting.py:343-344;
+ *   the strip, mode 0 main_ddpir_deblur.py:412-421 = main_ddpir_sisr.py:440-451: img_I = cv2.resize(img_L, x sf, INTER_NEAREST), the kernel
+ *                     bytes zoomed x 3 (INTER_NEAREST) written at img_I[:3kh, -3kw:], THEN img_L pasted at img_I[:h, :w], and
+ *                     np.concatenate([img_I, img_E, img_H], axis=1);
+ *   the strip, mode 1 main_ddpir_inpainting.py:346-347: np.concatenate([single2uint(img_L), img_E, img_H], axis=1) (sf = 1, no inset).
+ * y_dev float32 [B,3,h,w], h = H / sf, w = W / sf: what dpir_degrade wrote.  The L bytes are rint(clamp(y, 0, 1) 255) in float32, half to even
+ * (dpir_finalize's conversion): single2uint of the ENGINE's float32 measurement, bit for bit np.uint8((y.clip(0, 1) * 255.).round()); not
+ * single2uint of the reference's float64 img_L.  kv_u8_dev uint8 [B,kh,kw]: the host's single2uint(k / k.max()), or NULL for no inset (ignored
+ * in mode 1).  est_u8_dev, gt_u8_dev uint8 [B,H,W,3]: the loop's out_u8 and img_H.  Outputs, each may be NULL (not written; the inputs only it
+ * needs may then be NULL too): L_u8_out_dev [B,h,w,3]; leh_u8_out_dev [B,H,3W,3], whose panel 0 is per pixel the native L inside [0,h) x [0,w),
+ * else the inset (grey on three channels, source kv[Y / 3][(X - (W - 3kw)) / 3]) inside rows [0,3kh) and columns [W - 3kw, W), else the zoom
+ * (source pixel (Y / sf, X / sf)) -- the reference's write order as a priority; with sf = 1 the paste hides the inset entirely, as there.  Panels
+ * 1 and 2 are est and gt.  DPIR_ERR_INVALID before anything is launched: B < 1, sf < 1 or not dividing H and W, a mode other than 0 / 1, mode
+ * 1 with sf != 1, kernel bytes with 3kh > H or 3kw > W (the reference's slice assignment raises there), a missing input. */
+typedef struct dpir_result_desc {
+    int32_t B, H, W, sf, kh, kw;
+    int32_t mode;                        /* 0: kernel-inset strip (deblurring / super-resolution); 1: inpainting strip */
+} dpir_result_desc;
+int dpir_result_panels(dpir_engine* e, const dpir_result_desc* d, const float* y_dev, const uint8_t* kv_u8_dev, const uint8_t* est_u8_dev,
+                       const uint8_t* gt_u8_dev, uint8_t* L_u8_out_dev, uint8_t* leh_u8_out_dev);
+
 /* ---- LPIPS (calc_LPIPS: main_ddpir.py:489-493, 532-535, 543-545) --------------------------- */
 /* Replaces loss_fn_vgg = lpips.LPIPS(net='vgg') and its call loss_fn_vgg(x_0*2-1, img_H/255*2-1) (LPIPS v0.1, eval, normalize=False, spatial=False):
  * the scaling layer (shift -.030 -.088 -.188, scale .458 .448 .450, applied before the first convolution's zero padding), the 13 convolutions of
