@@ -125,19 +125,12 @@ __global__ __launch_bounds__(256) void ancestral_step_kernel(AncestralStepArgs a
     }
 }
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 Status launch_ancestral_step(hipStream_t s, const AncestralStepArgs& a) {
     const size_t P = (size_t)3 * a.HW, q = (P + 3) / 4;
     // H*W % 4 == 0 keeps every image's base (n P, n 2P) and the v planes (+ P) on a 16-byte boundary
     bool vec = !a.scalar_only && a.HW % 4 == 0 && aligned16(a.x) && aligned16(a.out6) && aligned16(a.x0_out) && aligned16(a.premix_out);
-    if (!a.lp) vec = vec && aligned16(a.y) && (reinterpret_cast<uintptr_t>(a.mask) & 3u) == 0 && aligned16(a.nps) && aligned16(a.nrp_next);
-    // memory-bound: no more workgroups than the device keeps resident (8 x 256 threads per CU), the rest by grid stride
-    const size_t cap = (size_t)(a.cus > 0 ? a.cus : 256) * 8;
-    const unsigned gy = (unsigned)(a.B < 65535 ? a.B : 65535);
-    size_t gx = (q + 255) / 256, per_image = cap / gy ? cap / gy : 1;
-    if (gx > per_image) gx = per_image;
-    const dim3 grid((unsigned)gx, gy);
+    if (!a.lp) vec = vec && aligned16(a.y) && aligned4(a.mask) && aligned16(a.nps) && aligned16(a.nrp_next);
+    const dim3 grid = resident_grid(q, a.B, a.cus);
     if (vec) hipLaunchKernelGGL(ancestral_step_kernel<true>, grid, dim3(256), 0, s, a, P, (unsigned)q);
     else hipLaunchKernelGGL(ancestral_step_kernel<false>, grid, dim3(256), 0, s, a, P, (unsigned)q);
     DPIR_HIP(hipGetLastError());

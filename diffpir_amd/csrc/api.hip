@@ -1,6 +1,8 @@
 // C ABI (include/diffpir_engine.h): lifecycle, memory plumbing, operator entry points and the
-// restoration loop with hipGraph capture.  Each entry cites the reference interface it replaces in
+// restoration loops.  Each entry cites the reference interface it replaces in
 // the header; this file only validates, dispatches to the launchers and keeps the error string.
+// The whole-loop entries share one skeleton ("whole loop" below): loop_prologue -> film_table / loop_init -> run_steps (the one
+// step driver with hipGraph capture; the gradient loops run an eager body instead) -> loop_finish.
 #include "engine.h"
 #include "grad.h"
 #include "blur.h"
@@ -308,6 +310,9 @@ static Status upload_ints(dpir_engine* e, const char* name, const int64_t* host,
     DPIR_HIP(hipMemcpyAsync(*dev, tmp.data(), B * sizeof(int), hipMemcpyHostToDevice, e->stream));
     DPIR_HIP(hipStreamSynchronize(e->stream));
     return Status{};
+}
+static Status labels_match(const dpir_engine* e, const int64_t* labels_host) {
+    return (e->net.desc.num_classes > 0) != (labels_host != nullptr) ? invalid("labels iff class-conditional model") : Status{};
 }
 
 // One timestep for the whole batch (what model_fn passes): written on the device by a 1-workgroup kernel -- no host buffer, no copy and, unlike
@@ -840,8 +845,12 @@ int dpir_fid_read_tap(dpir_engine* e, int k, float* host_dst, size_t cap, size_t
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------ whole loop
+// Every whole-loop runner is put together from the pieces of this section: loop_prologue (the shared refusals and buffers), film_table, loop_init,
+// first_repaint_mix, denoise and loop_finish.  The three graph-capable runners (run_loop_once, run_inpaint_loop_once, run_ancestral_loop_once) hand their
+// step to run_steps, the one place where a row becomes the current row and a step graph is looked up, captured or launched; run_grad_loop keeps an
+// eager body of its own between loop_init and loop_finish.
 namespace {
-struct LoopBufs { float *x, *x0, *out6, *n1, *n2, *init_src; int *t_dev, *y_dev; StepDev *steps_dev, *cur; LoopDev* lp;
+struct LoopBufs { int B, H, W; float *x, *x0, *out6, *n1, *n2, *init_src; int *t_dev, *y_dev; StepDev *steps_dev, *cur; LoopDev* lp;
                   float* film;      // film: hoisted FiLM table [n_steps][film_rows] (class-unconditional models) or null
                   // dpir_run_loop_per_image: the (tau, k1, k2, 0) table [n_steps][B] and the Philox image numbers [B] (both filled when per_image: a table
                   // the caller left out repeats the step's own scalars / image_offset + b); per_image selects the kernels' per-image instantiations
@@ -852,26 +861,44 @@ __global__ void fill_t_kernel(int* p, const StepDev* sp, int n) {
     if (i < n) p[i] = sp->t;
 }
 
-// init (main_ddpir.py:291-320): x_T from y, spectra of the batch
-Status loop_init(dpir_engine* e, const dpir_loop_desc& d, const LoopBufs& b, ProxState* prox) {
+// init (main_ddpir.py:291-320, main_ddpir_inpainting.py:190-193, main_ddpir_deblur.py:228-231): x_T = sa_start src + s1m_start n, both coefficients from
+// the host.  What differs between the loops is passed in, not read from d.task (the gradient loop over the blur operator is task deblur and has neither
+// spectra nor a mask): up_sf > 0 -- src is the bicubic up-sampling of y by up_sf (into b.init_src), 0 -- y itself; mask -- the known region keeps y
+// (inpainting), or null; prox -- the spectra of the batch to pre-calculate, or null.
+Status loop_init(dpir_engine* e, const dpir_loop_desc& d, const LoopBufs& b, int up_sf, const uint8_t* mask, ProxState* prox) {
     hipStream_t s = e->stream;
     const int B = d.B, H = d.H, W = d.W;
     const size_t total = (size_t)B * 3 * H * W;
     const float* src = d.y_dev;
-    if (d.task == DPIR_TASK_SR_BLUR || d.task == DPIR_TASK_SR_CUBIC) {
+    if (up_sf > 0) {
         ProfScope ps(&e->prof, PC_ELEM);
-        DPIR_TRY(launch_bicubic_up(s, d.y_dev, b.init_src, B * 3, H / d.sf, W / d.sf, d.sf));   // main_ddpir.py:295
+        DPIR_TRY(launch_bicubic_up(s, d.y_dev, b.init_src, B * 3, H / up_sf, W / up_sf, up_sf));   // main_ddpir.py:295
         src = b.init_src;
     }
     const float* n0 = d.noise_init_dev;
     if (!n0) { DPIR_TRY(launch_randn(s, b.n2, d.seed, 0, d.image_offset, B, (size_t)3 * H * W, nullptr, nullptr, b.per_image ? b.imgidx : nullptr)); n0 = b.n2; }
     {
         ProfScope ps(&e->prof, PC_ELEM);
-        DPIR_TRY(launch_init_x(s, src, d.task == DPIR_TASK_INPAINT ? d.mask_dev : nullptr, n0, d.sa_start, d.s1m_start, b.x, total));
+        DPIR_TRY(launch_init_x(s, src, mask, n0, d.sa_start, d.s1m_start, b.x, total));
     }
-    if (d.task == DPIR_TASK_DEBLUR || d.task == DPIR_TASK_SR_BLUR)
-        DPIR_TRY(prox_precalc(e, d.y_dev, d.k_dev, d.kh, d.kw, prox));
+    if (prox) DPIR_TRY(prox_precalc(e, d.y_dev, d.k_dev, d.kh, d.kw, prox));
     return Status{};
+}
+
+// The two fused loops, repaint: the first row's mix at its own noise level (main_ddpir_inpainting.py:244-246, main_ddpir.py:356-358); every later one
+// is applied by the fused pass of the row before it
+Status first_repaint_mix(dpir_engine* e, const dpir_loop_desc& d, const LoopBufs& b, float sa, float s1m) {
+    ProfScope ps(&e->prof, PC_ELEM);
+    const float* nr = d.noise_rp_dev;
+    if (!nr) { DPIR_TRY(launch_randn(e->stream, b.n2, d.seed, 3, d.image_offset, b.B, (size_t)3 * b.H * b.W)); nr = b.n2; }
+    return launch_repaint_mix(e->stream, b.x, d.y_dev, d.mask_dev, nr, sa, s1m, (size_t)b.B * 3 * b.H * b.W);
+}
+
+// The denoiser call of a graph-capable step: eps (and v) of b.x at the current row's timestep into b.out6.  cur_st is the StepDev at the head of the
+// fixed-address current row; with the hoisted FiLM table the network reads its row from there, without it the timestep vector is filled from it
+Status denoise(dpir_engine* e, const LoopBufs& b, const StepDev* cur_st) {
+    if (!b.film) hipLaunchKernelGGL(fill_t_kernel, dim3((b.B + 255) / 256), dim3(256), 0, e->stream, b.t_dev, cur_st, b.B);
+    return unet_forward(e, b.x, b.t_dev, b.y_dev, b.out6, b.B, b.H, b.W, b.film, b.film ? cur_st : nullptr);
 }
 
 // one iteration of main_ddpir.py:341-470; every per-step scalar is read on the device from b.cur
@@ -886,9 +913,8 @@ Status loop_step(dpir_engine* e, const dpir_loop_desc& d, const LoopBufs& b, Pro
         if (!nr) { DPIR_TRY(launch_randn(s, b.n1, d.seed, 3, d.image_offset, B, (size_t)3 * H * W, b.cur, b.lp, nullptr, b.per_image)); nr = b.n1; rstride = 0; }
         DPIR_TRY(launch_repaint_mix(s, b.x, d.y_dev, d.mask_dev, nr, 0.f, 0.f, total, b.cur, rstride, b.lp));
     }
-    if (!b.film) hipLaunchKernelGGL(fill_t_kernel, dim3((B + 255) / 256), dim3(256), 0, s, b.t_dev, b.cur, B);
-    DPIR_TRY(unet_forward(e, b.x, b.t_dev, b.y_dev, b.out6, B, H, W, b.film, b.film ? b.cur : nullptr));
-    bool fused = false;       // the data step and the re-noise inside the prox's own three launches (half layouts): nothing is left to do here
+    DPIR_TRY(denoise(e, b, b.cur));
+    bool fused = false;      // the data step and the re-noise inside the prox's own three launches (half layouts): nothing is left to do here
     DPIR_TRY(prox_fused_step(e, *prox, d, last, with_n1, b.x, b.out6, b.x0, b.cur, b.lp, &fused, b.per_image));
     if (fused) return Status{};
     {
@@ -926,11 +952,9 @@ Status loop_step(dpir_engine* e, const dpir_loop_desc& d, const LoopBufs& b, Pro
 
 extern "C" {
 
-static int run_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, int n_steps, const dpir_image_step* per_image,
-                         const int64_t* image_index, float* out_f32, uint8_t* out_u8);
-
 // Runs a whole-loop call and, in the f16 modes with the fused hop on, looks at the guard word afterwards: on a hop time-out the loop is run again
-// on the unfused path.  Shared by dpir_run_loop and dpir_run_inpaint_loop.
+// on the unfused path.  Every graph-capable entry goes through it (dpir_run_loop, dpir_run_loop_per_image, dpir_run_inpaint_loop,
+// dpir_run_ancestral_loop); the gradient loops do not (dpir_check_range reports a time-out inside them).
 static int run_with_hop_guard(dpir_engine* e, const std::function<int()>& once) {
     int rc = once();
     static const bool fuse_env_off = getenv("DPIR_FUSE_H1") && atoi(getenv("DPIR_FUSE_H1")) == 0;       // unet.hip: the hop is not used at all
@@ -944,23 +968,10 @@ static int run_with_hop_guard(dpir_engine* e, const std::function<int()>& once) 
     return once();
 }
 
-int dpir_run_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, int n_steps, float* out_f32, uint8_t* out_u8) {
-    ProgressOneShot one_shot{e};
-    return run_with_hop_guard(e, [&] { return run_loop_once(e, dd, steps, n_steps, nullptr, nullptr, out_f32, out_u8); });
-}
-int dpir_run_loop_per_image(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, int n_steps, const dpir_image_step* per_image,
-                            const int64_t* image_index, float* out_f32, uint8_t* out_u8) {
-    ProgressOneShot one_shot{e};
-    // refused before anything is enqueued: the first-order data step normalises by ONE residual norm of the whole batch (main_ddpir.py:425-427)
-    if (e && dd && per_image && dd->first_order)
-        return fail(e, Status{DPIR_ERR_UNSUPPORTED, "dpir_run_loop_per_image: the first-order data step (sub_1_analytic: false) has no per-image form: it "
-                                                    "normalises by a batch-wide residual norm"});
-    return run_with_hop_guard(e, [&] { return run_loop_once(e, dd, steps, n_steps, per_image, image_index, out_f32, out_u8); });
-}
-
-// The captured-step cache shared by dpir_run_loop and dpir_run_inpaint_loop: the graph for `key` (ws_generation is filled in here), or -- on a
-// miss -- `step` run eagerly once as a warm-up (every workspace buffer exists before capture; it is a real step of the loop, its result is kept:
-// *ran = true), then captured and cached, evicting the least recently used entry but never `keep_a` / `keep_b` (the partner graph of the same loop).
+// The captured-step cache of the engine, shared by every graph-capable loop through run_steps (GraphKey::loop keeps their entries apart): the graph
+// for `key` (ws_generation is filled in here), or -- on a miss -- `step` run eagerly once as a warm-up (every workspace buffer exists before capture;
+// it is a real step of the loop, its result is kept: *ran = true), then captured and cached, evicting the least recently used entry but never
+// `keep_a` / `keep_b` (the graphs the running loop already holds).
 static int cached_step_graph(dpir_engine* e, dpir_engine::GraphKey key, const std::function<Status()>& step, hipGraphExec_t keep_a, hipGraphExec_t keep_b,
                              hipGraphExec_t* out, bool* ran) {
     *ran = false;
@@ -985,36 +996,145 @@ static int cached_step_graph(dpir_engine* e, dpir_engine::GraphKey key, const st
     return DPIR_OK;
 }
 
+// What a whole-loop runner tells loop_prologue about itself
+struct LoopCall {
+    const char* entry;                      // the public entry's name: the prefix of the refusals
+    int n; const char* noun;                // length of the step / row table, and what the entry calls one of its entries
+    std::vector<char> last;                 // the table's `last` flags (empty: the table has none)
+    int mode_lo = 0;                        // generate_mode must lie in mode_lo .. 2 and is refused as "generate_mode must be <modes>";
+    const char* modes = "0 (DiffPIR), 1 (repaint) or 2 (vanilla)";      // null: not read (the gradient loops are told their variant)
+    bool x0 = false, n1 = false, init = false, t = false;      // the workspace buffers of LoopBufs it uses besides x, out6, n2 and the labels
+    Status own;                             // the entry's own refusal (task, shape, variant, host noise): reported after "no model", ahead of the shared ones
+};
+
+// The head of every whole-loop runner: what all of them refuse, then -- nothing is enqueued or allocated before this point -- a new range accounting
+// period, the workspace images and the labels.  (A workspace request past this point still precedes every capture: see run_steps.)
+static int loop_prologue(dpir_engine* e, const LoopCall& c, const dpir_loop_desc& d, LoopBufs* b) {
+    (void)hipSetDevice(e->device);
+    const std::string entry = c.entry;
+    if (!e->net.loaded) return fail(e, Status{DPIR_ERR_STATE, "dpir_load_unet has not been called"});
+    API_TRY(e, c.own);
+    if (c.modes && (d.generate_mode < c.mode_lo || d.generate_mode > 2)) return fail(e, invalid(entry + ": generate_mode must be " + c.modes));
+    API_TRY(e, labels_match(e, d.labels_host));
+    // the reference marks EVERY step with seq[i] == seq[-1] as final (two of them for quad skipping with iter_num > T/2): each is a dead
+    // denoiser call, prox and re-noise are skipped (main_ddpir.py:384, 448)
+    for (size_t i = 1; i < c.last.size(); ++i)
+        if (c.last[i - 1] && !c.last[i]) return fail(e, invalid(entry + ": a non-final " + c.noun + " may not follow a final " + c.noun));
+    API_TRY(e, progress_check(e, c.entry, c.n, d));
+    range_clear(e);
+    const size_t total = (size_t)d.B * 3 * d.H * d.W;
+    b->B = d.B; b->H = d.H; b->W = d.W;
+    API_TRY(e, e->ws.getT("loop#x", total, &b->x));
+    if (c.x0) API_TRY(e, e->ws.getT("loop#x0", total, &b->x0));
+    API_TRY(e, e->ws.getT("loop#out6", (size_t)d.B * e->net.desc.out_channels * d.H * d.W, &b->out6));
+    if (c.n1) API_TRY(e, e->ws.getT("loop#n1", total, &b->n1));
+    API_TRY(e, e->ws.getT("loop#n2", total, &b->n2));
+    if (c.init) API_TRY(e, e->ws.getT("loop#init", total, &b->init_src));
+    if (c.t) API_TRY(e, e->ws.getT("loop#t", (size_t)d.B, &b->t_dev));
+    API_TRY(e, upload_ints(e, "loop#y", d.labels_host, d.B, &b->y_dev));
+    return DPIR_OK;
+}
+
+// Time embedding + every ResBlock's FiLM projection for the timesteps ts, once per call (class-unconditional models: the timestep is batch-uniform).
+// Row i of the table serves the steps / rows whose StepDev::i is i.  *film stays null for a class-conditional model.
+static Status film_table(dpir_engine* e, const std::vector<int64_t>& ts, float** film) {
+    if (e->net.desc.num_classes != 0) return Status{};
+    const int n = (int)ts.size();
+    int* ts_dev = nullptr;
+    DPIR_TRY(e->ws.getT("loop#film", (size_t)n * e->net.film_rows, film));
+    DPIR_TRY(upload_ints(e, "loop#ts", ts.data(), n, &ts_dev));
+    return unet_film_table(e, ts_dev, n, *film);
+}
+
+// Repaint with a progress strip armed: the fused pass of the two fused loops mixes the next row's known region into x before x ever reaches memory,
+// so the rows that own a panel also write the pre-mix x to this scratch image, which the snapshot then reads.  (The alternative, forming the panel
+// inside the fused pass, would put the strip layout, the uint8 / masked outputs and the min/max reduction into that kernel a second time.)
+// A plain allocation, not a workspace buffer: see dpir_engine::progress_premix.
+static Status ensure_premix(dpir_engine* e, size_t total) {
+    if (e->progress_premix_bytes >= total * sizeof(float)) return Status{};
+    DPIR_HIP(hipStreamSynchronize(e->stream));
+    if (e->progress_premix) (void)hipFree(e->progress_premix);
+    e->progress_premix = nullptr; e->progress_premix_bytes = 0;
+    DPIR_HIP(hipMalloc((void**)&e->progress_premix, total * sizeof(float)));
+    e->progress_premix_bytes = total * sizeof(float);
+    return Status{};
+}
+
+// The tail of every whole-loop runner: the last entry's panel (read from panel_x) and x -> the caller's output
+static int loop_finish(dpir_engine* e, const dpir_loop_desc& d, const LoopBufs& b, int n, const float* panel_x, float* out_f32, uint8_t* out_u8) {
+    API_TRY(e, progress_emit(e, n - 1, panel_x, d));
+    ProfScope ps(&e->prof, PC_ELEM);
+    API_TRY(e, launch_finalize(e->stream, b.x, out_f32, out_u8, d.B, d.H * d.W));
+    return DPIR_OK;
+}
+
+// What a graph-capable loop hands to run_steps.  A row is classified as ROW_SKIP (nothing runs), ROW_DATA_ONLY (data_pass alone) or the graph slot
+// whose step runs it: dpir_run_loop has two (0 the ordinary step, 1 the final step), the fused loops one.
+enum { ROW_SKIP = -2, ROW_DATA_ONLY = -1 };
+struct StepLoop {
+    int n;                                                  // rows
+    const void* rows_dev; void* cur; size_t row_bytes;      // the device table and the fixed-address current row its steps read
+    std::function<int(int)> slot_of;                        // row -> ROW_SKIP | ROW_DATA_ONLY | slot
+    std::function<Status(int)> step;                        // slot -> the step: run eagerly, or recorded into the slot's graph
+    std::function<Status()> data_pass;                      // ROW_DATA_ONLY rows (only a loop that classifies one so sets it)
+    std::function<dpir_engine::GraphKey(int)> key_of;       // slot -> everything baked into its graph but the workspace generation
+    std::function<const float*(int)> panel_x;               // row -> the image its progress panel is read from once the row has run
+};
+
+// The step driver of the graph-capable loops.  Row i: the panel of row i - 1 first (a panel shows x after its row, and is taken when the next row
+// begins, or in loop_finish, so that a row skipped as dead yields its panel too); then the row's class; row i -> the current row; the step, eagerly
+// or as a graph.  One graph per slot serves all rows: a slot's first row looks it up in the engine's cache or, on a miss, IS the warm-up that
+// cached_step_graph runs eagerly before capturing.  No workspace request may fall between a capture and its replay: all of them precede this call
+// or happen inside the warm-up step.
+static int run_steps(dpir_engine* e, const dpir_loop_desc& d, const LoopBufs& b, const StepLoop& L, float* out_f32, uint8_t* out_u8) {
+    hipGraphExec_t g[2] = {nullptr, nullptr};
+    for (int i = 0; i < L.n; ++i) {
+        if (i > 0) API_TRY(e, progress_emit(e, i - 1, L.panel_x(i - 1), d));
+        const int slot = L.slot_of(i);
+        if (slot == ROW_SKIP) continue;
+        API_HIP(e, hipMemcpyAsync(L.cur, static_cast<const char*>(L.rows_dev) + (size_t)i * L.row_bytes, L.row_bytes, hipMemcpyDeviceToDevice, e->stream));
+        if (slot == ROW_DATA_ONLY) { API_TRY(e, L.data_pass()); continue; }
+        if (!d.use_graph) { API_TRY(e, L.step(slot)); continue; }
+        if (!g[slot]) {
+            bool ran = false;
+            if (int rc = cached_step_graph(e, L.key_of(slot), [&] { return L.step(slot); }, g[0], g[1], &g[slot], &ran)) return rc;
+            if (ran) continue;   // this row was executed eagerly
+        }
+        ProfScope ps(&e->prof, PC_LOOP);
+        API_HIP(e, hipGraphLaunch(g[slot], e->stream));
+    }
+    return loop_finish(e, d, b, L.n, L.panel_x(L.n - 1), out_f32, out_u8);
+}
+
 static int run_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, int n_steps, const dpir_image_step* per_image,
                          const int64_t* image_index, float* out_f32, uint8_t* out_u8) {
     if (!e || !dd || !steps || n_steps <= 0) return fail(e, invalid("dpir_run_loop: null argument"));
-    (void)hipSetDevice(e->device);
     const dpir_loop_desc& d = *dd;
-    if (!e->net.loaded) return fail(e, Status{DPIR_ERR_STATE, "dpir_load_unet has not been called"});
-    if (d.B <= 0 || d.H <= 0 || d.W <= 0 || d.sf < 1 || d.H % d.sf || d.W % d.sf) return fail(e, invalid("dpir_run_loop: bad shape"));
-    if (!d.y_dev) return fail(e, invalid("dpir_run_loop: y is required"));
-    if ((d.task == DPIR_TASK_DEBLUR || d.task == DPIR_TASK_SR_BLUR) && !d.k_dev) return fail(e, invalid("dpir_run_loop: task needs a PSF"));
-    if (d.task == DPIR_TASK_INPAINT && !d.mask_dev) return fail(e, invalid("dpir_run_loop: inpainting needs a mask"));
-    if (d.task < 0 || d.task > 3) return fail(e, invalid("dpir_run_loop: unknown task"));
-    if (d.generate_mode < 0 || d.generate_mode > 2) return fail(e, invalid("dpir_run_loop: generate_mode must be 0 (DiffPIR), 1 (repaint) or 2 (vanilla)"));
-    if (d.generate_mode != 0 && d.task != DPIR_TASK_INPAINT)
-        return fail(e, invalid("dpir_run_loop: repaint / vanilla are inpainting modes (main_ddpir.py:448 re-noises only for inpainting or DiffPIR)"));
-    if ((e->net.desc.num_classes > 0) != (d.labels_host != nullptr)) return fail(e, invalid("labels iff class-conditional model"));
-    if (d.first_order && (d.generate_mode != 0 || (d.task != DPIR_TASK_SR_BLUR && d.task != DPIR_TASK_SR_CUBIC)))
-        return fail(e, Status{DPIR_ERR_UNSUPPORTED, "the first-order data step (sub_1_analytic: false) is implemented for the DiffPIR mode of the "
-                                                    "super-resolution tasks (the reference's deblurring operator raises at main_ddpir.py:302)"});
-    API_TRY(e, progress_check(e, "dpir_run_loop", n_steps, d));
-    const int B = d.B, H = d.H, W = d.W;
-    const size_t total = (size_t)B * 3 * H * W;
-    range_clear(e);
+    const bool need_prox = d.task == DPIR_TASK_DEBLUR || d.task == DPIR_TASK_SR_BLUR;
+    bool with_n1 = false;
+    LoopCall c{"dpir_run_loop", n_steps, "step", std::vector<char>(n_steps)};
+    c.x0 = c.n1 = c.init = c.t = true;
+    for (int i = 0; i < n_steps; ++i) {
+        c.last[i] = steps[i].last != 0;
+        if (!steps[i].last && steps[i].es != 0.f) with_n1 = true;
+    }
+    c.own = [&]() -> Status {
+        if (d.B <= 0 || d.H <= 0 || d.W <= 0 || d.sf < 1 || d.H % d.sf || d.W % d.sf) return invalid("dpir_run_loop: bad shape");
+        if (!d.y_dev) return invalid("dpir_run_loop: y is required");
+        if (need_prox && !d.k_dev) return invalid("dpir_run_loop: task needs a PSF");
+        if (d.task == DPIR_TASK_INPAINT && !d.mask_dev) return invalid("dpir_run_loop: inpainting needs a mask");
+        if (d.task < 0 || d.task > 3) return invalid("dpir_run_loop: unknown task");
+        if (d.generate_mode != 0 && d.task != DPIR_TASK_INPAINT)
+            return invalid("dpir_run_loop: repaint / vanilla are inpainting modes (main_ddpir.py:448 re-noises only for inpainting or DiffPIR)");
+        if (d.first_order && (d.generate_mode != 0 || (d.task != DPIR_TASK_SR_BLUR && d.task != DPIR_TASK_SR_CUBIC)))
+            return Status{DPIR_ERR_UNSUPPORTED, "the first-order data step (sub_1_analytic: false) is implemented for the DiffPIR mode of the "
+                                                "super-resolution tasks (the reference's deblurring operator raises at main_ddpir.py:302)"};
+        if (with_n1 && d.noise_n2_dev && !d.noise_n1_dev) return invalid("dpir_run_loop: eta != 0 with host noise needs noise_n1_dev");
+        return Status{};
+    }();
     LoopBufs b{};
-    API_TRY(e, e->ws.getT("loop#x", total, &b.x));
-    API_TRY(e, e->ws.getT("loop#x0", total, &b.x0));
-    API_TRY(e, e->ws.getT("loop#out6", (size_t)B * e->net.desc.out_channels * H * W, &b.out6));
-    API_TRY(e, e->ws.getT("loop#n1", total, &b.n1));
-    API_TRY(e, e->ws.getT("loop#n2", total, &b.n2));
-    API_TRY(e, e->ws.getT("loop#init", total, &b.init_src));
-    API_TRY(e, e->ws.getT("loop#t", (size_t)B, &b.t_dev));
+    if (int rc = loop_prologue(e, c, d, &b)) return rc;
+    const int B = d.B, H = d.H, W = d.W;
     API_TRY(e, e->ws.getT("loop#steps", (size_t)n_steps, &b.steps_dev));
     API_TRY(e, e->ws.getT("loop#cur", (size_t)1, &b.cur));
     API_TRY(e, e->ws.getT("loop#lp", (size_t)1, &b.lp));
@@ -1023,10 +1143,9 @@ static int run_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_st
     API_TRY(e, e->ws.getT("loop#img", (size_t)n_steps * B, &b.img));
     API_TRY(e, e->ws.getT("loop#imgidx", (size_t)B, &b.imgidx));
     b.per_image = per_image != nullptr || image_index != nullptr;
-    API_TRY(e, upload_ints(e, "loop#y", d.labels_host, B, &b.y_dev));
-    const bool hoist_film = e->net.desc.num_classes == 0;
-    if (hoist_film) API_TRY(e, e->ws.getT("loop#film", (size_t)n_steps * e->net.film_rows, &b.film));
-    bool need_prox = d.task == DPIR_TASK_DEBLUR || d.task == DPIR_TASK_SR_BLUR;
+    std::vector<int64_t> ts(n_steps);
+    for (int i = 0; i < n_steps; ++i) ts[i] = steps[i].t;
+    API_TRY(e, film_table(e, ts, &b.film));
     ProxState& prox = e->loop_prox;
     if (need_prox) {
         bool reallocated = false;
@@ -1039,16 +1158,11 @@ static int run_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_st
     }
 
     // per-step scalar table and the per-batch device block -> device (two small H2D copies per batch)
-    bool with_n1 = false;
     {
         std::vector<StepDev> hs(n_steps);
         for (int i = 0; i < n_steps; ++i) {
             const dpir_step& st = steps[i];
             hs[i] = StepDev{st.t, st.last, i, 0, st.c1, st.c2, st.tau, st.sa_t, st.s1m_t, st.sa_p, st.k1, st.q, st.es, st.k2};
-            if (!st.last && st.es != 0.f) with_n1 = true;
-            // the reference marks EVERY step with seq[i] == seq[-1] as final (two of them for quad skipping with
-            // iter_num > T/2): each is a dead denoiser call, prox and re-noise are skipped (main_ddpir.py:384, 448)
-            if (i > 0 && steps[i - 1].last && !st.last) return fail(e, invalid("dpir_run_loop: a non-final step may not follow a final step"));
         }
         LoopDev hl{d.y_dev, d.mask_dev, d.noise_n1_dev, d.noise_n2_dev, d.noise_rp_dev, (unsigned long long)d.seed, (long long)d.image_offset,
                    b.per_image ? b.img : nullptr, b.per_image ? b.imgidx : nullptr, B, 0};
@@ -1070,50 +1184,39 @@ static int run_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_st
         API_HIP(e, hipMemcpyAsync(b.lp, &hl, sizeof(hl), hipMemcpyHostToDevice, e->stream));
         API_HIP(e, hipStreamSynchronize(e->stream));
     }
-    if (with_n1 && d.noise_n2_dev && !d.noise_n1_dev) return fail(e, invalid("dpir_run_loop: eta != 0 with host noise needs noise_n1_dev"));
+    const bool sr = d.task == DPIR_TASK_SR_BLUR || d.task == DPIR_TASK_SR_CUBIC;
+    API_TRY(e, loop_init(e, d, b, sr ? d.sf : 0, d.task == DPIR_TASK_INPAINT ? d.mask_dev : nullptr, need_prox ? &prox : nullptr));
 
-    if (b.film) {   // time embedding + every ResBlock's FiLM projection for all steps, once per batch (batch-uniform timestep)
-        std::vector<int64_t> ts(n_steps);
-        for (int i = 0; i < n_steps; ++i) ts[i] = steps[i].t;
-        int* ts_dev = nullptr;
-        API_TRY(e, upload_ints(e, "loop#ts", ts.data(), n_steps, &ts_dev));
-        API_TRY(e, unet_film_table(e, ts_dev, n_steps, b.film));
-    }
-    API_TRY(e, loop_init(e, d, b, &prox));
-    hipGraphExec_t g_step = nullptr, g_last = nullptr;
-    // a progress panel shows x after its step (the repaint mix of this loop opens the NEXT step): taken when the next iteration begins, or before finalize,
-    // so that a step skipped by skip_dead_final_eval yields its panel too
-    for (int i = 0; i < n_steps; ++i) {
-        API_TRY(e, progress_emit(e, i - 1, b.x, d));
-        const bool last = steps[i].last != 0;
-        if (last && d.skip_dead_final_eval) continue;
-        API_HIP(e, hipMemcpyAsync(b.cur, b.steps_dev + i, sizeof(StepDev), hipMemcpyDeviceToDevice, e->stream));
-        if (!d.use_graph) {
-            API_TRY(e, loop_step(e, d, b, &prox, last, with_n1));
-            continue;
-        }
-        hipGraphExec_t& g = last ? g_last : g_step;
-        if (!g) {
-            dpir_engine::GraphKey k{};
-            k.task = d.task; k.B = B; k.H = H; k.W = W; k.sf = d.sf; k.in_iter = d.in_iter; k.generate_mode = d.generate_mode;
-            k.kind = (last ? 1 : 0) | (with_n1 ? 2 : 0) | (d.first_order ? 4 : 0);
-            k.host_n1 = d.noise_n1_dev != nullptr; k.host_n2 = d.noise_n2_dev != nullptr; k.host_rp = d.noise_rp_dev != nullptr;
-            k.has_labels = d.labels_host != nullptr;
-            k.gamma = d.gamma; k.guidance = d.guidance;
-            k.per_image = per_image != nullptr; k.image_index = image_index != nullptr;
-            bool ran = false;
-            if (int rc = cached_step_graph(e, k, [&] { return loop_step(e, d, b, &prox, last, with_n1); }, g_step, g_last, &g, &ran)) return rc;
-            if (ran) continue;   // this step was executed eagerly
-        }
-        ProfScope ps(&e->prof, PC_LOOP);
-        API_HIP(e, hipGraphLaunch(g, e->stream));
-    }
-    API_TRY(e, progress_emit(e, n_steps - 1, b.x, d));
-    {
-        ProfScope ps(&e->prof, PC_ELEM);
-        API_TRY(e, launch_finalize(e->stream, b.x, out_f32, out_u8, B, H * W));
-    }
-    return DPIR_OK;
+    StepLoop L{n_steps, b.steps_dev, b.cur, sizeof(StepDev)};
+    // the repaint mix of this loop opens the NEXT step, so every panel is x itself; skip_dead_final_eval drops the dead final step(s) altogether
+    L.panel_x = [&](int) { return b.x; };
+    L.slot_of = [&](int i) { return !steps[i].last ? 0 : d.skip_dead_final_eval ? (int)ROW_SKIP : 1; };
+    L.step = [&](int slot) { return loop_step(e, d, b, &prox, slot == 1, with_n1); };
+    L.key_of = [&](int slot) {
+        dpir_engine::GraphKey k{};
+        k.task = d.task; k.B = B; k.H = H; k.W = W; k.sf = d.sf; k.in_iter = d.in_iter; k.generate_mode = d.generate_mode;
+        k.kind = (slot == 1 ? 1 : 0) | (with_n1 ? 2 : 0) | (d.first_order ? 4 : 0);
+        k.host_n1 = d.noise_n1_dev != nullptr; k.host_n2 = d.noise_n2_dev != nullptr; k.host_rp = d.noise_rp_dev != nullptr;
+        k.has_labels = d.labels_host != nullptr;
+        k.gamma = d.gamma; k.guidance = d.guidance;
+        k.per_image = per_image != nullptr; k.image_index = image_index != nullptr;
+        return k;
+    };
+    return run_steps(e, d, b, L, out_f32, out_u8);
+}
+
+int dpir_run_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, int n_steps, float* out_f32, uint8_t* out_u8) {
+    ProgressOneShot one_shot{e};
+    return run_with_hop_guard(e, [&] { return run_loop_once(e, dd, steps, n_steps, nullptr, nullptr, out_f32, out_u8); });
+}
+int dpir_run_loop_per_image(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, int n_steps, const dpir_image_step* per_image,
+                            const int64_t* image_index, float* out_f32, uint8_t* out_u8) {
+    ProgressOneShot one_shot{e};
+    // refused before anything is enqueued: the first-order data step normalises by ONE residual norm of the whole batch (main_ddpir.py:425-427)
+    if (e && dd && per_image && dd->first_order)
+        return fail(e, Status{DPIR_ERR_UNSUPPORTED, "dpir_run_loop_per_image: the first-order data step (sub_1_analytic: false) has no per-image form: it "
+                                                    "normalises by a batch-wide residual norm"});
+    return run_with_hop_guard(e, [&] { return run_loop_once(e, dd, steps, n_steps, per_image, image_index, out_f32, out_u8); });
 }
 
 // ------------------------------------------------------------------------------------------ inpainting with resampling (main_ddpir_inpainting.py)
@@ -1153,140 +1256,89 @@ int dpir_inpaint_step(dpir_engine* e, float* x, const float* eps, int eps_ch, co
 static int run_inpaint_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_inpaint_row* rows, int n_rows, const float* noise_back,
                                  float* out_f32, uint8_t* out_u8) {
     if (!e || !dd || !rows || n_rows <= 0) return fail(e, invalid("dpir_run_inpaint_loop: null argument"));
-    (void)hipSetDevice(e->device);
     const dpir_loop_desc& d = *dd;
-    if (!e->net.loaded) return fail(e, Status{DPIR_ERR_STATE, "dpir_load_unet has not been called"});
-    API_TRY(e, check_shape("dpir_run_inpaint_loop", d.B, d.H, d.W));
-    if (d.task != DPIR_TASK_INPAINT || d.sf != 1) return fail(e, invalid("dpir_run_inpaint_loop: the standalone inpainting program's loop: task must be inpainting, sf 1"));
-    if (!d.y_dev || !d.mask_dev) return fail(e, invalid("dpir_run_inpaint_loop: y and mask are required"));
-    if (d.generate_mode < 0 || d.generate_mode > 2) return fail(e, invalid("dpir_run_inpaint_loop: generate_mode must be 0 (DiffPIR), 1 (repaint) or 2 (vanilla)"));
-    if (d.first_order) return fail(e, Status{DPIR_ERR_UNSUPPORTED, "sub_1_analytic: false is a TODO in the reference (main_ddpir_inpainting.py:280-283)"});
-    if ((e->net.desc.num_classes > 0) != (d.labels_host != nullptr)) return fail(e, invalid("labels iff class-conditional model"));
-    const int B = d.B, H = d.H, W = d.W;
-    const size_t total = (size_t)B * 3 * H * W;
     const bool host = d.noise_n2_dev != nullptr;
-    bool with_n1 = false, any_back = false;
-    int n_pos = 0;
-    for (int r = 0; r < n_rows; ++r) {
-        const dpir_inpaint_row& w = rows[r];
-        if (!w.last && w.es != 0.f) with_n1 = true;
-        if (!w.last && w.back) any_back = true;
-        if (r > 0 && rows[r - 1].last && !w.last) return fail(e, invalid("dpir_run_inpaint_loop: a non-final row may not follow a final row"));
-        if (w.pos < 0 || w.pos >= n_rows || (r > 0 && (w.pos < rows[r - 1].pos || w.pos > rows[r - 1].pos + 1)) || (r == 0 && w.pos != 0))
-            return fail(e, invalid("dpir_run_inpaint_loop: pos must start at 0 and grow by 0 or 1 per row"));
-        if ((w.mix_next != 0) != (r + 1 < n_rows)) return fail(e, invalid("dpir_run_inpaint_loop: mix_next must be 1 on every row but the last"));
-        n_pos = w.pos + 1;
-    }
-    if (host) {
-        if (!d.noise_init_dev) return fail(e, invalid("dpir_run_inpaint_loop: host noise needs noise_init_dev"));
-        if (with_n1 && !d.noise_n1_dev) return fail(e, invalid("dpir_run_inpaint_loop: eta != 0 with host noise needs noise_n1_dev"));
-        if (any_back && !noise_back) return fail(e, invalid("dpir_run_inpaint_loop: iter_num_U > 1 with host noise needs noise_back_dev"));
-        if (d.generate_mode == 1 && !d.noise_rp_dev) return fail(e, invalid("dpir_run_inpaint_loop: repaint with host noise needs noise_rp_dev"));
-    } else if (d.noise_init_dev || d.noise_n1_dev || d.noise_rp_dev || noise_back) {
-        return fail(e, invalid("dpir_run_inpaint_loop: host noise needs noise_n2_dev (all null selects device noise)"));
-    }
-    API_TRY(e, progress_check(e, "dpir_run_inpaint_loop", n_rows, d));
-    // generate_mode repaint: the fused pass mixes the next sub-step's known region into x before x ever reaches memory, so the rows that own a
-    // panel also write the pre-mix x to a scratch image, which the snapshot then reads.  (The alternative, forming the panel inside the fused pass,
-    // would put the strip layout, the uint8 / masked outputs and the min/max reduction into that kernel a second time.)
+    LoopCall c{"dpir_run_inpaint_loop", n_rows, "row", std::vector<char>(n_rows)};
+    c.t = true;
+    for (int r = 0; r < n_rows; ++r) c.last[r] = rows[r].last != 0;
+    c.own = [&]() -> Status {
+        DPIR_TRY(check_shape("dpir_run_inpaint_loop", d.B, d.H, d.W));
+        if (d.task != DPIR_TASK_INPAINT || d.sf != 1) return invalid("dpir_run_inpaint_loop: the standalone inpainting program's loop: task must be inpainting, sf 1");
+        if (!d.y_dev || !d.mask_dev) return invalid("dpir_run_inpaint_loop: y and mask are required");
+        if (d.first_order) return Status{DPIR_ERR_UNSUPPORTED, "sub_1_analytic: false is a TODO in the reference (main_ddpir_inpainting.py:280-283)"};
+        bool with_n1 = false, any_back = false;
+        for (int r = 0; r < n_rows; ++r) {
+            const dpir_inpaint_row& w = rows[r];
+            if (!w.last && w.es != 0.f) with_n1 = true;
+            if (!w.last && w.back) any_back = true;
+            if (w.pos < 0 || w.pos >= n_rows || (r > 0 && (w.pos < rows[r - 1].pos || w.pos > rows[r - 1].pos + 1)) || (r == 0 && w.pos != 0))
+                return invalid("dpir_run_inpaint_loop: pos must start at 0 and grow by 0 or 1 per row");
+            if ((w.mix_next != 0) != (r + 1 < n_rows)) return invalid("dpir_run_inpaint_loop: mix_next must be 1 on every row but the last");
+        }
+        if (host) {
+            if (!d.noise_init_dev) return invalid("dpir_run_inpaint_loop: host noise needs noise_init_dev");
+            if (with_n1 && !d.noise_n1_dev) return invalid("dpir_run_inpaint_loop: eta != 0 with host noise needs noise_n1_dev");
+            if (any_back && !noise_back) return invalid("dpir_run_inpaint_loop: iter_num_U > 1 with host noise needs noise_back_dev");
+            if (d.generate_mode == 1 && !d.noise_rp_dev) return invalid("dpir_run_inpaint_loop: repaint with host noise needs noise_rp_dev");
+        } else if (d.noise_init_dev || d.noise_n1_dev || d.noise_rp_dev || noise_back) {
+            return invalid("dpir_run_inpaint_loop: host noise needs noise_n2_dev (all null selects device noise)");
+        }
+        return Status{};
+    }();
+    LoopBufs b{};
+    if (int rc = loop_prologue(e, c, d, &b)) return rc;
+    const int B = d.B, H = d.H, W = d.W;
     const dpir_engine::Progress& pg = e->progress;
     const bool premix = pg.armed && d.generate_mode == 1;
-    if (premix && e->progress_premix_bytes < total * sizeof(float)) {
-        API_HIP(e, hipStreamSynchronize(e->stream));
-        if (e->progress_premix) (void)hipFree(e->progress_premix);
-        e->progress_premix = nullptr; e->progress_premix_bytes = 0;
-        API_HIP(e, hipMalloc((void**)&e->progress_premix, total * sizeof(float)));
-        e->progress_premix_bytes = total * sizeof(float);
-    }
-    range_clear(e);
-    LoopBufs b{};
+    if (premix) API_TRY(e, ensure_premix(e, (size_t)B * 3 * H * W));
     InpaintRowDev *rows_dev = nullptr, *cur = nullptr;
     InpaintLoopDev* lp = nullptr;
-    API_TRY(e, e->ws.getT("loop#x", total, &b.x));
-    API_TRY(e, e->ws.getT("loop#out6", (size_t)B * e->net.desc.out_channels * H * W, &b.out6));
-    API_TRY(e, e->ws.getT("loop#n2", total, &b.n2));        // the init draw and the first repaint mix (device noise); the sub-steps draw in place
-    API_TRY(e, e->ws.getT("loop#t", (size_t)B, &b.t_dev));
     API_TRY(e, e->ws.getT("inpaint#rows", (size_t)n_rows, &rows_dev));
     API_TRY(e, e->ws.getT("inpaint#cur", (size_t)1, &cur));
     API_TRY(e, e->ws.getT("inpaint#lp", (size_t)1, &lp));
-    API_TRY(e, upload_ints(e, "loop#y", d.labels_host, B, &b.y_dev));
-    const bool hoist_film = e->net.desc.num_classes == 0;
-    if (hoist_film) API_TRY(e, e->ws.getT("loop#film", (size_t)n_pos * e->net.film_rows, &b.film));
+    std::vector<int64_t> ts(rows[n_rows - 1].pos + 1);      // one FiLM row per visited timestep: the U sub-steps of a timestep share it (row.pos)
     {
         std::vector<InpaintRowDev> hr(n_rows);
-        for (int r = 0; r < n_rows; ++r) { hr[r] = row_dev_of(rows[r], r); hr[r].emit = premix && pg.panel_of[r] >= 0; }
+        for (int r = 0; r < n_rows; ++r) { hr[r] = row_dev_of(rows[r], r); hr[r].emit = premix && pg.panel_of[r] >= 0; ts[rows[r].pos] = rows[r].t; }
         InpaintLoopDev hl{d.y_dev, d.mask_dev, d.noise_n1_dev, d.noise_n2_dev, noise_back, d.noise_rp_dev, (unsigned long long)d.seed, (long long)d.image_offset,
                           premix ? e->progress_premix : nullptr};
         API_HIP(e, hipMemcpyAsync(rows_dev, hr.data(), sizeof(InpaintRowDev) * n_rows, hipMemcpyHostToDevice, e->stream));
         API_HIP(e, hipMemcpyAsync(lp, &hl, sizeof(hl), hipMemcpyHostToDevice, e->stream));
         API_HIP(e, hipStreamSynchronize(e->stream));
     }
-    if (b.film) {   // one FiLM row per visited timestep: the U sub-steps of a timestep share it (row.pos)
-        std::vector<int64_t> ts(n_pos);
-        for (int r = 0; r < n_rows; ++r) ts[rows[r].pos] = rows[r].t;
-        int* ts_dev = nullptr;
-        API_TRY(e, upload_ints(e, "loop#ts", ts.data(), n_pos, &ts_dev));
-        API_TRY(e, unet_film_table(e, ts_dev, n_pos, b.film));
-    }
-    ProxState none{};
-    API_TRY(e, loop_init(e, d, b, &none));                  // x from y's own noise level: sa_start / s1m_start (main_ddpir_inpainting.py:190-193)
-    hipStream_t s = e->stream;
-    if (d.generate_mode == 1) {                             // the first sub-step's mix (:244-246); every later one is applied by the sub-step before it
-        ProfScope ps(&e->prof, PC_ELEM);
-        const float* nr = d.noise_rp_dev;
-        if (!nr) { API_TRY(e, launch_randn(s, b.n2, d.seed, 3, d.image_offset, B, (size_t)3 * H * W)); nr = b.n2; }
-        API_TRY(e, launch_repaint_mix(s, b.x, d.y_dev, d.mask_dev, nr, rows[0].sa_t, rows[0].s1m_t, total));
-    }
+    API_TRY(e, film_table(e, ts, &b.film));
+    API_TRY(e, loop_init(e, d, b, 0, d.mask_dev, nullptr));      // x from y's own noise level: sa_start / s1m_start (main_ddpir_inpainting.py:190-193)
+    if (d.generate_mode == 1) API_TRY(e, first_repaint_mix(e, d, b, rows[0].sa_t, rows[0].s1m_t));
     // one 16-byte access per lane needs every tensor behind lp aligned; the decision is baked into a captured graph, so it is part of its key
-    auto al = [](const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) == 0; };
-    const bool aligned = al(d.y_dev, 15) && al(d.mask_dev, 3) && al(d.noise_n1_dev, 15) && al(d.noise_n2_dev, 15) && al(noise_back, 15) && al(d.noise_rp_dev, 15);
+    const bool aligned = aligned16(d.y_dev) && aligned4(d.mask_dev) && aligned16(d.noise_n1_dev) && aligned16(d.noise_n2_dev) && aligned16(noise_back) &&
+                         aligned16(d.noise_rp_dev);
     InpaintStepArgs a{};
     a.x = b.x; a.eps = b.out6; a.eps_ch = e->net.desc.out_channels; a.mode = d.generate_mode; a.guidance = d.guidance;
     a.device_noise = host ? 0 : 1; a.row = cur; a.lp = lp; a.B = B; a.HW = H * W; a.cus = e->cus; a.scalar_only = aligned ? 0 : 1;
-    const StepDev* cur_st = &cur->st;
-    auto data_pass = [&]() -> Status {
+
+    StepLoop L{n_rows, rows_dev, cur, sizeof(InpaintRowDev)};
+    // repaint: a row that mixed the next one in left its own x in the scratch image
+    L.panel_x = [&](int r) { return premix && rows[r].mix_next ? e->progress_premix : b.x; };
+    // the dead final evaluation is skipped, the next row's mix is not: it reaches x_0
+    L.slot_of = [&](int r) { return !(rows[r].last && d.skip_dead_final_eval) ? 0 : d.generate_mode == 1 && rows[r].mix_next ? (int)ROW_DATA_ONLY : (int)ROW_SKIP; };
+    L.data_pass = [&]() -> Status {
         ProfScope ps(&e->prof, PC_ELEM);
-        return launch_inpaint_step(s, a);
+        return launch_inpaint_step(e->stream, a);
     };
-    auto sub_step = [&]() -> Status {
-        if (!b.film) hipLaunchKernelGGL(fill_t_kernel, dim3((B + 255) / 256), dim3(256), 0, s, b.t_dev, cur_st, B);
-        DPIR_TRY(unet_forward(e, b.x, b.t_dev, b.y_dev, b.out6, B, H, W, b.film, b.film ? cur_st : nullptr));
-        return data_pass();
+    L.step = [&](int) -> Status {
+        DPIR_TRY(denoise(e, b, &cur->st));
+        return L.data_pass();
     };
-    hipGraphExec_t g = nullptr;
-    // the panel of row r - 1 when row r begins (or before finalize): a row skipped as dead yields its panel too.  Repaint: a row that mixed the
-    // next one in left its own x in the scratch image
-    auto emit = [&](int r) -> Status {
-        return progress_emit(e, r, r >= 0 && premix && rows[r].mix_next ? e->progress_premix : b.x, d);
+    L.key_of = [&](int) {
+        dpir_engine::GraphKey k{};
+        k.task = d.task; k.B = B; k.H = H; k.W = W; k.sf = 1; k.generate_mode = d.generate_mode;
+        k.kind = aligned ? 1 : 0;
+        k.host_n1 = d.noise_n1_dev != nullptr; k.host_n2 = host; k.host_rp = d.noise_rp_dev != nullptr;
+        k.has_labels = d.labels_host != nullptr;
+        k.guidance = d.guidance; k.loop = 1;
+        return k;
     };
-    for (int r = 0; r < n_rows; ++r) {
-        API_TRY(e, emit(r - 1));
-        const bool last = rows[r].last != 0;
-        const bool dead = last && d.skip_dead_final_eval;
-        if (dead && !(d.generate_mode == 1 && rows[r].mix_next)) continue;
-        API_HIP(e, hipMemcpyAsync(cur, rows_dev + r, sizeof(InpaintRowDev), hipMemcpyDeviceToDevice, s));
-        if (dead) { API_TRY(e, data_pass()); continue; }        // the dead evaluation is skipped, the next row's mix is not: it reaches x_0
-        if (!d.use_graph) { API_TRY(e, sub_step()); continue; }
-        if (!g) {
-            dpir_engine::GraphKey k{};
-            k.task = d.task; k.B = B; k.H = H; k.W = W; k.sf = 1; k.generate_mode = d.generate_mode;
-            k.kind = aligned ? 1 : 0;
-            k.host_n1 = d.noise_n1_dev != nullptr; k.host_n2 = host; k.host_rp = d.noise_rp_dev != nullptr;
-            k.has_labels = d.labels_host != nullptr;
-            k.guidance = d.guidance; k.loop = 1;
-            bool ran = false;
-            if (int rc = cached_step_graph(e, k, sub_step, nullptr, nullptr, &g, &ran)) return rc;
-            if (ran) continue;   // this sub-step was executed eagerly
-        }
-        ProfScope ps(&e->prof, PC_LOOP);
-        API_HIP(e, hipGraphLaunch(g, s));
-    }
-    API_TRY(e, emit(n_rows - 1));
-    {
-        ProfScope ps(&e->prof, PC_ELEM);
-        API_TRY(e, launch_finalize(s, b.x, out_f32, out_u8, B, H * W));
-    }
-    return DPIR_OK;
+    return run_steps(e, d, b, L, out_f32, out_u8);
 }
 
 int dpir_run_inpaint_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_inpaint_row* rows, int n_rows, const float* noise_back,
@@ -1333,122 +1385,77 @@ int dpir_ancestral_step(dpir_engine* e, float* x, const float* out6, int out_ch,
 static int run_ancestral_loop_once(dpir_engine* e, const dpir_loop_desc* dd, const dpir_ancestral_row* rows, int n_rows, const float* noise_ps,
                                    float* out_f32, uint8_t* out_u8) {
     if (!e || !dd || !rows || n_rows <= 0) return fail(e, invalid("dpir_run_ancestral_loop: null argument"));
-    (void)hipSetDevice(e->device);
     const dpir_loop_desc& d = *dd;
-    if (!e->net.loaded) return fail(e, Status{DPIR_ERR_STATE, "dpir_load_unet has not been called"});
-    API_TRY(e, check_shape("dpir_run_ancestral_loop", d.B, d.H, d.W));
-    if (d.task != DPIR_TASK_INPAINT || d.sf != 1)
-        return fail(e, invalid("dpir_run_ancestral_loop: task must be inpainting, sf 1 (main_ddpir.py:355-366 updates x from 'pred_x_prev' for inpainting only)"));
-    if (!d.y_dev || !d.mask_dev) return fail(e, invalid("dpir_run_ancestral_loop: y and mask are required"));
-    if (d.generate_mode != 1 && d.generate_mode != 2)
-        return fail(e, invalid("dpir_run_ancestral_loop: generate_mode must be 1 (repaint) or 2 (vanilla); DiffPIR with pred_x_prev reads an unbound tau at main_ddpir.py:417"));
-    if (e->net.desc.out_channels != 6) return fail(e, Status{DPIR_ERR_UNSUPPORTED, std::string("dpir_run_ancestral_loop: ") + kNeedsLearnSigma});
-    if ((e->net.desc.num_classes > 0) != (d.labels_host != nullptr)) return fail(e, invalid("labels iff class-conditional model"));
-    const int B = d.B, H = d.H, W = d.W;
-    const size_t total = (size_t)B * 3 * H * W;
     const bool host = noise_ps != nullptr;
     const bool repaint = d.generate_mode == 1;
-    for (int r = 0; r < n_rows; ++r)
-        if ((rows[r].mix_next != 0) != (r + 1 < n_rows)) return fail(e, invalid("dpir_run_ancestral_loop: mix_next must be 1 on every row but the last"));
-    if (host) {
-        if (!d.noise_init_dev) return fail(e, invalid("dpir_run_ancestral_loop: host noise needs noise_init_dev"));
-        if (repaint && !d.noise_rp_dev) return fail(e, invalid("dpir_run_ancestral_loop: repaint with host noise needs noise_rp_dev"));
-    } else if (d.noise_init_dev || d.noise_rp_dev) {
-        return fail(e, invalid("dpir_run_ancestral_loop: host noise needs noise_ps_dev (all null selects device noise)"));
-    }
-    API_TRY(e, progress_check(e, "dpir_run_ancestral_loop", n_rows, d));
-    // repaint: the fused pass mixes the next step's known region into x before x reaches memory, so the rows that own a panel also write the
-    // pre-mix x to a scratch image, which the snapshot then reads (as dpir_run_inpaint_loop)
+    LoopCall c{"dpir_run_ancestral_loop", n_rows, "row", {}};       // no row is final: the loop has no dead step
+    c.mode_lo = 1; c.modes = "1 (repaint) or 2 (vanilla); DiffPIR with pred_x_prev reads an unbound tau at main_ddpir.py:417";
+    c.t = true;
+    c.own = [&]() -> Status {
+        DPIR_TRY(check_shape("dpir_run_ancestral_loop", d.B, d.H, d.W));
+        if (d.task != DPIR_TASK_INPAINT || d.sf != 1)
+            return invalid("dpir_run_ancestral_loop: task must be inpainting, sf 1 (main_ddpir.py:355-366 updates x from 'pred_x_prev' for inpainting only)");
+        if (!d.y_dev || !d.mask_dev) return invalid("dpir_run_ancestral_loop: y and mask are required");
+        if (e->net.desc.out_channels != 6) return Status{DPIR_ERR_UNSUPPORTED, std::string("dpir_run_ancestral_loop: ") + kNeedsLearnSigma};
+        for (int r = 0; r < n_rows; ++r)
+            if ((rows[r].mix_next != 0) != (r + 1 < n_rows)) return invalid("dpir_run_ancestral_loop: mix_next must be 1 on every row but the last");
+        if (host) {
+            if (!d.noise_init_dev) return invalid("dpir_run_ancestral_loop: host noise needs noise_init_dev");
+            if (repaint && !d.noise_rp_dev) return invalid("dpir_run_ancestral_loop: repaint with host noise needs noise_rp_dev");
+        } else if (d.noise_init_dev || d.noise_rp_dev) {
+            return invalid("dpir_run_ancestral_loop: host noise needs noise_ps_dev (all null selects device noise)");
+        }
+        return Status{};
+    }();
+    LoopBufs b{};
+    if (int rc = loop_prologue(e, c, d, &b)) return rc;
+    const int B = d.B, H = d.H, W = d.W;
     const dpir_engine::Progress& pg = e->progress;
     const bool premix = pg.armed && repaint;
-    if (premix && e->progress_premix_bytes < total * sizeof(float)) {
-        API_HIP(e, hipStreamSynchronize(e->stream));
-        if (e->progress_premix) (void)hipFree(e->progress_premix);
-        e->progress_premix = nullptr; e->progress_premix_bytes = 0;
-        API_HIP(e, hipMalloc((void**)&e->progress_premix, total * sizeof(float)));
-        e->progress_premix_bytes = total * sizeof(float);
-    }
-    range_clear(e);
-    LoopBufs b{};
+    if (premix) API_TRY(e, ensure_premix(e, (size_t)B * 3 * H * W));
     AncestralRowDev *rows_dev = nullptr, *cur = nullptr;
     AncestralLoopDev* lp = nullptr;
-    API_TRY(e, e->ws.getT("loop#x", total, &b.x));
-    API_TRY(e, e->ws.getT("loop#out6", (size_t)B * 6 * H * W, &b.out6));
-    API_TRY(e, e->ws.getT("loop#n2", total, &b.n2));        // the init draw and the first repaint mix (device noise); the steps draw in place
-    API_TRY(e, e->ws.getT("loop#t", (size_t)B, &b.t_dev));
     API_TRY(e, e->ws.getT("ancestral#rows", (size_t)n_rows, &rows_dev));
     API_TRY(e, e->ws.getT("ancestral#cur", (size_t)1, &cur));
     API_TRY(e, e->ws.getT("ancestral#lp", (size_t)1, &lp));
-    API_TRY(e, upload_ints(e, "loop#y", d.labels_host, B, &b.y_dev));
-    const bool hoist_film = e->net.desc.num_classes == 0;
-    if (hoist_film) API_TRY(e, e->ws.getT("loop#film", (size_t)n_rows * e->net.film_rows, &b.film));
+    std::vector<int64_t> ts(n_rows);        // one FiLM row per step
     {
         std::vector<AncestralRowDev> hr(n_rows);
-        for (int r = 0; r < n_rows; ++r) { hr[r] = ancestral_row_dev_of(rows[r], r); hr[r].emit = premix && pg.panel_of[r] >= 0; }
+        for (int r = 0; r < n_rows; ++r) { hr[r] = ancestral_row_dev_of(rows[r], r); hr[r].emit = premix && pg.panel_of[r] >= 0; ts[r] = rows[r].t; }
         AncestralLoopDev hl{d.y_dev, d.mask_dev, noise_ps, d.noise_rp_dev, (unsigned long long)d.seed, (long long)d.image_offset,
                             premix ? e->progress_premix : nullptr};
         API_HIP(e, hipMemcpyAsync(rows_dev, hr.data(), sizeof(AncestralRowDev) * n_rows, hipMemcpyHostToDevice, e->stream));
         API_HIP(e, hipMemcpyAsync(lp, &hl, sizeof(hl), hipMemcpyHostToDevice, e->stream));
         API_HIP(e, hipStreamSynchronize(e->stream));
     }
-    if (b.film) {   // one FiLM row per step
-        std::vector<int64_t> ts(n_rows);
-        for (int r = 0; r < n_rows; ++r) ts[r] = rows[r].t;
-        int* ts_dev = nullptr;
-        API_TRY(e, upload_ints(e, "loop#ts", ts.data(), n_rows, &ts_dev));
-        API_TRY(e, unet_film_table(e, ts_dev, n_rows, b.film));
-    }
-    ProxState none{};
-    API_TRY(e, loop_init(e, d, b, &none));                  // main_ddpir.py:312-315
-    hipStream_t s = e->stream;
-    if (repaint) {                                          // the first step's mix (:356-358); every later one is applied by the step before it
-        ProfScope ps(&e->prof, PC_ELEM);
-        const float* nr = d.noise_rp_dev;
-        if (!nr) { API_TRY(e, launch_randn(s, b.n2, d.seed, 3, d.image_offset, B, (size_t)3 * H * W)); nr = b.n2; }
-        API_TRY(e, launch_repaint_mix(s, b.x, d.y_dev, d.mask_dev, nr, rows[0].sa_t, rows[0].s1m_t, total));
-    }
+    API_TRY(e, film_table(e, ts, &b.film));
+    API_TRY(e, loop_init(e, d, b, 0, d.mask_dev, nullptr));      // main_ddpir.py:312-315
+    if (repaint) API_TRY(e, first_repaint_mix(e, d, b, rows[0].sa_t, rows[0].s1m_t));
     // one 16-byte access per lane needs every tensor behind lp aligned; the decision is baked into a captured graph, so it is part of its key
-    auto al = [](const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) == 0; };
-    const bool aligned = al(d.y_dev, 15) && al(d.mask_dev, 3) && al(noise_ps, 15) && al(d.noise_rp_dev, 15);
+    const bool aligned = aligned16(d.y_dev) && aligned4(d.mask_dev) && aligned16(noise_ps) && aligned16(d.noise_rp_dev);
     AncestralStepArgs a{};
     a.x = b.x; a.out6 = b.out6; a.mode = d.generate_mode; a.ddim = d.ddim_sample ? 1 : 0;
     a.device_noise = host ? 0 : 1; a.row = cur; a.lp = lp; a.B = B; a.HW = H * W; a.cus = e->cus; a.scalar_only = aligned ? 0 : 1;
-    const StepDev* cur_st = &cur->st;
-    auto step = [&]() -> Status {
-        if (!b.film) hipLaunchKernelGGL(fill_t_kernel, dim3((B + 255) / 256), dim3(256), 0, s, b.t_dev, cur_st, B);
-        DPIR_TRY(unet_forward(e, b.x, b.t_dev, b.y_dev, b.out6, B, H, W, b.film, b.film ? cur_st : nullptr));
+
+    StepLoop L{n_rows, rows_dev, cur, sizeof(AncestralRowDev)};
+    // repaint: a row that mixed the next one in left its own x in the scratch image
+    L.panel_x = [&](int r) { return premix && rows[r].mix_next ? e->progress_premix : b.x; };
+    L.slot_of = [](int) { return 0; };
+    L.step = [&](int) -> Status {
+        DPIR_TRY(denoise(e, b, &cur->st));
         ProfScope ps(&e->prof, PC_ELEM);
-        return launch_ancestral_step(s, a);
+        return launch_ancestral_step(e->stream, a);
     };
-    hipGraphExec_t g = nullptr;
-    // the panel of row r - 1 when row r begins (or before finalize).  Repaint: a row that mixed the next one in left its own x in the scratch image
-    auto emit = [&](int r) -> Status {
-        return progress_emit(e, r, r >= 0 && premix && rows[r].mix_next ? e->progress_premix : b.x, d);
+    L.key_of = [&](int) {
+        dpir_engine::GraphKey k{};
+        k.task = d.task; k.B = B; k.H = H; k.W = W; k.sf = 1; k.generate_mode = d.generate_mode;
+        k.kind = (aligned ? 1 : 0) | (d.ddim_sample ? 2 : 0);
+        k.host_n2 = host; k.host_rp = d.noise_rp_dev != nullptr;
+        k.has_labels = d.labels_host != nullptr;
+        k.loop = 2;
+        return k;
     };
-    for (int r = 0; r < n_rows; ++r) {
-        API_TRY(e, emit(r - 1));
-        API_HIP(e, hipMemcpyAsync(cur, rows_dev + r, sizeof(AncestralRowDev), hipMemcpyDeviceToDevice, s));
-        if (!d.use_graph) { API_TRY(e, step()); continue; }
-        if (!g) {
-            dpir_engine::GraphKey k{};
-            k.task = d.task; k.B = B; k.H = H; k.W = W; k.sf = 1; k.generate_mode = d.generate_mode;
-            k.kind = (aligned ? 1 : 0) | (d.ddim_sample ? 2 : 0);
-            k.host_n2 = host; k.host_rp = d.noise_rp_dev != nullptr;
-            k.has_labels = d.labels_host != nullptr;
-            k.loop = 2;
-            bool ran = false;
-            if (int rc = cached_step_graph(e, k, step, nullptr, nullptr, &g, &ran)) return rc;
-            if (ran) continue;   // this step was executed eagerly
-        }
-        ProfScope ps(&e->prof, PC_LOOP);
-        API_HIP(e, hipGraphLaunch(g, s));
-    }
-    API_TRY(e, emit(n_rows - 1));
-    {
-        ProfScope ps(&e->prof, PC_ELEM);
-        API_TRY(e, launch_finalize(s, b.x, out_f32, out_u8, B, H * W));
-    }
-    return DPIR_OK;
+    return run_steps(e, d, b, L, out_f32, out_u8);
 }
 
 int dpir_run_ancestral_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_ancestral_row* rows, int n_rows, const float* noise_ps,
@@ -1572,7 +1579,7 @@ int dpir_p_sample(dpir_engine* e, const float* x_dev, int t, const dpir_psample_
     if (!e || !x_dev || !c || !noise_dev || !xt_out_dev || !x0_out_dev || B <= 0 || H <= 0 || W <= 0) return fail(e, invalid("dpir_p_sample: bad argument"));
     (void)hipSetDevice(e->device);
     if (!e->net.loaded) return fail(e, Status{DPIR_ERR_STATE, "dpir_load_unet has not been called"});
-    if ((e->net.desc.num_classes > 0) != (y_host != nullptr)) return fail(e, invalid("labels iff class-conditional model"));
+    API_TRY(e, labels_match(e, y_host));
     range_clear(e);
     int *t_dev = nullptr, *y_dev = nullptr;
     float* out6 = nullptr;
@@ -1637,52 +1644,39 @@ int dpir_grad_and_value(dpir_engine* e, int through_network, const float* x_hat_
     return grad_and_value_impl(e, through_network, x_hat_dev, measurement_dev, op, norm_grad_out_dev, norm_out_dev, B, H, W);
 }
 
-// What both whole-loop entries of the gradient modes refuse ahead of their own task / shape checks
+// What both whole-loop entries of the gradient modes refuse ahead of their own task / shape checks (and behind "no model")
 static Status grad_loop_ready(dpir_engine* e, int variant) {
-    if (!e->net.loaded) return Status{DPIR_ERR_STATE, "dpir_load_unet has not been called"};
     if (variant == 0 && !e->grad_enabled) return Status{DPIR_ERR_STATE, "DPS_y0 needs gradient mode: dpir_enable_grad before dpir_load_unet"};
     return Status{};
 }
 
 // The loop of the gradient modes over the operator of `op`: the body of dpir_run_dps_loop (main_ddpir.py:291-470) and dpir_run_deblur_grad_loop
-// (main_ddpir_deblur.py:228-360), which have checked the task, the shape and the variants they admit.  The operator decides the image the initial
-// x is noised from (bicubic up-sampling of y | y), the measurement ((2y - 1) and sa_t (2y - 1) + s1m_t n | y and that / 2 + 0.5), the extent of
-// the y_t draw and whether the norm is the batch's or each image's.  Eager launches, no step graph.
-static int run_grad_loop(dpir_engine* e, const char* entry, const dpir_loop_desc& d, const dpir_step* steps, const dpir_dps_coef* coefs, int n_steps,
-                         int variant, float lambda_, const float* noise_ps_dev, const float* noise_yt_dev, float step_scale, const GradOp& op,
+// (main_ddpir_deblur.py:228-360), which pass what they refuse about the task, the shape and the variants they admit as `own`.  The operator decides
+// the image the initial x is noised from (bicubic up-sampling of y | y), the measurement ((2y - 1) and sa_t (2y - 1) + s1m_t n | y and that / 2 + 0.5),
+// the extent of the y_t draw and whether the norm is the batch's or each image's.  Eager launches, no step graph: only the head, the
+// initialisation and the tail are the other loops'.
+static int run_grad_loop(dpir_engine* e, const char* entry, const Status& own, const dpir_loop_desc& d, const dpir_step* steps, const dpir_dps_coef* coefs,
+                         int n_steps, int variant, float lambda_, const float* noise_ps_dev, const float* noise_yt_dev, float step_scale, const GradOp& op,
                          float* out_f32, uint8_t* out_u8) {
-    if ((e->net.desc.num_classes > 0) != (d.labels_host != nullptr)) return fail(e, invalid("labels iff class-conditional model"));
-    API_TRY(e, progress_check(e, entry, n_steps, d));
-    const int B = d.B, H = d.H, W = d.W, oc = e->net.desc.out_channels, images = op.norm_images(B);
-    const size_t total = (size_t)B * 3 * H * W, small = op.measurement_count(B, H, W);
     bool with_n1 = false;
+    LoopCall c{entry, n_steps, "step", std::vector<char>(n_steps)};
     for (int i = 0; i < n_steps; ++i) {
-        if (i > 0 && steps[i - 1].last && !steps[i].last) return fail(e, invalid(std::string(entry) + ": a non-final step may not follow a final step"));
+        c.last[i] = steps[i].last != 0;
         if (variant == 2 && !steps[i].last && steps[i].es != 0.f) with_n1 = true;
     }
-    if (with_n1 && d.noise_n2_dev && !d.noise_n1_dev) return fail(e, invalid(std::string(entry) + ": eta != 0 with host noise needs noise_n1_dev"));
-    hipStream_t s = e->stream;
-    range_clear(e);
+    c.modes = nullptr; c.x0 = true; c.n1 = with_n1; c.init = !op.k;
+    c.own = own;
+    if (own.ok() && with_n1 && d.noise_n2_dev && !d.noise_n1_dev) c.own = invalid(std::string(entry) + ": eta != 0 with host noise needs noise_n1_dev");
     LoopBufs b{};
+    if (int rc = loop_prologue(e, c, d, &b)) return rc;
+    const int B = d.B, H = d.H, W = d.W, oc = e->net.desc.out_channels, images = op.norm_images(B);
+    const size_t total = (size_t)B * 3 * H * W, small = op.measurement_count(B, H, W);
+    hipStream_t s = e->stream;
     float* xprev = nullptr;
-    API_TRY(e, e->ws.getT("loop#x", total, &b.x));
-    API_TRY(e, e->ws.getT("loop#x0", total, &b.x0));
-    API_TRY(e, e->ws.getT("loop#out6", (size_t)B * oc * H * W, &b.out6));
-    API_TRY(e, e->ws.getT("loop#n2", total, &b.n2));
-    if (with_n1) API_TRY(e, e->ws.getT("loop#n1", total, &b.n1));
-    if (!op.k) API_TRY(e, e->ws.getT("loop#init", total, &b.init_src));
     API_TRY(e, e->ws.getT("dps#xprev", total, &xprev));
-    API_TRY(e, upload_ints(e, "loop#y", d.labels_host, B, &b.y_dev));
     // init: the Resizer noises the bicubic up-sampling of y to t_start (main_ddpir.py:293-315); the deblurring program noises y itself from its own
-    // level t_y up to t_start (main_ddpir_deblur.py:228-231).  The two coefficients come from the host either way
-    {
-        ProfScope ps(&e->prof, PC_ELEM);
-        const float* src = d.y_dev;
-        if (!op.k) { API_TRY(e, launch_bicubic_up(s, d.y_dev, b.init_src, B * 3, H / op.sf, W / op.sf, op.sf)); src = b.init_src; }
-        const float* n0 = d.noise_init_dev;
-        if (!n0) { API_TRY(e, launch_randn(s, b.n2, d.seed, 0, d.image_offset, B, (size_t)3 * H * W)); n0 = b.n2; }
-        API_TRY(e, launch_init_x(s, src, nullptr, n0, d.sa_start, d.s1m_start, b.x, total));
-    }
+    // level t_y up to t_start (main_ddpir_deblur.py:228-231): no mask, and no spectra although its task is deblur
+    API_TRY(e, loop_init(e, d, b, op.k ? 0 : op.sf, nullptr, nullptr));
     for (int i = 0; i < n_steps; ++i) {
         API_TRY(e, progress_emit(e, i - 1, b.x, d));     // the panel of step i - 1: x after its update
         const dpir_step& st = steps[i];
@@ -1743,12 +1737,7 @@ static int run_grad_loop(dpir_engine* e, const char* entry, const dpir_loop_desc
         API_TRY(e, dps_grad_through_network(e, gup, normv, &direct, &dxn, images != 0));
         API_TRY(e, launch_dps_update(s, xprev, direct, dxn, step_scale, b.x, nullptr, total));
     }
-    API_TRY(e, progress_emit(e, n_steps - 1, b.x, d));
-    {
-        ProfScope ps(&e->prof, PC_ELEM);
-        API_TRY(e, launch_finalize(s, b.x, out_f32, out_u8, B, H * W));
-    }
-    return DPIR_OK;
+    return loop_finish(e, d, b, n_steps, b.x, out_f32, out_u8);
 }
 
 int dpir_run_dps_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step* steps, const dpir_dps_coef* coefs, int n_steps,
@@ -1757,15 +1746,17 @@ int dpir_run_dps_loop(dpir_engine* e, const dpir_loop_desc* dd, const dpir_step*
     ProgressOneShot one_shot{e};
     if (!e || !dd || !steps || !coefs || n_steps <= 0) return fail(e, invalid("dpir_run_dps_loop: null argument"));
     if (variant != 0 && variant != 1) return fail(e, invalid("dpir_run_dps_loop: variant must be 0 (DPS_y0) or 1 (DPS_yt)"));
-    (void)hipSetDevice(e->device);
     const dpir_loop_desc& d = *dd;
-    API_TRY(e, grad_loop_ready(e, variant));
-    if (d.task != DPIR_TASK_SR_BLUR && d.task != DPIR_TASK_SR_CUBIC)
-        return fail(e, Status{DPIR_ERR_UNSUPPORTED, "DPS_y0 is implemented for the super-resolution tasks (the reference's deblurring operator raises at "
-                                                    "main_ddpir.py:302 and its inpainting branch never defines xt)"});
-    if (d.B <= 0 || d.H <= 0 || d.W <= 0 || d.sf < 1 || d.H % d.sf || d.W % d.sf || !d.y_dev) return fail(e, invalid("dpir_run_dps_loop: bad shape"));
+    const Status own = [&]() -> Status {
+        DPIR_TRY(grad_loop_ready(e, variant));
+        if (d.task != DPIR_TASK_SR_BLUR && d.task != DPIR_TASK_SR_CUBIC)
+            return Status{DPIR_ERR_UNSUPPORTED, "DPS_y0 is implemented for the super-resolution tasks (the reference's deblurring operator raises at "
+                                                "main_ddpir.py:302 and its inpainting branch never defines xt)"};
+        if (d.B <= 0 || d.H <= 0 || d.W <= 0 || d.sf < 1 || d.H % d.sf || d.W % d.sf || !d.y_dev) return invalid("dpir_run_dps_loop: bad shape");
+        return Status{};
+    }();
     GradOp op; op.sf = d.sf;
-    return run_grad_loop(e, "dpir_run_dps_loop", d, steps, coefs, n_steps, variant, lambda_, noise_ps_dev, noise_yt_dev, step_scale, op, out_f32, out_u8);
+    return run_grad_loop(e, "dpir_run_dps_loop", own, d, steps, coefs, n_steps, variant, lambda_, noise_ps_dev, noise_yt_dev, step_scale, op, out_f32, out_u8);
 }
 
 // ------------------------------------------------------------------------------------------ deblurring program: blur operator + gradient modes
@@ -1801,15 +1792,16 @@ int dpir_run_deblur_grad_loop(dpir_engine* e, const dpir_loop_desc* dd, const dp
     if (!e || !dd || !steps || n_steps <= 0) return fail(e, invalid("dpir_run_deblur_grad_loop: null argument"));
     if (variant < 0 || variant > 2) return fail(e, invalid("dpir_run_deblur_grad_loop: variant must be 0 (DPS_y0), 1 (DPS_yt) or 2 (first-order data step)"));
     if (variant != 2 && !coefs) return fail(e, invalid("dpir_run_deblur_grad_loop: the DPS variants need the p_sample coefficients"));
-    (void)hipSetDevice(e->device);
     const dpir_loop_desc& d = *dd;
-    API_TRY(e, grad_loop_ready(e, variant));
-    if (d.task != DPIR_TASK_DEBLUR || d.sf != 1) return fail(e, invalid("dpir_run_deblur_grad_loop: the deblurring program runs task deblur (sf 1) only"));
-    if (!d.y_dev || !d.k_dev) return fail(e, invalid("dpir_run_deblur_grad_loop: y and the PSF are required"));
-    API_TRY(e, blur_check("dpir_run_deblur_grad_loop", d.kh, d.kw, d.B, d.H, d.W));
+    const Status own = [&]() -> Status {
+        DPIR_TRY(grad_loop_ready(e, variant));
+        if (d.task != DPIR_TASK_DEBLUR || d.sf != 1) return invalid("dpir_run_deblur_grad_loop: the deblurring program runs task deblur (sf 1) only");
+        if (!d.y_dev || !d.k_dev) return invalid("dpir_run_deblur_grad_loop: y and the PSF are required");
+        return blur_check("dpir_run_deblur_grad_loop", d.kh, d.kw, d.B, d.H, d.W);
+    }();
     GradOp op; op.k = d.k_dev; op.K = d.kh;
     // the program's DPS_y0 update is a unit step (main_ddpir_deblur.py:326)
-    return run_grad_loop(e, "dpir_run_deblur_grad_loop", d, steps, coefs, n_steps, variant, lambda_, noise_ps_dev, noise_yt_dev, 1.f, op, out_f32, out_u8);
+    return run_grad_loop(e, "dpir_run_deblur_grad_loop", own, d, steps, coefs, n_steps, variant, lambda_, noise_ps_dev, noise_yt_dev, 1.f, op, out_f32, out_u8);
 }
 
 // ------------------------------------------------------------------------------------------ profiling

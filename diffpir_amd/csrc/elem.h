@@ -29,6 +29,18 @@ struct LoopDev {
 // the per-image row of image n at the current step
 __device__ __forceinline__ float4 image_row(const StepDev* sp, const LoopDev* lp, size_t n) { return lp->img[(size_t)sp->i * lp->B + n]; }
 
+// Launcher helpers of the fused per-row passes (inpaint.hip, ancestral.hip) and of the loops that decide for the tensors behind their device block
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }       // a uint8 mask read four bytes at a time
+// memory-bound pass over B images of q float4 each: no more workgroups than the device keeps resident (8 x 256 threads per CU), the rest by grid stride
+inline dim3 resident_grid(size_t q, int B, int cus) {
+    const size_t cap = (size_t)(cus > 0 ? cus : 256) * 8;
+    const unsigned gy = (unsigned)(B < 65535 ? B : 65535);
+    size_t gx = (q + 255) / 256, per_image = cap / gy ? cap / gy : 1;
+    if (gx > per_image) gx = per_image;
+    return dim3((unsigned)gx, gy);
+}
+
 Status launch_xstart(hipStream_t s, const float* x, const float* out6, int out_ch, float c1, float c2, float* x0, int B, int HW, const StepDev* sp = nullptr);
 // per_image (here and below; needs sp and lp): the per-image instantiation, which reads tau / k1 / k2 / the Philox image number from lp->img / lp->imgidx
 Status launch_prox_mask(hipStream_t s, float* x0, const float* y, const uint8_t* mask, float tau, float g, size_t total, const StepDev* sp = nullptr,

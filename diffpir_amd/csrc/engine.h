@@ -115,11 +115,15 @@ struct dpir_engine {
     // mode fields below and the workspace generation; per-batch pointers, seed and image offset live in a device block
     // (dpir::LoopDev), so every batch of a test set replays the same graph.  Entries are compared field by field on a
     // hit (no hash-only match) and the cache is capped (least recently used entry is destroyed).
+    // `loop` says whose step the graph holds, so two loops never share an entry, and `kind` is read per loop (each loop's key_of in api.hip fills it):
+    //   loop 0, dpir_run_loop's step:               kind bit0 final step, bit1 eta draw (n1), bit2 first-order data step
+    //   loop 1, dpir_run_inpaint_loop's sub-step:   kind bit0 16-byte accesses to the tensors behind the device block
+    //   loop 2, dpir_run_ancestral_loop's step:     kind bit0 16-byte accesses, bit1 ddim_sample
     struct GraphKey {
-        int32_t task, B, H, W, sf, in_iter, generate_mode, kind;      // kind: bit0 final step, bit1 eta draw
+        int32_t task, B, H, W, sf, in_iter, generate_mode, kind;
         int32_t host_n1, host_n2, host_rp, has_labels;
         float gamma, guidance;
-        int32_t loop, loop_pad;      // 0: dpir_run_loop's step, 1: dpir_run_inpaint_loop's sub-step (kind bit0: 16-byte accesses), 2: dpir_run_ancestral_loop's step (kind bit0: 16-byte accesses, bit1: ddim)
+        int32_t loop, loop_pad;
         int32_t per_image, image_index;   // dpir_run_loop_per_image: a per-image scalar table / image-number table was given (per-image kernel instantiations)
         uint64_t ws_generation;
     };
